@@ -7,6 +7,8 @@
                                                         plumbing alone on gloo, no GPU work (a rehearsal line, not a measurement)
   python bench.py --config4 ...                        BASELINE config 4 preset: 128 pages per GPU
   python bench.py --mode dropin                        the drop-in path instead: B = 1, page at a time through the plugins
+  python bench.py ... --dump-outputs DIR              also write what the last timed step returned to DIR/*.npy (float32, <= 64 MB;
+                                                        same arguments, same inputs: two builds compare output for output)
 
 One *step* = one pass of the dense hot path over one batch of ``--pages`` synthetic pages per GPU (BASELINE config 3:
 64 pages, full detect -> OCR -> inpaint).  Pages, text-line quads and inpainting masks are resident in HBM before the
@@ -117,7 +119,14 @@ def parse(argv=None):
     ap.add_argument("--cpu-pages", type=int, default=3, help="timed pages of the CPU baseline (after 1 warm-up page)")
     ap.add_argument("--cpu-threads", default="8,16,32,64,128", help="thread counts swept per stage")
     ap.add_argument("--prof-dump", default="", help="write one CSV line per conv_gemm launch of the instrumented passes to this path (suffix .<stage>)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's pages) to DIR/<name>.npy in float32, "
+                         f"at most {DUMP_MAX_BYTES >> 20} MB in all (a fixed seeded sample of the large maps) + DIR/manifest.json")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.config1 or args.config5 or args.coupled_only or args.launch_rehearsal or args.mode != "batch"):
+        ap.error("--dump-outputs applies to the headline batch path only")
     if args.config4 or (args.pages is None and args.gpus == 8):
         args.pages = 128   # BASELINE config 4: 1024 pages over 8 GPUs; --gpus 8 without --pages IS that configuration
     if args.pages is None:
@@ -149,6 +158,58 @@ def make_inputs(n_pages, distinct, rank, device):
     masks_t = torch.from_numpy(np.stack([masks[i] for i in idx])).to(device)
     quad_objs = [pipeline.quads_from_array(quads[i]) for i in idx]
     return pages_t, quad_objs, masks_t, (pages, quads, masks), idx
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------------------------------
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20241225
+# Elements kept per array: a map larger than this is reduced to a sample of flat indices drawn without replacement by
+# np.random.default_rng(DUMP_SEED) (sorted), so the same shape gives the same sample in every run and every build.
+# 4M + 2 x 2M + 5 x 1M float32 = 52 MB at most.
+DUMP_MAX_ELEMS = {"inpainted": 4_000_000, "det_mask": 2_000_000, "det_shrink": 2_000_000}
+DUMP_MAX_ELEMS_OTHER = 1_000_000
+
+
+def dump_outputs(res, out_dir: str, lines_per_page: int = N_BOXES) -> dict:
+    """Write the arrays one ``PageEngine.run`` returned (``res``, a PageBatchResult) as ``out_dir/<name>.npy``, float32.
+
+    Every value is an integer below 2^24 or already float32, so the conversion is exact.  The OCR rows are put in (page, line)
+    order, whatever order the batched beam search returned them in (``ocr_page_line`` names each row).  Arrays above their
+    element cap (DUMP_MAX_ELEMS) are sampled at fixed seeded flat indices.  ``manifest.json`` records each array's source shape
+    and dtype and whether it was sampled.  Returns the manifest."""
+    arrays = {"det_mask": res.det_mask, "det_shrink": res.det_shrink, "inpainted": res.inpainted}
+    if res.ocr_tokens is not None:
+        keys = torch.tensor([p * lines_per_page + l for p, l in res.ocr_order], dtype=torch.long)
+        perm = torch.argsort(keys)
+        dev_perm = perm.to(res.ocr_tokens.device)
+        arrays.update(ocr_tokens=res.ocr_tokens[dev_perm], ocr_length=res.ocr_length[dev_perm], ocr_prob=res.ocr_prob[dev_perm],
+                      ocr_colors=res.ocr_colors[dev_perm], ocr_page_line=torch.tensor(res.ocr_order, dtype=torch.int32).reshape(-1, 2)[perm])
+    os.makedirs(out_dir, exist_ok=True)
+    manifest = {"seed": DUMP_SEED, "arrays": {}}
+    total = 0
+    for name, t in arrays.items():
+        cap = DUMP_MAX_ELEMS.get(name, DUMP_MAX_ELEMS_OTHER)
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "sampled": t.numel() > cap}
+        if entry["sampled"]:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), size=cap, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry["elements"] = cap
+        else:
+            a = t
+        a = a.float().cpu().numpy()
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        total += os.path.getsize(path)
+        manifest["arrays"][name] = entry
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs wrote {total} bytes, above the {DUMP_MAX_BYTES} byte budget")
+    manifest["bytes"] = total
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1141,6 +1202,8 @@ def main():
     D.barrier()
     torch.cuda.synchronize()
     dt = D.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:   # outside the timed region, before any later leg runs the engine again
+        dump_outputs(res, args.dump_outputs)
 
     roof = per_cfg = cpu = parity = dropin = fp32 = None
     leg_errors = {}

@@ -24,6 +24,8 @@ Fixtures (all small; each .npz also records the reference file whose code produc
   textline_merge.json  the line sets + expected groupings of the reference's test/test_textline_merge.py and the reference code's own output
   mask_refinement.npz  the reference's mask_refinement.dispatch / complete_mask on a synthetic page (DenseCRF + bilateralFilter stubbed)
   textline.npz     sort_pnts / Quadrilateral / get_transformed_region (utils/generic.py:324-481) on 12 quads
+  ref_schemas.json     parameter / buffer names and shapes of every reference module a synthetic state_dict layout mirrors
+  load_dump_image.npz  load_image / dump_image (utils/generic.py:223-249) on seeded RGB, RGBA, L and P pages
 """
 from __future__ import annotations
 
@@ -666,6 +668,66 @@ def golden_share_stream():
         json.dump(out, f, indent=1)
 
 
+def reference_schemas() -> dict:
+    """module -> {state_dict key: shape} of every reference module whose layout a synthetic schema restates (the ResNet-34 part
+    of the default detector is the oracle's own restatement of torchvision's module, unpinned)."""
+    def shapes(module_sd):
+        return {n: list(t.shape) for n, t in module_sd.items()}
+
+    m, _, _ = build_ref_lama(9, True)
+    m18, _, _ = build_ref_lama(18, False)
+    ocr, _ = build_ref_ocr()
+    bm, yolo = R.ctd()
+    ctc, _ = build_ref_ocr_ctc()
+    det, _ = build_ref_dbnet()
+    esr, _ = build_ref_esrgan(3)
+    return {"lama_generator_9": shapes(m.generator.state_dict()), "lama_mpe": shapes(m.mpe.state_dict()),
+            "lama_generator_18": shapes(m18.generator.state_dict()), f"ocr48_dict{OCR_DICT}": shapes(ocr.state_dict()),
+            "ctd_unet_head": shapes(bm.UnetHead(act="leaky").state_dict()), "ctd_db_head": shapes(bm.DBHead(64, act="leaky").state_dict()),
+            "ctd_yolov5s": shapes(yolo.Model(ctd_schema.YOLOV5S_CFG).state_dict()), f"ocr_ctc_dict{OCR_DICT}": shapes(ctc.state_dict()),
+            "dbnet": shapes(det.state_dict()), "esrgan_nb3": shapes(esr.state_dict())}
+
+
+def golden_schemas():
+    import json
+
+    with open(os.path.join(GOLDEN, "ref_schemas.json"), "w") as f:
+        json.dump(reference_schemas(), f, indent=0)
+        f.write("\n")
+
+
+def pil_pages():
+    """Seeded 20x28 pages in the four PIL modes load_image / dump_image treat differently (P with a transparent palette entry)."""
+    from PIL import Image
+
+    rng = np.random.default_rng(8)
+    rgb = Image.fromarray(rng.integers(0, 256, (20, 28, 3)).astype(np.uint8))
+    rgba = Image.fromarray(rng.integers(0, 256, (20, 28, 4)).astype(np.uint8), "RGBA")
+    grey = Image.fromarray(rng.integers(0, 256, (20, 28)).astype(np.uint8))
+    pal = rgb.convert("P", palette=Image.Palette.ADAPTIVE, colors=16)
+    pal.info["transparency"] = 3
+    return {"RGB": rgb, "RGBA": rgba, "L": grey, "P": pal}
+
+
+def load_dump_outputs(load_image, dump_image) -> dict:
+    """For every page of pil_pages(): what ``load_image`` returns (array, alpha when there is one) and what ``dump_image`` makes of
+    a result derived from that array."""
+    out = {}
+    for mode, page in pil_pages().items():
+        arr, alpha = load_image(page.copy())
+        out[f"{mode}_load"] = np.asarray(arr)
+        if alpha is not None:
+            out[f"{mode}_alpha"] = np.array(alpha)
+        res = (np.asarray(arr).astype(np.int32) // 2).astype(np.uint8)
+        out[f"{mode}_dump"] = np.array(dump_image(page, res.copy(), alpha))
+    return out
+
+
+def golden_load_dump_image():
+    G = R.generic()
+    np.savez_compressed(os.path.join(GOLDEN, "load_dump_image.npz"), **load_dump_outputs(G.load_image, G.dump_image))
+
+
 def main():
     if not R.available():
         raise SystemExit("/root/reference is not present: fixtures can only be regenerated in the build container")
@@ -687,6 +749,8 @@ def main():
     golden_boxes()
     golden_bubble()
     golden_share_stream()
+    golden_schemas()
+    golden_load_dump_image()
 
 
 if __name__ == "__main__":

@@ -177,3 +177,53 @@ def test_committed_stdout_of_a_driver_style_run_parses_from_an_8k_tail(path):
     assert d["metric"].startswith("pages/sec end-to-end") and d["value"] > 0 and d["roofline"]["frac"] > 0 and d["cpu_baseline"]["value"] > 0
     full = os.path.join(ROOT, "profiles", os.path.basename(path).replace("_headline", ""))
     assert json.load(open(full))["value"] == d["value"]
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_as_float32(tmp_path, monkeypatch):
+    """--dump-outputs: every array of a PageBatchResult as <name>.npy in float32, OCR rows in (page, line) order, large maps reduced to the
+    same seeded sample in every run, the whole dump within its byte budget."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from manga_image_translator_amd.pipeline import PageBatchResult
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", {"inpainted": 500, "det_mask": 5000, "det_shrink": 5000})
+    g = torch.Generator().manual_seed(3)
+    B, T = 2, 4
+    order = [(1, 0), (0, 1), (0, 0), (1, 2)]
+    res = PageBatchResult(det_mask=torch.randint(0, 256, (B, 16, 12), generator=g, dtype=torch.uint8),
+                          det_shrink=torch.randint(0, 2, (B, 16, 12), generator=g, dtype=torch.uint8),
+                          ocr_tokens=torch.randint(0, 6004, (4, T + 1), generator=g, dtype=torch.int32),
+                          ocr_length=torch.tensor([5, 3, 2, 4], dtype=torch.int32), ocr_prob=torch.rand(4, generator=g),
+                          ocr_colors=torch.rand(4, T, 10, generator=g), ocr_order=order,
+                          inpainted=torch.randint(0, 256, (B, 20, 14, 3), generator=g, dtype=torch.uint8))
+    m1 = bench.dump_outputs(res, str(tmp_path / "a"), lines_per_page=3)
+    m2 = bench.dump_outputs(res, str(tmp_path / "b"), lines_per_page=3)
+    assert m1 == m2 and m1["bytes"] <= bench.DUMP_MAX_BYTES
+    names = {"det_mask", "det_shrink", "inpainted", "ocr_tokens", "ocr_length", "ocr_prob", "ocr_colors", "ocr_page_line"}
+    assert set(m1["arrays"]) == names and {p.name for p in (tmp_path / "a").iterdir()} == {n + ".npy" for n in names} | {"manifest.json"}
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    for n in names:
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert np.array_equal(a["det_mask"], res.det_mask.float().numpy()) and not m1["arrays"]["det_mask"]["sampled"]
+    assert m1["arrays"]["inpainted"]["sampled"] and a["inpainted"].shape == (500,)
+    flat = res.inpainted.reshape(-1).float().numpy()
+    assert np.isin(a["inpainted"], flat).all() and not np.array_equal(a["inpainted"], flat[:500])
+    perm = [2, 1, 0, 3]                     # (0, 0), (0, 1), (1, 0), (1, 2)
+    assert a["ocr_page_line"].tolist() == [[0, 0], [0, 1], [1, 0], [1, 2]]
+    assert np.array_equal(a["ocr_tokens"], res.ocr_tokens[perm].float().numpy())
+    assert np.array_equal(a["ocr_colors"], res.ocr_colors[perm].numpy()) and np.array_equal(a["ocr_prob"], res.ocr_prob[perm].numpy())
+
+
+def test_steps_and_dump_outputs_arguments():
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "out"])
+    assert a.steps == 7 and a.warmup == 2 and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--config1", "--dump-outputs", "out"], ["--mode", "dropin", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)

@@ -2,6 +2,8 @@
 the numpy descriptor emulator (tests/_desc_emulator.py, the documented semantics of include/mit_hip.h), reproduce
 torch's conv2d / conv_transpose2d + eval BatchNorm + activation on the CPU.  The same descriptors are what the GPU
 kernel receives, so this pins packing, tap tables, padding modes, strided views and epilogue folding on their own."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -265,15 +267,9 @@ def test_rfft_row_plan_and_tables():
 
 
 def _pil_pages():
-    from PIL import Image
+    from oracle import make_golden as MG
 
-    rng = np.random.default_rng(8)
-    rgb = Image.fromarray(rng.integers(0, 256, (20, 28, 3)).astype(np.uint8))
-    rgba = Image.fromarray(rng.integers(0, 256, (20, 28, 4)).astype(np.uint8), "RGBA")
-    grey = Image.fromarray(rng.integers(0, 256, (20, 28)).astype(np.uint8))
-    pal = rgb.convert("P", palette=Image.Palette.ADAPTIVE, colors=16)
-    pal.info["transparency"] = 3
-    return {"RGB": rgb, "RGBA": rgba, "L": grey, "P": pal}
+    return MG.pil_pages()
 
 
 def test_load_and_dump_image_round_trip():
@@ -298,18 +294,17 @@ def test_load_and_dump_image_round_trip():
 
 
 def test_load_and_dump_image_match_the_reference_functions():
-    from oracle import ref_import as R
-
-    if not R.available():
-        pytest.skip("/root/reference not present")
+    """imgproc.load_image / dump_image against the reference's own functions (utils/generic.py:223-249): their outputs recorded in
+    tests/golden/load_dump_image.npz by oracle/make_golden.py, re-derived from the reference where the tree is present."""
     from manga_image_translator_amd import imgproc
+    from oracle import make_golden as MG, ref_import as R
 
-    G = R.generic()
-    for mode, page in _pil_pages().items():
-        a0, al0 = G.load_image(page.copy())
-        a1, al1 = imgproc.load_image(page.copy())
-        assert np.array_equal(a0, a1) and (al0 is None) == (al1 is None)
-        if al0 is not None:
-            assert np.array_equal(np.array(al0), np.array(al1))
-        res = (a0.astype(np.int32) // 2).astype(np.uint8)
-        assert np.array_equal(np.array(G.dump_image(page, res.copy(), al0)), np.array(imgproc.dump_image(page, res.copy(), al1)))
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "load_dump_image.npz"), allow_pickle=False)
+    sides = {"imgproc": MG.load_dump_outputs(imgproc.load_image, imgproc.dump_image)}
+    if R.available():
+        G = R.generic()
+        sides["reference"] = MG.load_dump_outputs(G.load_image, G.dump_image)
+    for side, got in sides.items():
+        assert sorted(got) == sorted(gold.files), side
+        for k in gold.files:
+            assert np.array_equal(got[k], gold[k]), (side, k)
