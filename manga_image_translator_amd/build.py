@@ -43,7 +43,7 @@ HIPCC_FLAGS = [
 # (profiles/r07h) —, the planar GEMM) and are checked by tests/test_build_flags.py to contain no packed-fp32 instruction with a
 # modifier; every other unit must contain none at all.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-PACKED_FP32_BY_DESIGN = {"conv_small_cout.hip", "pgemm.hip"} | {f"conv_gemm_inst{i}.hip" for i in range(8)}
+PACKED_FP32_BY_DESIGN = {"conv_small_cout.hip", "pgemm.hip"} | {f"conv_gemm_inst{i}.hip" for i in range(6)}
 
 
 # Kernel-argument preloading (gfx940+): the leading scalar arguments of a kernel arrive in user SGPRs with the wave instead of behind a scalar
@@ -59,12 +59,6 @@ def flags_for(src_name: str) -> list:
     if src_name in KERNARG_PRELOAD:
         f = f + ["-mllvm", f"-amdgpu-kernarg-preload-count={KERNARG_PRELOAD[src_name]}"]
     return f
-
-
-if os.environ.get("MIT_WITH_SLP"):  # A/B only: the build of rounds 1-4 (reproduces the co-tenancy failures)
-    HIPCC_FLAGS.remove("-fno-slp-vectorize")
-if os.environ.get("MIT_CONV_EXPERIMENTS"):  # rejected scheduling variants + timing ablations of the conv kernel (scripts/bench_conv.py)
-    HIPCC_FLAGS.append("-DMIT_CONV_EXPERIMENTS")
 
 
 def _hipcc() -> str:

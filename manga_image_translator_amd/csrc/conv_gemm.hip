@@ -67,15 +67,14 @@ bool buf_eligible(const MitConvGemm &p) {
     if (maxoff * 4 >= 0x80000000LL) return false;
     return (int64_t)3 * (p.Kw >> 3) * p.ldw * 16 < 0x80000000LL;
 }
-// the buffer-load twin of a shipped p6 tile ("...p6o" -> "...p6u"), or the tile itself (MIT_CONV_NO_BUF=1: A/B knob)
+// the buffer-load twin of a shipped p6 tile ("...p6o" -> "...p6u"), or the tile itself
 int buf_twin(int c) {
     static const std::vector<int> twin = [] {
         std::vector<int> t(kNumCfgs);
-        const bool off = getenv("MIT_CONV_NO_BUF") != nullptr;
         for (int i = 0; i < kNumCfgs; ++i) {
             t[i] = i;
             const std::string n = kCfgs[i].name;
-            if (!off && n.size() > 3 && n.compare(n.size() - 3, 3, "p6o") == 0) {
+            if (n.size() > 3 && n.compare(n.size() - 3, 3, "p6o") == 0) {
                 const int u = cfg_by_name((n.substr(0, n.size() - 1) + "u").c_str());
                 if (u >= 0) t[i] = u;
             }
@@ -126,24 +125,21 @@ int env_cfg(const char *name, const char *dflt_name) {  // tuning knob for scrip
     const char *v = getenv(name);
     if (!v || !*v) return dflt;
     const int c = cfg_by_name(v);
-    return (c >= 0 && (kCfgs[c].fast == 1 || kCfgs[c].fast == 2) && kCfgs[c].BK == 16) ? c : dflt;
+    return (c >= 0 && kCfgs[c].fast == 1 && kCfgs[c].BK == 16) ? c : dflt;
 }
 
 int pick_cfg(const MitConvGemm &p, int64_t M) {
     // measured on MI355X (scripts/bench_conv.py)
     static const int wide = env_cfg("MIT_CONV_TILE_WIDE", "fast128x128x16w4c"), narrow = env_cfg("MIT_CONV_TILE_NARROW", "fast128x64x16w5c");
     static const int m192 = env_cfg("MIT_CONV_TILE_M192", "fast192x64x16w4c"), bigk = env_cfg("MIT_CONV_TILE_BIGK", nullptr);
-    static const int wide_l = env_cfg("MIT_CONV_TILE_WIDE_L", nullptr), narrow_l = env_cfg("MIT_CONV_TILE_NARROW_L", nullptr);  // experiments: Cin % 32 == 0
     static const int kCfgGemv16 = cfg_by_name("gemv16"), kCfgGemv4 = cfg_by_name("gemv4"), kCfgGemv16N1 = cfg_by_name("gemv16n1"), kCfgGemv4N1 = cfg_by_name("gemv4n1");
     static const int kCfgSmall = cfg_by_name("fast64x64x16w8c"), kCfgGen128 = cfg_by_name("128x128x16"), kCfgGen64 = cfg_by_name("128x64x16"), kCfgGen32 = cfg_by_name("128x32x16");
-    static const int narrow_max = getenv("MIT_CONV_NARROW_MAX") ? atoi(getenv("MIT_CONV_NARROW_MAX")) : 64;
     const bool f16 = fast_eligible(p, 16);
-    static const bool gemv_off = getenv("MIT_CONV_NO_GEMV") != nullptr;  // A/B knob for scripts/
-    if (!gemv_off && gemv_eligible(p, 16)) return p.N == 1 ? kCfgGemv16N1 : kCfgGemv16;
-    if (!gemv_off && gemv_eligible(p, 4)) return p.N == 1 ? kCfgGemv4N1 : kCfgGemv4;
+    if (gemv_eligible(p, 16)) return p.N == 1 ? kCfgGemv16N1 : kCfgGemv16;
+    if (gemv_eligible(p, 4)) return p.N == 1 ? kCfgGemv4N1 : kCfgGemv4;
     if (p.N <= 32) {  // ESRGAN's growth-32 convolutions, small heads: a 128 x 32 tile on the best kernel the layer is eligible for
         static const int n32_split6 = cfg_by_name("split128x32x16p6o"), n32_split9 = cfg_by_name("split128x32x16p9m");
-        static const int n32_fast = getenv("MIT_CONV_NO_N32_FAST") ? -1 : cfg_by_name("fast128x32x16w4c");
+        static const int n32_fast = cfg_by_name("fast128x32x16w4c");
         const int sp = gemm_mode_now();
         if ((sp == 6 || sp == 9) && p.w_split && split_eligible(p, 16) && ((M + 127) / 128) * p.Z >= split_min_now()) {
             const int c = sp == 6 ? n32_split6 : n32_split9;
@@ -159,9 +155,8 @@ int pick_cfg(const MitConvGemm &p, int64_t M) {
     if ((split == 6 || split == 9) && p.w_split && split_eligible(p, 16) && tiles128 * p.Z >= split_min) {
         static const int wide6 = cfg_by_name("split128x128x16p6o"), wide9 = cfg_by_name("split128x128x16p9m");
         static const int narrow6 = cfg_by_name("split128x64x16p6o"), narrow9 = cfg_by_name("split128x64x16p9");
-        static const int small6 = getenv("MIT_CONV_NO_SMALL_TILE") ? -1 : cfg_by_name("split64x64x16p6o");
-        static const int small9 = getenv("MIT_CONV_NO_SMALL_TILE") ? -1 : cfg_by_name("split64x64x16p9m");
-        static const int64_t ssmall_max = getenv("MIT_CONV_SPLIT_SMALL_MAX") ? atoll(getenv("MIT_CONV_SPLIT_SMALL_MAX")) : 768;  // one wave of 128-row split tiles (3 workgroups per CU)
+        static const int small6 = cfg_by_name("split64x64x16p6o"), small9 = cfg_by_name("split64x64x16p9m");
+        constexpr int64_t ssmall_max = 768;  // one wave of 128-row split tiles (3 workgroups per CU)
         const int r = p.N % 128;
         int c = (p.N <= 64 || (r != 0 && r <= 64)) ? (split == 6 ? narrow6 : narrow9) : (split == 6 ? wide6 : wide9);
         // Exact-N tiles (round 5; wave tile 32 x BN, the A tile split once for all BN columns) where the 64-column tile would otherwise
@@ -195,8 +190,7 @@ int pick_cfg(const MitConvGemm &p, int64_t M) {
             // launches of at most two workgroups per CU (one page through the plugins: the decoder at M = 160 rows, the detector's deep
             // layers) are bound by the latency of a K-loop iteration, not by its throughput: two MFMA steps per barrier (BK = 32) take
             // 10-22 % off them and cost 2 % on fuller launches (profiles/r03l_split_check_bk32.log).  Same MFMA sequence per element.
-            static const int small6k = getenv("MIT_CONV_NO_SMALL_BK32") ? -1 : cfg_by_name("split64x64x32p6o");
-            static const int small9k = getenv("MIT_CONV_NO_SMALL_BK32") ? -1 : cfg_by_name("split64x64x32p9m");
+            static const int small6k = cfg_by_name("split64x64x32p6o"), small9k = cfg_by_name("split64x64x32p9m");
             const int smk = split == 6 ? small6k : small9k;
             if (smk >= 0 && ((M + 63) / 64) * ((p.N + 63) / 64) <= 512 && split_eligible(p, 32)) c = smk;
         }
@@ -206,13 +200,12 @@ int pick_cfg(const MitConvGemm &p, int64_t M) {
     if (f16 && bigk >= 0 && p.N % 128 == 0 && p.N <= 128 && p.ntaps * p.Cin >= 4096 && M >= 256 * 1024) return bigk;
     // under-filled launches (the decoder's GEMMs: M = lines x beams = 10240): a 128-row tiling leaves most CUs with one workgroup or
     // none, 64 x 64 tiles double the count
-    static const int small = getenv("MIT_CONV_NO_SMALL_TILE") ? -1 : kCfgSmall;
-    static const int64_t small_max = getenv("MIT_CONV_SMALL_MAX") ? atoll(getenv("MIT_CONV_SMALL_MAX")) : 1280;  // swept 640 .. 5120 on the OCR and detector stages (same-box A/B): 1280 = one full wave of workgroups
-    if (f16 && small >= 0 && p.Z == 1 && p.N > 32 && ((M + 127) / 128) * ((p.N + 63) / 64) < small_max) return small;
+    constexpr int64_t small_max = 1280;  // swept 640 .. 5120 on the OCR and detector stages (same-box A/B): 1280 = one full wave of workgroups
+    if (f16 && kCfgSmall >= 0 && p.Z == 1 && p.N > 32 && ((M + 127) / 128) * ((p.N + 63) / 64) < small_max) return kCfgSmall;
+    constexpr int narrow_max = 64;  // N % 128 up to this takes the 64-column tile
     const int rem = p.N % 128;
-    const bool lines = f16 && p.Cin % 32 == 0;
-    if (p.N <= 64 || (rem != 0 && rem <= narrow_max)) return f16 ? (lines && narrow_l >= 0 ? narrow_l : narrow) : kCfgGen64;  // e.g. N = 192: 3 x 64 beats 2 x 128 with a half-empty tile
-    return f16 ? (lines && wide_l >= 0 ? wide_l : wide) : kCfgGen128;  // 4 waves of 128 x 32, <= 128 registers: 4 workgroups per CU (+3-7 % over the 2 x 2 layout)
+    if (p.N <= 64 || (rem != 0 && rem <= narrow_max)) return f16 ? narrow : kCfgGen64;  // e.g. N = 192: 3 x 64 beats 2 x 128 with a half-empty tile
+    return f16 ? wide : kCfgGen128;  // 4 waves of 128 x 32, <= 128 registers: 4 workgroups per CU (+3-7 % over the 2 x 2 layout)
 }
 
 // ---- kernel-time probe (mit_prof_*): HIP events around every launch while enabled ----
@@ -305,8 +298,7 @@ bool map_vec_ok(const MitTensorMap &m, bool split_ok = false) {
 }
 // dwordx4 epilogue (epilogue_store_vec): whole float4 column groups, contiguous and 16-byte aligned in every tensor it touches
 bool vec_epilogue_ok(const MitConvGemm &p) {
-    static const bool off = getenv("MIT_CONV_SCALAR_EPILOGUE") != nullptr;  // A/B knob for scripts/
-    if (off || (p.N & 3) || !map_vec_ok(p.c, true)) return false;
+    if ((p.N & 3) || !map_vec_ok(p.c, true)) return false;
     if (p.pre.base && !map_vec_ok(p.pre)) return false;
     if (p.post.base && !map_vec_ok(p.post)) return false;
     if (p.lut_rows && ((p.lut_ld & 3) || (reinterpret_cast<uintptr_t>(p.lut1) & 15) || (reinterpret_cast<uintptr_t>(p.lut2) & 15))) return false;
@@ -351,9 +343,8 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
     // 2048 x 1456 x 64: LaMa's first stride-2 conv) is cut into runs of whole images that fit, instead of falling to the generic kernel.
     // Round 6: in the split mode the runs are cut to what the buffer-load tiles address (2^31 BYTES per run: buf_eligible) when one
     // image fits that — every run is still thousands of workgroups, and each takes the "u" tile instead of its "o" twin.
-    static const bool cut_for_buf = getenv("MIT_CONV_NO_BUF") == nullptr && getenv("MIT_CONV_NO_BUF_CUT") == nullptr;
     bool want_buf = false;
-    if (cfg < 0 && cut_for_buf && p.Z == 1 && p.NB > 1 && gemm_mode_now() == 6 && p.w_split != nullptr && split_eligible(p, 16)) {
+    if (cfg < 0 && p.Z == 1 && p.NB > 1 && gemm_mode_now() == 6 && p.w_split != nullptr && split_eligible(p, 16)) {
         MitConvGemm one = p;
         one.NB = 1;
         want_buf = buf_eligible(one);
@@ -388,7 +379,7 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
     if (cfg >= kNumCfgs) return mit_set_error("mit_conv_gemm: bad cfg %d", cfg);
     const CfgEntry &c = kCfgs[cfg];
     if (p.lut_rows) {  // the row-lookup epilogue exists as an instantiation of the vector store path of the fast / split tiles only
-        if (c.fast != 1 && c.fast != 2 && c.fast != 4)
+        if (c.fast != 1 && c.fast != 4)
             return mit_set_error("mit_conv_gemm: the row-lookup epilogue (lut_rows) needs a fast or split tile (Cin %% 16 == 0, <= %d taps); this launch takes %s", FAST_MAX_TAPS, c.name);
         if (!(p.act & MIT_ACT_VEC_OK)) return mit_set_error("mit_conv_gemm: lut_rows needs the float4 epilogue (N %% 4 == 0, 16-byte aligned maps, tables and lut_ld %% 4 == 0)");
         if (p.post.base) return mit_set_error("mit_conv_gemm: lut_rows together with a post residual is not implemented");
@@ -396,7 +387,6 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
     }
     if (p.dyn && c.fast == 3) return mit_set_error("mit_conv_gemm: the device-side step offset (dyn) is not implemented by the N <= 4 kernel");
     if (p.dyn && ((p.a_dyn | p.c_dyn) & 3)) return mit_set_error("mit_conv_gemm: a_dyn / c_dyn must be multiples of 4 floats");
-    if (c.fast == 2 && (p.Cin % 32)) return mit_set_error("mit_conv_gemm: cfg %s needs Cin %% 32 == 0", c.name);
     if (c.fast == 3) {
         const int lpr = (!strcmp(c.name, "gemv16") || !strcmp(c.name, "gemv16n1")) ? 16 : 4;
         if (!gemv_eligible(p, lpr) || p.N > c.BN)
@@ -404,7 +394,7 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
     }
     if (c.fast == 4 && !split_eligible(p, c.BK))
         return mit_set_error("mit_conv_gemm: cfg %s needs w_split (mit_gemm_split_pack, 16-byte aligned, w_zs1 == 0, Kw %% 8 == 0) and the fast tiles' preconditions", c.name);
-    if ((c.fast == 1 || c.fast == 2) && !fast_eligible(p, c.BK))
+    if (c.fast == 1 && !fast_eligible(p, c.BK))
         return mit_set_error("mit_conv_gemm: cfg %s needs Cin %% %d == 0, <= %d taps and 32-bit element offsets", c.name, c.BK, FAST_MAX_TAPS);
     const int M = (int)M64;
     const int MT = (M + c.BM - 1) / c.BM;

@@ -2,23 +2,23 @@
 // cfg_by_name): the index is only the position in this table.
 // X(group, name, fast, BM, BN, BK, launcher, remaining template arguments...)
 //   group    : which conv_gemm_inst<group>.hip instantiates it (parallel compilation only)
-//   fast     : 0 generic kernel; 1 conv_gemm_fast_kernel (needs fast_eligible()); 2 and Cin % 32 == 0
+//   fast     : 0 generic kernel; 1 conv_gemm_fast_kernel (needs fast_eligible())
 //   launcher : launch_cfg<BM,BN,BK,WAVES_M,WAVES_N>, launch_fast<BM,BN,BK,WAVES_M,WAVES_N,MINW,VAR> or
 //              launch_gemv<ROWS_PER_ITERATION,NMAX,KVEC,LANES_PER_ROW> (fast = 3; the BM/BN/BK columns hold its first three arguments)
 //              launch_split<BM,BN,BK,WAVES_M,WAVES_N,MINW,NPROD,VAR> (fast = 4: conv_gemm_split_kernel, needs MitConvGemm.w_split)
 //              launch_split_pp<same arguments> (fast = 4: conv_gemm_split_pp_kernel, 512 threads)
-// The default build holds what pick_cfg() can return plus the reference forms the tests compare against; every other schedule that was
-// measured and rejected, and the timing ablations, build with MIT_CONV_EXPERIMENTS (scripts/bench_conv.py, scripts/split_check).
+// The table holds what pick_cfg() can return plus the reference forms the tests compare against.  The schedules that were measured and
+// rejected, and the timing ablations, were removed; DESIGN.md and profiles/ keep their measurements, git history (e7f35b0) their code.
 // ---- generic kernel (any Cin % 4 == 0, any number of taps, 64-bit offsets)
 X(0, "128x128x16", 0, 128, 128, 16, launch_cfg, 2, 2)  // general
 X(0, "128x64x16", 0, 128, 64, 16, launch_cfg, 2, 2)    // Cout <= 64
 X(0, "128x32x16", 0, 128, 32, 16, launch_cfg, 4, 1)    // Cout <= 32
 // ---- fp32 MFMA fast kernel (GEMM mode 0, and every layer without split planes)
-X(3, "fast128x128x16w4c", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4)   // wide default: wave tile 128 x 32, <= 128 registers (4 workgroups per CU), gather offsets cached per tap
-X(3, "fast128x64x16w5c", 1, 128, 64, 16, launch_fast, 2, 2, 5, 4)     // narrow default (N <= 64 or N % 128 <= 64): <= 96 registers
-X(3, "fast192x64x16w4c", 1, 192, 64, 16, launch_fast, 2, 2, 4, 4)     // 128 < M <= 192 per batch entry (W-axis DFT fallback)
-X(3, "fast64x64x16w8c", 1, 64, 64, 16, launch_fast, 2, 2, 8, 4)       // under-filled launches (decoder GEMMs)
-X(3, "fast128x32x16w4c", 1, 128, 32, 16, launch_fast, 4, 1, 4, 4)     // N <= 32 (ESRGAN's growth-32 convolutions)
+X(1, "fast128x128x16w4c", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4)   // wide default: wave tile 128 x 32, <= 128 registers (4 workgroups per CU), gather offsets cached per tap
+X(1, "fast128x64x16w5c", 1, 128, 64, 16, launch_fast, 2, 2, 5, 4)     // narrow default (N <= 64 or N % 128 <= 64): <= 96 registers
+X(1, "fast192x64x16w4c", 1, 192, 64, 16, launch_fast, 2, 2, 4, 4)     // 128 < M <= 192 per batch entry (W-axis DFT fallback)
+X(1, "fast64x64x16w8c", 1, 64, 64, 16, launch_fast, 2, 2, 8, 4)       // under-filled launches (decoder GEMMs)
+X(1, "fast128x32x16w4c", 1, 128, 32, 16, launch_fast, 4, 1, 4, 4)     // N <= 32 (ESRGAN's growth-32 convolutions)
 // ---- N <= 4 on the VALU (conv_gemv_kernel)
 X(0, "gemv16", 3, 8, 4, 4, launch_gemv, 16)   // Cin % 64 == 0: 16 lanes per output pixel
 X(0, "gemv4", 3, 8, 4, 4, launch_gemv, 4)     // Cin % 16 == 0: 4 lanes per output pixel
@@ -26,104 +26,35 @@ X(0, "gemv16n1", 3, 8, 1, 4, launch_gemv, 16) // N == 1 forms of the two
 X(0, "gemv4n1", 3, 4, 1, 4, launch_gemv, 4)
 // ---- split-bf16 tiles (GEMM mode 6 | 9): fp32 as three bf16 planes, NPROD plane pairs on the bf16 MFMA.  "o" / "m": the staging of the
 // next K-tile placed step by step behind the MFMAs (VAR 1 + 128), "o" also with the fragment reads in consumption order (+ 256)
-X(6, "split128x128x16p6o", 4, 128, 128, 16, launch_split, 2, 2, 3, 6, 385)  // the shipped wide tile
-X(6, "split128x128x16p9m", 4, 128, 128, 16, launch_split, 2, 2, 3, 9, 129)
-X(6, "split128x64x16p6o", 4, 128, 64, 16, launch_split, 2, 2, 3, 6, 385)    // the shipped narrow tile
-X(5, "split128x64x16p9", 4, 128, 64, 16, launch_split, 2, 2, 2, 9, 0)
-X(5, "split64x64x16p6o", 4, 64, 64, 16, launch_split, 2, 2, 4, 6, 385)      // under-filled launches (same arithmetic per output element as the large tiles)
-X(5, "split64x64x16p9m", 4, 64, 64, 16, launch_split, 2, 2, 4, 9, 129)
-X(5, "split64x64x32p6o", 4, 64, 64, 32, launch_split, 2, 2, 3, 6, 385)      // ... with two MFMA steps per barrier for latency-bound launches
-X(5, "split64x64x32p9m", 4, 64, 64, 32, launch_split, 2, 2, 3, 9, 129)
-X(5, "split128x32x16p6o", 4, 128, 32, 16, launch_split, 4, 1, 4, 6, 385)    // N <= 32
-X(5, "split128x32x16p9m", 4, 128, 32, 16, launch_split, 4, 1, 4, 9, 129)
-X(5, "split128x160x16p6o", 4, 128, 160, 16, launch_split, 4, 1, 2, 6, 385)   // N = 160 / 320 / 640 / 1280 without padded columns: wave tile 32 x 160
-X(5, "split128x96x16p6o", 4, 128, 96, 16, launch_split, 4, 1, 3, 6, 385)     // N = 80 (ConvNeXt stage-1 pw2): 96 computed columns instead of 128
-X(5, "split128x192x16p6o", 4, 128, 192, 16, launch_split, 4, 1, 2, 6, 385)   // N = 192 / 384 (LaMa spectral convs): wave tile 32 x 192
+X(4, "split128x128x16p6o", 4, 128, 128, 16, launch_split, 2, 2, 3, 6, 385)  // the shipped wide tile
+X(4, "split128x128x16p9m", 4, 128, 128, 16, launch_split, 2, 2, 3, 9, 129)
+X(4, "split128x64x16p6o", 4, 128, 64, 16, launch_split, 2, 2, 3, 6, 385)    // the shipped narrow tile
+X(3, "split128x64x16p9", 4, 128, 64, 16, launch_split, 2, 2, 2, 9, 0)
+X(3, "split64x64x16p6o", 4, 64, 64, 16, launch_split, 2, 2, 4, 6, 385)      // under-filled launches (same arithmetic per output element as the large tiles)
+X(3, "split64x64x16p9m", 4, 64, 64, 16, launch_split, 2, 2, 4, 9, 129)
+X(3, "split64x64x32p6o", 4, 64, 64, 32, launch_split, 2, 2, 3, 6, 385)      // ... with two MFMA steps per barrier for latency-bound launches
+X(3, "split64x64x32p9m", 4, 64, 64, 32, launch_split, 2, 2, 3, 9, 129)
+X(3, "split128x32x16p6o", 4, 128, 32, 16, launch_split, 4, 1, 4, 6, 385)    // N <= 32
+X(3, "split128x32x16p9m", 4, 128, 32, 16, launch_split, 4, 1, 4, 9, 129)
+X(3, "split128x160x16p6o", 4, 128, 160, 16, launch_split, 4, 1, 2, 6, 385)   // N = 160 / 320 / 640 / 1280 without padded columns: wave tile 32 x 160
+X(3, "split128x96x16p6o", 4, 128, 96, 16, launch_split, 4, 1, 3, 6, 385)     // N = 80 (ConvNeXt stage-1 pw2): 96 computed columns instead of 128
+X(3, "split128x192x16p6o", 4, 128, 192, 16, launch_split, 4, 1, 2, 6, 385)   // N = 192 / 384 (LaMa spectral convs): wave tile 32 x 192
 // ---- "u": the shipped p6 tiles with their operand loads through buffer instructions (VAR + 2048, round 6): descriptor + 32-bit byte
 // offset per lane, rows that contribute zeros answered by the range check — 58 instead of 77 VALU instructions per K-tile beside the 24
 // MFMAs, 1.03-1.06x on every shape (profiles/r10s_split_check_buffer_loads.log), same bits.  pick_cfg takes them whenever every A and W
 // byte offset is below 2^31 (buf_eligible), else the "o" twin.
-X(4, "split128x128x16p6u", 4, 128, 128, 16, launch_split, 2, 2, 3, 6, 2433)
-X(4, "split128x64x16p6u", 4, 128, 64, 16, launch_split, 2, 2, 3, 6, 2433)
-X(4, "split64x64x16p6u", 4, 64, 64, 16, launch_split, 2, 2, 4, 6, 2433)
-X(4, "split64x64x32p6u", 4, 64, 64, 32, launch_split, 2, 2, 3, 6, 2433)
-X(7, "split128x32x16p6u", 4, 128, 32, 16, launch_split, 4, 1, 4, 6, 2433)
-X(7, "split128x160x16p6u", 4, 128, 160, 16, launch_split, 4, 1, 2, 6, 2433)
-X(7, "split128x96x16p6u", 4, 128, 96, 16, launch_split, 4, 1, 3, 6, 2433)
-X(7, "split128x192x16p6u", 4, 128, 192, 16, launch_split, 4, 1, 2, 6, 2433)
+X(2, "split128x128x16p6u", 4, 128, 128, 16, launch_split, 2, 2, 3, 6, 2433)
+X(2, "split128x64x16p6u", 4, 128, 64, 16, launch_split, 2, 2, 3, 6, 2433)
+X(2, "split64x64x16p6u", 4, 64, 64, 16, launch_split, 2, 2, 4, 6, 2433)
+X(2, "split64x64x32p6u", 4, 64, 64, 32, launch_split, 2, 2, 3, 6, 2433)
+X(5, "split128x32x16p6u", 4, 128, 32, 16, launch_split, 4, 1, 4, 6, 2433)
+X(5, "split128x160x16p6u", 4, 128, 160, 16, launch_split, 4, 1, 2, 6, 2433)
+X(5, "split128x96x16p6u", 4, 128, 96, 16, launch_split, 4, 1, 3, 6, 2433)
+X(5, "split128x192x16p6u", 4, 128, 192, 16, launch_split, 4, 1, 2, 6, 2433)
 // ---- ping-pong split tiles (round 6): 512 threads, two waves per SIMD alternating compute and load segments (conv_gemm_split_pp.h)
-X(7, "split128x256x16p6pp", 4, 128, 256, 16, launch_split_pp, 2, 4, 2, 6, 0)   // wave tile 64 x 64, the A tile split once for 256 columns: long-K layers with N % 256 == 0 (pick_cfg, MIT_CONV_PP=1)
+X(5, "split128x256x16p6pp", 4, 128, 256, 16, launch_split_pp, 2, 4, 2, 6, 0)   // wave tile 64 x 64, the A tile split once for 256 columns: long-K layers with N % 256 == 0 (pick_cfg, MIT_CONV_PP=1)
 // reference forms for the tests: the plain (unpipelined) schedule of the same arithmetic, and the 3-pair rung of the accuracy ladder
-X(5, "split128x128x16p6", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 0)
-X(5, "split128x128x16p9", 4, 128, 128, 16, launch_split, 2, 2, 2, 9, 0)
-X(5, "split128x128x16p3", 4, 128, 128, 16, launch_split, 2, 2, 2, 3, 0)     // 16-bit-significand products (tests only)
-X(5, "split128x64x16p6", 4, 128, 64, 16, launch_split, 2, 2, 2, 6, 0)
-#ifdef MIT_CONV_EXPERIMENTS  // schedules measured and rejected, and timing ablations (WRONG results) — scripts/bench_conv.py, scripts/split_check
-X(7, "split128x128x16p6v", 4, 128, 128, 16, launch_split, 2, 2, 3, 6, 6529)   // "u" + two K-tiles per loop trip with constant LDS buffer parity (VAR + 4096; 48 instead of 58 VALU per K-tile): +2-3 % on long K, -2-5 % on the 12-32 step loops (profiles/r10w_split_check_unroll2.log)
-X(7, "split128x128x16p6b", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1409)    // W fragments straight from global (VAR + 1024; 189 registers, two workgroups per CU): 0.88-0.94x (profiles/r10m_split_check_direct_w.log)
-X(7, "split256x128x16p6pp", 4, 256, 128, 16, launch_split_pp, 4, 2, 2, 6, 0)   // ping-pong, 256 rows x 128 columns: 0.95-1.07x of the 128 x 128 tile (profiles/r10d_split_check_pp.log)
-X(1, "256x128x16", 0, 256, 128, 16, launch_cfg, 2, 2)
-X(1, "128x128x32", 0, 128, 128, 32, launch_cfg, 2, 2)
-X(1, "256x64x16", 0, 256, 64, 16, launch_cfg, 4, 1)
-X(1, "64x64x16", 0, 64, 64, 16, launch_cfg, 2, 2)
-X(1, "fast128x128x16", 1, 128, 128, 16, launch_fast, 2, 2, 1, 0)
-X(1, "fast128x128x32", 1, 128, 128, 32, launch_fast, 2, 2, 1, 0)
-X(1, "fast128x64x16", 1, 128, 64, 16, launch_fast, 2, 2, 1, 0)
-X(1, "fast256x64x16", 1, 256, 64, 16, launch_fast, 4, 1, 1, 0)
-X(1, "fast256x128x16", 1, 256, 128, 16, launch_fast, 2, 2, 1, 0)
-X(1, "fast128x64x32", 1, 128, 64, 32, launch_fast, 2, 2, 1, 0)
-X(1, "fast256x64x32", 1, 256, 64, 32, launch_fast, 4, 1, 1, 0)
-X(2, "fast128x128x16w4", 1, 128, 128, 16, launch_fast, 2, 2, 4, 0)
-X(2, "fast128x128x16w4a", 1, 128, 128, 16, launch_fast, 4, 1, 4, 0)       // wave tile 32 x 128
-X(2, "fast128x128x16w4b", 1, 128, 128, 16, launch_fast, 1, 4, 4, 0)       // wave tile 128 x 32
-X(2, "fast128x128x16w4r", 1, 128, 128, 16, launch_fast, 1, 4, 4, 1)       // with the write-after-barrier rotation
-X(2, "fast128x64x16r", 1, 128, 64, 16, launch_fast, 2, 2, 1, 1)
-X(2, "fast128x128x16w4rb", 1, 128, 128, 16, launch_fast, 2, 2, 4, 1)
-X(2, "fast128x64x16c", 1, 128, 64, 16, launch_fast, 2, 2, 1, 4)
-X(2, "fast256x128x16w2c", 1, 256, 128, 16, launch_fast, 2, 2, 2, 4)       // wave tile 128 x 64, 2 workgroups per CU
-X(2, "fast128x64x16w6c", 1, 128, 64, 16, launch_fast, 2, 2, 6, 4)         // <= 80 registers
-X(7, "split128x128x32p6", 4, 128, 128, 32, launch_split, 2, 2, 1, 6, 0)   // two MFMA steps per barrier
-X(7, "split128x128x16p6s", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1)  // software-pipelined (split + LDS writes of the next tile among the MFMAs)
-X(7, "split128x128x16p9s", 4, 128, 128, 16, launch_split, 2, 2, 2, 9, 1)
-X(7, "split128x64x16p6s", 4, 128, 64, 16, launch_split, 2, 2, 2, 6, 1)
-X(7, "split128x128x32p6s", 4, 128, 128, 32, launch_split, 2, 2, 1, 6, 1)
-X(7, "split128x128x16p6m", 4, 128, 128, 16, launch_split, 2, 2, 3, 6, 129)
-X(7, "split128x64x16p6m", 4, 128, 64, 16, launch_split, 2, 2, 3, 6, 129)
-X(7, "split128x128x32p6m", 4, 128, 128, 32, launch_split, 2, 2, 1, 6, 129)
-X(4, "fast128x128x16w4L", 2, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 16384)  // A fetched in full 128-B lines (Cin % 32 == 0)
-X(4, "fast128x64x16L", 2, 128, 64, 16, launch_fast, 2, 2, 1, 4 + 16384)
-X(4, "fast128x128x16w4p", 1, 128, 128, 16, launch_fast, 1, 4, 4, 2)          // pinned fragment prefetch
-X(4, "fast128x128x16w4pc", 1, 128, 128, 16, launch_fast, 1, 4, 4, 6)
-X(4, "fast128x128x16w4pcs", 1, 128, 128, 16, launch_fast, 1, 4, 4, 14)       // + setprio
-X(4, "fast128x128x16w4m", 1, 128, 128, 16, launch_fast, 1, 4, 4, 20)         // mid-loop LDS stores
-X(4, "fast128x64x16pc", 1, 128, 64, 16, launch_fast, 2, 2, 1, 6)
-X(4, "fast128x256x16w2c", 1, 128, 256, 16, launch_fast, 1, 4, 2, 4)
-X(4, "xNoA", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 512)
-X(4, "xNoB", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 1024)
-X(4, "xHotA", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 2048)
-X(4, "xNoLoad", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 32)
-X(4, "xNoLoadStore", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 32 + 64)
-X(4, "xNoBar", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 128)
-X(4, "xNoFrag", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 256)
-X(4, "xMfmaOnly", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 32 + 64 + 128 + 256)
-X(4, "xeNoStoreW", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 4096)
-X(4, "xeNoActW", 1, 128, 128, 16, launch_fast, 1, 4, 4, 4 + 8192)
-X(4, "xeNoStoreN", 1, 128, 64, 16, launch_fast, 2, 2, 1, 4 + 4096)
-X(7, "split64x256x16p6o", 4, 64, 256, 16, launch_split, 1, 4, 2, 6, 385)  // wide-N, A (64 rows) split once for 256 columns: 180 registers, no scratch, 2 workgroups per CU; 0.68-0.93x of the 128 x 128 tile on every short-K shape (K = 80 .. 768), 1.03x on a 3x3 stride-2 (profiles/r07b_split_check_wide_tile.log) — the A split is not what bounds these layers (rejected, round 5)
-X(7, "split256x64x16p6o", 4, 256, 64, 16, launch_split, 4, 1, 2, 6, 385)   // N <= 64 with a 64 x 64 wave tile: 182 registers, 2 workgroups per CU; 0.97-1.02x of the 128 x 64 tile on K = 224 .. 576, 0.86x on K = 80 (profiles/r08b_split_check_256x64.log; rejected, round 5)
-X(7, "split128x256x16p6m", 4, 128, 256, 16, launch_split, 2, 2, 2, 6, 1 + 128)  // wave tile 64 x 128: 256 registers with 40 spilled, 0.6-1.2x of the fp32 tile (rejected)
-X(7, "split256x128x16p6m", 4, 256, 128, 16, launch_split, 2, 2, 2, 6, 1 + 128)  // wave tile 128 x 64: likewise
-X(7, "xsAsmSub", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 64)       // software-pipelined with scalar v_sub_f32 residuals (correct results)
-X(7, "xsAsmSubNP", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 64)
-X(7, "xsNoLoad", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 2)        // split-tile ablations (WRONG results)
-X(7, "xsNoSplit", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 4)
-X(7, "xsNoWrite", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 8)
-X(7, "xsNoFrag", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 16)
-X(7, "xsNoBar", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 32)
-X(7, "xsMfmaOnly", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 1 + 2 + 8 + 16 + 32)
-X(7, "xsNoLoadNP", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 2)
-X(7, "xsNoWriteNP", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 8)
-X(7, "xsNoFragNP", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 16)
-X(7, "xsNoLoadWriteNP", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 2 + 8)
-X(7, "xsMfmaOnlyNP", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 2 + 8 + 16 + 32)
-#endif
+X(3, "split128x128x16p6", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 0)
+X(3, "split128x128x16p9", 4, 128, 128, 16, launch_split, 2, 2, 2, 9, 0)
+X(3, "split128x128x16p3", 4, 128, 128, 16, launch_split, 2, 2, 2, 3, 0)     // 16-bit-significand products (tests only)
+X(3, "split128x64x16p6", 4, 128, 64, 16, launch_split, 2, 2, 2, 6, 0)

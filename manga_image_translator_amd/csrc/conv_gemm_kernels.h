@@ -75,7 +75,7 @@ __device__ __forceinline__ float apply_act(float v, float alpha) {
 // ---- epilogue shared by both kernels: row offsets computed once per row, shared through LDS ----
 // The activation (and whether a residual joins) is a compile-time parameter of the store loop and dispatched once per
 // wave: a per-element switch costs more than the stores on the small-K layers.
-template <int TM, int TN, int ACT, bool HAS_POST, int XE>
+template <int TM, int TN, int ACT, bool HAS_POST>
 __device__ __forceinline__ void epilogue_store(const MitConvGemm &p, f32x16 (&acc)[TM][TN], const RowOff *rowoff, const int n0,
                                                const int wm0, const int wn0, const int tid) {
     const int lane = tid & 63;
@@ -104,13 +104,9 @@ __device__ __forceinline__ void epilogue_store(const MitConvGemm &p, f32x16 (&ac
                 if (has_pre) v += p.pre.base[ro.pre + ncol_pre];
                 v = v * sc + bi;
                 if (HAS_POST && post_first) v += p.post.base[ro.post + ncol_post];
-                if (!(XE & 2)) v = apply_act<ACT>(v, p.act_alpha);
+                v = apply_act<ACT>(v, p.act_alpha);
                 if (HAS_POST && !post_first) v += p.post.base[ro.post + ncol_post];
-                if (XE & 1) {  // timing ablation: results computed but (practically) never stored
-                    if (v == 12345.678f) p.c.base[ro.c + ncol_c] = v;
-                } else {
-                    p.c.base[ro.c + ncol_c] = v;
-                }
+                p.c.base[ro.c + ncol_c] = v;
             }
         }
     }
@@ -123,7 +119,7 @@ __device__ __forceinline__ void epilogue_store(const MitConvGemm &p, f32x16 (&ac
 constexpr int EPI_PITCH = 36;
 #define MIT_ACT_VEC_OK 0x200
 
-template <int TM, int TN, int ACT, bool HAS_POST, int XE, bool HAS_LUT = false>
+template <int TM, int TN, int ACT, bool HAS_POST, bool HAS_LUT = false>
 __device__ __forceinline__ void epilogue_store_vec(const MitConvGemm &p, f32x16 (&acc)[TM][TN], const RowOff *rowoff, float *tbuf,
                                                    const int n0, const int wm0, const int wn0, const int tid, const LutOff *lutoff = nullptr) {
     const int lane = tid & 63;
@@ -158,12 +154,10 @@ __device__ __forceinline__ void epilogue_store_vec(const MitConvGemm &p, f32x16 
                 f32x4 pv = {0.f, 0.f, 0.f, 0.f};
                 if (HAS_POST) pv = *reinterpret_cast<const f32x4 *>(p.post.base + ro.post + n);
                 if (HAS_POST && post_first) v += pv;
-                if (!(XE & 2)) {
-                    v.x = apply_act<ACT>(v.x, p.act_alpha);
-                    v.y = apply_act<ACT>(v.y, p.act_alpha);
-                    v.z = apply_act<ACT>(v.z, p.act_alpha);
-                    v.w = apply_act<ACT>(v.w, p.act_alpha);
-                }
+                v.x = apply_act<ACT>(v.x, p.act_alpha);
+                v.y = apply_act<ACT>(v.y, p.act_alpha);
+                v.z = apply_act<ACT>(v.z, p.act_alpha);
+                v.w = apply_act<ACT>(v.w, p.act_alpha);
                 if (HAS_POST && !post_first) v += pv;
                 if (HAS_LUT) {  // the row-lookup form (its own instantiation): two table rows joined after everything else, in this order
                     const LutOff lo = lutoff[wm0 + mi * 32 + rl];
@@ -177,7 +171,7 @@ __device__ __forceinline__ void epilogue_store_vec(const MitConvGemm &p, f32x16 
     }
 }
 
-template <int BM, int TM, int TN, int XE = 0, int SMEM_FLOATS = 0, int NTHR = 256>
+template <int BM, int TM, int TN, int SMEM_FLOATS = 0, int NTHR = 256>
 __device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM][TN], float *smem, const int M, const int m0,
                                          const int n0, const int wm0, const int wn0, const int z1, const int z0,
                                          const int HoWo, const int tid) {
@@ -204,7 +198,7 @@ __device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM]
     constexpr int ROWOFF_FLOATS = (BM * (int)sizeof(RowOff) + 15) / 16 * 4;
     constexpr int LUT_FLOATS = BM * (int)sizeof(LutOff) / 4;   // the row-lookup offsets sit behind the transpose buffers
     constexpr int NWAVES = NTHR / 64;  // one transpose buffer per wave
-    constexpr bool VEC_FITS = SMEM_FLOATS >= ROWOFF_FLOATS + NWAVES * 32 * EPI_PITCH + LUT_FLOATS && !(XE & 1);
+    constexpr bool VEC_FITS = SMEM_FLOATS >= ROWOFF_FLOATS + NWAVES * 32 * EPI_PITCH + LUT_FLOATS;
     LutOff *lutoff = reinterpret_cast<LutOff *>(smem + ROWOFF_FLOATS + NWAVES * 32 * EPI_PITCH);
     const bool lut = VEC_FITS && p.lut_rows != nullptr;   // (the launcher admits lut_rows only on kernels and operands that take the vector path)
     if (VEC_FITS && lut) {
@@ -220,16 +214,16 @@ __device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM]
     float *tbuf = smem + ROWOFF_FLOATS + (tid >> 6) * (32 * EPI_PITCH);
     const bool vec = VEC_FITS && (p.act & MIT_ACT_VEC_OK);
     if (VEC_FITS && vec && lut) {  // act in {none, relu}, no post residual (mit_conv_gemm_cfg checks)
-        if ((p.act & 0xff) == MIT_ACT_RELU) epilogue_store_vec<TM, TN, MIT_ACT_RELU, false, XE, true>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid, lutoff);
-        else epilogue_store_vec<TM, TN, MIT_ACT_NONE, false, XE, true>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid, lutoff);
+        if ((p.act & 0xff) == MIT_ACT_RELU) epilogue_store_vec<TM, TN, MIT_ACT_RELU, false, true>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid, lutoff);
+        else epilogue_store_vec<TM, TN, MIT_ACT_NONE, false, true>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid, lutoff);
         return;
     }
 #define MIT_EPI(A)                                                                                   \
     if (VEC_FITS && vec) {                                                                           \
-        if (has_post) epilogue_store_vec<TM, TN, A, true, XE>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid); \
-        else epilogue_store_vec<TM, TN, A, false, XE>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid);         \
-    } else if (has_post) epilogue_store<TM, TN, A, true, XE>(p, acc, rowoff, n0, wm0, wn0, tid);      \
-    else epilogue_store<TM, TN, A, false, XE>(p, acc, rowoff, n0, wm0, wn0, tid)
+        if (has_post) epilogue_store_vec<TM, TN, A, true>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid); \
+        else epilogue_store_vec<TM, TN, A, false>(p, acc, rowoff, tbuf, n0, wm0, wn0, tid);         \
+    } else if (has_post) epilogue_store<TM, TN, A, true>(p, acc, rowoff, n0, wm0, wn0, tid);      \
+    else epilogue_store<TM, TN, A, false>(p, acc, rowoff, n0, wm0, wn0, tid)
     switch (p.act & 0xff) {
         case MIT_ACT_RELU: MIT_EPI(MIT_ACT_RELU); break;
         case MIT_ACT_LEAKY: MIT_EPI(MIT_ACT_LEAKY); break;
@@ -426,7 +420,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, con
         __syncthreads();
     }
 
-    epilogue<BM, TM, TN, 0, 2 * A_TILE + 2 * B_TILE>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
+    epilogue<BM, TM, TN, 2 * A_TILE + 2 * B_TILE>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
 }
 
 // ---- fast path: Cin % BK == 0, so every K-tile lies inside ONE tap ----------------------------
@@ -438,10 +432,9 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, con
 // generic kernel, so results are bitwise identical to it.
 constexpr int FAST_MAX_TAPS = 16;
 
-// VAR bits (scheduling variants, identical arithmetic): 1 = write-after-barrier rotation, 2 = fragment reads of k-step s+1 pinned
-// ahead of the MFMAs of k-step s (sched_barrier), 4 = gather offsets kept in registers while the tap does not change +
-// incremental weight pointer, 8 = raised wave priority while MFMAs issue.
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR = 0>
+// VAR = 4 (the only schedule built; it stays in the template-id, which profiles and the roofline name): gather offsets kept in
+// registers while the tap does not change + incremental weight pointer.
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR>
 __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConvGemm p, const int M, const int MT,
                                                                const int NT, const int KT) {
     constexpr int WM = BM / WAVES_M;
@@ -450,18 +443,7 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     constexpr int TN = WN / 32;
     static_assert(WAVES_M * WAVES_N == 4, "4 waves");
     static_assert(TM >= 1 && TN >= 1, "wave tile");
-    constexpr bool ROT = (VAR & 1) != 0;
-    constexpr bool PIPE = (VAR & 2) != 0;
-    constexpr bool CACHE = (VAR & 4) != 0;
-    constexpr bool PRIO = (VAR & 8) != 0;
-    constexpr bool MID = (VAR & 16) != 0;
-    // 16384: A fetched in full 128-byte lines — 8 lanes x 16 B per row, i.e. the 16-channel slices of TWO consecutive K-tiles in one
-    // load (8 rows x 128 B per wave instruction instead of 16 rows x 64 B); needs Cin % 32 == 0.  Each half goes to LDS in its own K-tile.
-    constexpr bool A2 = (VAR & 16384) != 0;
-    constexpr int A2_ITERS = BM / 32;
-    // timing ablations (WRONG results; scripts/bench_conv.py only): skip the in-loop global loads / LDS stores / barrier / fragment reads
-    constexpr bool X_NOA = (VAR & 512) != 0, X_NOB = (VAR & 1024) != 0, X_HOT = (VAR & 2048) != 0;  // skip A / B loads; A rows folded into 64 KB
-    constexpr bool X_NOLOAD = (VAR & 32) != 0, X_NOSTORE = (VAR & 64) != 0, X_NOBAR = (VAR & 128) != 0, X_NOFRAG = (VAR & 256) != 0;  // next tile's LDS stores issued between the MFMAs of k-steps 4..6, not after the last one
+    static_assert(VAR == 4, "schedule");
     constexpr int KQ = BK / 4;
     constexpr int A_ITERS = BM * KQ / 256;
     constexpr int A_MSTEP = 256 / KQ;
@@ -542,78 +524,38 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     // (tap, ci0) of the tile being loaded: wave-uniform, advanced incrementally
     int ld_tap = 0, ld_ci0 = 0;
     int a_off[A_ITERS];
-    const int aq8 = tid & 7, am8 = tid >> 3;
-    f32x4 a2_reg[A2 ? A2_ITERS : 1];
-    int a2_off[A2 ? A2_ITERS : 1];
-    auto load_a2 = [&]() {  // K-tiles (2j, 2j + 1): channels ld_ci0 .. ld_ci0 + 31 of tap ld_tap
-        if (ld_ci0 == 0) {
-            const int *rt = rowtab + ld_tap * BM + am8;
-#pragma unroll
-            for (int i = 0; i < A2_ITERS; ++i) a2_off[i] = rt[i * 32];
-        }
-        const float *ak = a_base + ld_ci0 + aq8 * 4;
-#pragma unroll
-        for (int i = 0; i < A2_ITERS; ++i) {
-            const int off = a2_off[i];
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (off >= 0) v = *reinterpret_cast<const f32x4 *>(ak + off);
-            a2_reg[i] = v;
-        }
-        ld_ci0 += 2 * BK;
-        if (ld_ci0 >= p.Cin) {
-            ld_ci0 = 0;
-            ++ld_tap;
-        }
-    };
-    auto store_a2 = [&](int buf, int par) {  // the lanes holding K-tile parity `par` of the pair
-        if ((aq8 >> 2) == par) {
-            float *as = As + buf * A_TILE + ((aq8 & 3) * 4) * LDA + am8;
-#pragma unroll
-            for (int i = 0; i < A2_ITERS; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) as[j * LDA + i * 32] = a2_reg[i][j];
-        }
-    };
-    const float *__restrict__ w_row = w_thr + (int64_t)bk * p.ldw;  // CACHE: row (kt*BK + bk) of this thread's weight column
+    const float *__restrict__ w_row = w_thr + (int64_t)bk * p.ldw;  // row (kt*BK + bk) of this thread's weight column
     const int64_t w_kstep = (int64_t)B_KSTEP * p.ldw, w_tstep = (int64_t)BK * p.ldw;
     auto load_tile = [&](int kt) {
         const int *rt = rowtab + ld_tap * BM + am;
         const float *ak = a_thr + ld_ci0;
-        if (!A2 && (!CACHE || ld_ci0 == 0)) {  // wave-uniform: the row offsets only change with the tap
+        if (ld_ci0 == 0) {  // wave-uniform: the row offsets only change with the tap
 #pragma unroll
             for (int i = 0; i < A_ITERS; ++i) a_off[i] = rt[i * A_MSTEP];
         }
 #pragma unroll
-        for (int i = 0; i < (A2 ? 0 : A_ITERS); ++i) {
-            const int off = X_HOT ? (a_off[i] & 0x3ffc) : a_off[i];
+        for (int i = 0; i < A_ITERS; ++i) {
+            const int off = a_off[i];
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (!X_NOA) {
-                if (off >= 0) v = *reinterpret_cast<const f32x4 *>(ak + off);
-                a_reg[i] = v;
-            }
+            if (off >= 0) v = *reinterpret_cast<const f32x4 *>(ak + off);
+            a_reg[i] = v;
         }
 #pragma unroll
         for (int i = 0; i < B_ITERS; ++i) {
             const int k = kt * BK + bk + i * B_KSTEP;
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (CACHE) {
-                if (b_ncol_ok && k < p.Kw) v = *reinterpret_cast<const f32x4 *>(w_row + i * w_kstep);
-            } else {
-                if (b_ncol_ok && k < p.Kw) v = *reinterpret_cast<const f32x4 *>(w_thr + (int64_t)k * p.ldw);
-            }
-            if (!X_NOB) b_reg[i] = v;
+            if (b_ncol_ok && k < p.Kw) v = *reinterpret_cast<const f32x4 *>(w_row + i * w_kstep);
+            b_reg[i] = v;
         }
-        if (CACHE) w_row += w_tstep;
-        if (!A2) {
-            ld_ci0 += BK;
-            if (ld_ci0 >= p.Cin) {
-                ld_ci0 = 0;
-                ++ld_tap;
-            }
+        w_row += w_tstep;
+        ld_ci0 += BK;
+        if (ld_ci0 >= p.Cin) {
+            ld_ci0 = 0;
+            ++ld_tap;
         }
     };
 
-    auto store_a = [&](int buf) {
+    auto store_tile = [&](int buf) {
         float *as = As + buf * A_TILE;
 #pragma unroll
         for (int i = 0; i < A_ITERS; ++i) {
@@ -621,18 +563,12 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
 #pragma unroll
             for (int j = 0; j < 4; ++j) as[(aq * 4 + j) * LDA + ml] = a_reg[i][j];
         }
-    };
-    auto store_b = [&](int buf) {
         float *bs = Bs + buf * B_TILE;
 #pragma unroll
         for (int i = 0; i < B_ITERS; ++i) {
             const int kl = bk + i * B_KSTEP;
             if (!B_PARTIAL || bk < BK) *reinterpret_cast<f32x4 *>(bs + kl * LDB + bn4 * 4) = b_reg[i];
         }
-    };
-    auto store_tile = [&](int buf) {
-        if (!A2) store_a(buf);
-        store_b(buf);
     };
 
     f32x16 acc[TM][TN];
@@ -646,11 +582,8 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     const int wm0 = (wave / WAVES_N) * WM;
     const int wn0 = (wave % WAVES_N) * WN;
 
-    if (A2) load_a2();
     load_tile(0);
-    if (A2) store_a2(0, 0);
     store_tile(0);
-    if (ROT && KT > 1) load_tile(1);  // stays in registers across the barrier
     __syncthreads();
 
     for (int kt = 0; kt < KT; ++kt) {
@@ -658,68 +591,35 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
         const float *as = As + cur * A_TILE + lh * LDA + wm0 + li;
         const float *bs = Bs + cur * B_TILE + lh * LDB + wn0 + li;
         float af[2][TM], bf[2][TN];
-        if (MID) {  // first fragments on their way while the global loads are being issued
+        if (kt + 1 < KT) load_tile(kt + 1);
 #pragma unroll
-            for (int mi = 0; mi < TM; ++mi) af[0][mi] = as[mi * 32];
+        for (int mi = 0; mi < TM; ++mi) af[0][mi] = as[mi * 32];
 #pragma unroll
-            for (int ni = 0; ni < TN; ++ni) bf[0][ni] = bs[ni * 32];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (ROT) {  // tile kt+1 (loaded during the previous iteration) -> LDS right after the barrier, then fetch kt+2
-            if (kt + 1 < KT) store_tile(cur ^ 1);
-            if (kt + 2 < KT) load_tile(kt + 2);
-        } else if (kt + 1 < KT && !X_NOLOAD) {
-            if (A2 && (kt & 1)) load_a2();  // both halves of the previous pair are in LDS by now
-            load_tile(kt + 1);
-        }
-        if (!MID) {
-#pragma unroll
-            for (int mi = 0; mi < TM; ++mi) af[0][mi] = as[mi * 32];
-#pragma unroll
-            for (int ni = 0; ni < TN; ++ni) bf[0][ni] = bs[ni * 32];
-        }
+        for (int ni = 0; ni < TN; ++ni) bf[0][ni] = bs[ni * 32];
 #pragma unroll
         for (int ks = 0; ks < BK / 2; ++ks) {
             const int c = ks & 1;
-            if (ks + 1 < BK / 2 && !X_NOFRAG) {
+            if (ks + 1 < BK / 2) {
 #pragma unroll
                 for (int mi = 0; mi < TM; ++mi) af[c ^ 1][mi] = as[(2 * ks + 2) * LDA + mi * 32];
 #pragma unroll
                 for (int ni = 0; ni < TN; ++ni) bf[c ^ 1][ni] = bs[(2 * ks + 2) * LDB + ni * 32];
-            } else if (X_NOFRAG) {
-#pragma unroll
-                for (int mi = 0; mi < TM; ++mi) af[c ^ 1][mi] = af[c][mi] + 1.f;
-#pragma unroll
-                for (int ni = 0; ni < TN; ++ni) bf[c ^ 1][ni] = bf[c][ni];
             }
-            if (PIPE || MID) __builtin_amdgcn_sched_barrier(0);  // the reads above stay ahead of this step's MFMAs
-            if (PRIO) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
             for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < TN; ++ni)
                     acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c][mi], bf[c][ni], acc[mi][ni], 0, 0, 0);
-            if (PRIO) __builtin_amdgcn_s_setprio(0);
-            if (PIPE || MID) __builtin_amdgcn_sched_barrier(0);
-            if (MID && !ROT && kt + 1 < KT) {
-                if (ks == BK / 2 - 4) store_a(cur ^ 1);
-                if (ks == BK / 2 - 3) store_b(cur ^ 1);
-                if (ks == BK / 2 - 4 || ks == BK / 2 - 3) __builtin_amdgcn_sched_barrier(0);
-            }
         }
-        if (!ROT && !MID && kt + 1 < KT && !X_NOSTORE) {
-            if (A2) store_a2(cur ^ 1, (kt + 1) & 1);
-            store_tile(cur ^ 1);
-        }
-        if (!X_NOBAR) __syncthreads();
+        if (kt + 1 < KT) store_tile(cur ^ 1);
+        __syncthreads();
     }
-    if (X_NOBAR) __syncthreads();
 
     // the launcher sizes the dynamic LDS for the larger of the staging area and the epilogue's row table + per-wave transpose
     // buffers, so small tiles (64 x 64) get the dwordx4 store path too
     constexpr int EPI_FLOATS = (BM * (int)sizeof(RowOff) + 15) / 16 * 4 + 4 * 32 * EPI_PITCH + BM * (int)sizeof(LutOff) / 4;
     constexpr int SMEM_F = (2 * A_TILE + 2 * B_TILE) > EPI_FLOATS ? (2 * A_TILE + 2 * B_TILE) : EPI_FLOATS;
-    epilogue<BM, TM, TN, (VAR >> 12) & 3, SMEM_F>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
+    epilogue<BM, TM, TN, SMEM_F>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
 }
 // ---- N <= 4: one output column group per row — a dot product, not a tile ------------------------------------------------
 // An MFMA tile would idle >= 28 of its 32 columns (the ctd heads' last ConvTranspose2d 64 -> 1 and 16 -> 1 ran at 2 TFLOP/s on
@@ -814,7 +714,7 @@ struct CfgEntry {
     const char *name;
     int BM, BN, BK;
     void (*launch)(const MitConvGemm &, int M, int MT, int NT, int KT, hipStream_t);
-    int fast;  // 1: conv_gemm_fast_kernel (needs fast_eligible()); 2: and Cin % 32 == 0; 3: conv_gemv_kernel (needs gemv_eligible()); 4: conv_gemm_split_kernel (needs split_eligible())
+    int fast;  // 1: conv_gemm_fast_kernel (needs fast_eligible()); 3: conv_gemv_kernel (needs gemv_eligible()); 4: conv_gemm_split_kernel (needs split_eligible())
     const char *kernel;  // the kernel's template-id as profilers print it, e.g. "conv_gemm_fast_kernel<128, 128, 16, 1, 4, 4, 4>"
 };
 
@@ -837,7 +737,7 @@ void launch_cfg(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, p, M, MT, NT, KT);
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR = 0>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR>
 void launch_fast(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {
     constexpr int LDA = BM + (BK == 16 ? 2 : 1);
     constexpr int LDB = BN + 4;

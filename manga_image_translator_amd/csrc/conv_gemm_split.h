@@ -1,7 +1,7 @@
 // conv_gemm_split.h — the split-bf16 tiles of mit_conv_gemm (GEMM mode 6, the default, and 9: mit_gemm_mode_set / MIT_GEMM_SPLIT): kernel,
 // weight packer and launcher.  No kernel here may spill to scratch memory (check .amdhsa_private_segment_fixed_size after changes).
 // Included at the end of conv_gemm_kernels.h (it shares that header's epilogue, RowOff and launch conventions); instantiated by
-// conv_gemm_inst5 / 6 / 7.hip through conv_gemm_cfgs.inc.
+// conv_gemm_inst2 .. 5.hip through conv_gemm_cfgs.inc.
 #pragma once
 #include "bf16_split.h"
 
@@ -32,9 +32,9 @@ namespace mitcg {
 template <int BK>
 __device__ __forceinline__ constexpr int split_swz(int kh) { return kh * (64 / BK); }
 
-// VAR bit 1: software pipeline — the next tile's operands (loaded one iteration ahead) are split and written to the other LDS buffer
-// among this tile's MFMAs, and the loads of the tile after it are issued behind them.
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR = 0>
+// VAR bits 1 + 128 (always together): software pipeline — the next tile's operands (loaded one iteration ahead) are split and written to
+// the other LDS buffer among this tile's MFMAs, and the loads of the tile after it are issued behind them; VAR 0: the plain schedule.
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
 __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitConvGemm p, const int M, const int MT, const int NT,
                                                                   const int KT) {
     constexpr int WM = BM / WAVES_M;
@@ -50,29 +50,18 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     constexpr int A_ITERS = BM * KQ / 256;
     constexpr int A_MSTEP = 256 / KQ;
     static_assert(A_ITERS >= 1 && (BM * KQ) % 256 == 0, "A tile must fill the workgroup");
-    constexpr bool PIPE = (VAR & 1) != 0;
-    // timing ablations (WRONG results; scripts/split_check --ablate only): skip the in-loop global loads / the split arithmetic / the LDS
-    // writes / the fragment reads / the barrier
-    constexpr bool X_NOLOAD = (VAR & 2) != 0, X_NOSPLIT = (VAR & 4) != 0, X_NOWRITE = (VAR & 8) != 0, X_NOFRAG = (VAR & 16) != 0,
-                   X_NOBAR = (VAR & 32) != 0;
-    constexpr bool MID = (VAR & 128) != 0;  // with PIPE: the staging cut into steps, one placed behind each MFMA (sched_barrier keeps them there)
-    constexpr bool ORD = (VAR & 256) != 0;  // with MID: fragment reads issued in the order the plane pairs consume them; next row offsets fetched in step 0
+    constexpr bool PIPE = (VAR & 1) != 0;  // the staging cut into steps, one placed behind each MFMA (sched_barrier keeps them there)
+    static_assert(PIPE == ((VAR & 128) != 0), "the pipelined schedule is the stepped one (VAR 1 + 128)");
+    constexpr bool ORD = (VAR & 256) != 0;  // with PIPE: fragment reads issued in the order the plane pairs consume them; next row offsets fetched in step 0
     // (multi-tile forms — 2 / 4 consecutive output tiles per workgroup, and a grid-strided persistent form with the next tile's set-up
     // issued ahead of the epilogue — were measured in round 3 and removed: 0.45-1.02x of this form, profiles/r03d_split_check_experiments.log)
-    // VAR bit 1024 (round 6 experiment): the W fragments do not pass through LDS at all — W planes are stored in MFMA-operand cells, so a
-    // lane's B operand of (plane, k-group lh, column) is ONE 16-byte global load (L2-resident weights, 512 contiguous bytes per
-    // half-wave); the fragments of K-tile t + 1 are requested at the top of tile t.  Takes the 13-cycle ds_write_b128 of W (half of the
-    // VGPR -> LDS store traffic that bounds this tile) and half of the fragment reads off the LDS; costs W's L2 -> L1 traffic twice
-    // (the two waves of a column read the same cells) and nine registers.
-    constexpr bool BDIR = (VAR & 1024) != 0;
     // VAR bit 2048 (round 6): operand loads through BUFFER instructions — one resource descriptor per operand (SGPRs), a 32-bit byte
     // offset per lane, the K-tile cursor as the scalar offset.  Rows that contribute zeros carry offset 2^31, past the descriptor's 2^31
     // bytes, which the hardware's range check answers with zeros: no clamp, no compare, no select on the loaded values, no 64-bit address arithmetic — 16 of the
     // 77 VALU instructions a wave issues per K-tile beside its 24 MFMAs (profiles/r10p_pmc_split_tile.json).  The launcher takes it
     // only when every A and W byte offset is below 2^31 (buf_eligible in conv_gemm.hip).
     constexpr bool BUF = (VAR & 2048) != 0;
-    constexpr bool UNR2 = (VAR & 4096) != 0;  // see tile()
-    constexpr bool ASM_SUB = (VAR & 64) != 0;  // residuals through v_sub_f32 inline asm: keeps the SLP vectoriser from packing them into v_pk_add_f32
+    static_assert((VAR & ~(1 | 128 | 256 | 2048)) == 0, "VAR bits");
     constexpr int SA = BM, SB = BN;
     constexpr int A_TILE = 3 * KH * SA, B_TILE = 3 * KH * SB;  // cells per buffer
     constexpr int B_CPP = KH * BN;                             // W cells per plane per K-tile
@@ -181,12 +170,10 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             else a_reg[i] = *reinterpret_cast<const f32x4 *>(ak + (a_off[i] < 0 ? 0 : a_off[i]));  // on the loaded value would wait for the load
         }
         const u32x4 *wk = ws + (int64_t)ld_k8 * ldn;  // split_eligible(): every K-tile lies inside the packed planes
-        if (!BDIR) {
 #pragma unroll
-            for (int i = 0; i < B_ITERS; ++i) {
-                if (BUF) b_reg[i] = __builtin_amdgcn_raw_buffer_load_b128(rw, bok(i) ? bsrc(i) * 16 : -1, ld_k8 * ldn * 16, 0);
-                else b_reg[i] = wk[bok(i) ? bsrc(i) : 0];  // columns past ldw get arbitrary finite-or-not values: never stored
-            }
+        for (int i = 0; i < B_ITERS; ++i) {
+            if (BUF) b_reg[i] = __builtin_amdgcn_raw_buffer_load_b128(rw, bok(i) ? bsrc(i) * 16 : -1, ld_k8 * ldn * 16, 0);
+            else b_reg[i] = wk[bok(i) ? bsrc(i) : 0];  // columns past ldw get arbitrary finite-or-not values: never stored
         }
         ld_k8 += KH;
         ld_ci0 += BK;
@@ -202,22 +189,15 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             const int ml = (am + i * A_MSTEP) ^ split_swz<BK>(kh);
             u32x2 h, m, l;
             const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            if (X_NOSPLIT) {
-                const u32x4 raw = __builtin_bit_cast(u32x4, a_reg[i]);
-                h = u32x2{raw.x, raw.y}, m = u32x2{raw.z, raw.w}, l = u32x2{raw.x ^ raw.z, raw.y ^ raw.w};
-            } else {
-                split3<ASM_SUB>(!BUF && a_off[i] < 0 ? zero : a_reg[i], h, m, l);
-            }
+            split3(!BUF && a_off[i] < 0 ? zero : a_reg[i], h, m, l);
             as2[((0 * KH + kh) * SA + ml) * 2 + half] = h;
             as2[((1 * KH + kh) * SA + ml) * 2 + half] = m;
             as2[((2 * KH + kh) * SA + ml) * 2 + half] = l;
         }
         u32x4 *bs = Bs + buf * B_TILE;
-        if (!BDIR) {
 #pragma unroll
-            for (int i = 0; i < B_ITERS; ++i)
-                if ((i + 1) * 256 <= B_CELLS || tid + i * 256 < B_CELLS) bs[bdst(i)] = b_reg[i];
-        }
+        for (int i = 0; i < B_ITERS; ++i)
+            if ((i + 1) * 256 <= B_CELLS || tid + i * 256 < B_CELLS) bs[bdst(i)] = b_reg[i];
     };
 
     f32x16 acc[TM][TN];
@@ -225,7 +205,7 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     const int wm0 = (wave / WAVES_N) * WM;
     const int wn0 = (wave % WAVES_N) * WN;
 
-    // The staging of one tile as a sequence of small steps (MID): per A chunk three (pack a plane, write it, form the residual), one
+    // The staging of one tile as a sequence of small steps (PIPE): per A chunk three (pack a plane, write it, form the residual), one
     // per W cell write, then the loads of the following tile (row offsets, A chunks, W cells).
     constexpr int STAGE_WRITE_STEPS = 3 * A_ITERS + B_ITERS, STAGE_STEPS = STAGE_WRITE_STEPS + 1 + A_ITERS + B_ITERS;
     auto stage_step = [&](const int st, const int buf, const bool with_loads) {
@@ -252,14 +232,14 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             const u32x2 pk = {pack_bf16(r.x, r.y), pack_bf16(r.z, r.w)};
             reinterpret_cast<u32x2 *>(As + buf * A_TILE)[((ph * KH + kh) * SA + ml) * 2 + half] = pk;
             if (ph < 2) {
-                r.x = sub_f32<ASM_SUB>(r.x, bf16_lo(pk.x));
-                r.y = sub_f32<ASM_SUB>(r.y, bf16_hi(pk.x));
-                r.z = sub_f32<ASM_SUB>(r.z, bf16_lo(pk.y));
-                r.w = sub_f32<ASM_SUB>(r.w, bf16_hi(pk.y));
+                r.x = r.x - bf16_lo(pk.x);
+                r.y = r.y - bf16_hi(pk.x);
+                r.z = r.z - bf16_lo(pk.y);
+                r.w = r.w - bf16_hi(pk.y);
             }
         } else if (st < STAGE_WRITE_STEPS) {
             const int j = st - 3 * A_ITERS;
-            if (!BDIR && ((j + 1) * 256 <= B_CELLS || tid + j * 256 < B_CELLS)) (Bs + buf * B_TILE)[bdst(j)] = b_reg[j];
+            if ((j + 1) * 256 <= B_CELLS || tid + j * 256 < B_CELLS) (Bs + buf * B_TILE)[bdst(j)] = b_reg[j];
         } else if (st == STAGE_WRITE_STEPS) {
             if (!ORD) {
                 const int *rt = rowtab + ld_tap * BM + am;
@@ -272,10 +252,8 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             else a_reg[i] = *reinterpret_cast<const f32x4 *>(a_thr + ld_ci0 + (a_off[i] < 0 ? 0 : a_off[i]));
         } else if (st < STAGE_STEPS) {
             const int j = st - STAGE_WRITE_STEPS - 1 - A_ITERS;
-            if (!BDIR) {
-                if (BUF) b_reg[j] = __builtin_amdgcn_raw_buffer_load_b128(rw, bok(j) ? bsrc(j) * 16 : -1, ld_k8 * ldn * 16, 0);
-                else b_reg[j] = (ws + (int64_t)ld_k8 * ldn)[bok(j) ? bsrc(j) : 0];
-            }
+            if (BUF) b_reg[j] = __builtin_amdgcn_raw_buffer_load_b128(rw, bok(j) ? bsrc(j) * 16 : -1, ld_k8 * ldn * 16, 0);
+            else b_reg[j] = (ws + (int64_t)ld_k8 * ldn)[bok(j) ? bsrc(j) : 0];
             if (st == STAGE_STEPS - 1) {
                 ld_k8 += KH;
                 ld_ci0 += BK;
@@ -287,53 +265,27 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     };
 
     bf16x8 af[KS][3][TM], bf[KS][3][TN];
-    // BDIR: the W fragments of the next K-tile, straight from the packed planes: cell (plane, k cell 2 ks + lh of the tile, column)
-    u32x4 bnext[BDIR ? KS : 1][3][BDIR ? TN : 1];
-    int bcol[BDIR ? TN : 1];  // this lane's cell of tile 0, plane 0, per 32-column block (columns past ldw: a valid duplicate, never stored)
-    if (BDIR) {
-#pragma unroll
-        for (int ni = 0; ni < TN; ++ni) {
-            const int n = n0 + wn0 + ni * 32 + li;
-            bcol[ni] = lh * ldn + (n < ldn ? n : ldn - 1);
-        }
-    }
-    auto load_bnext = [&](const int kt) {
-        const u32x4 *wk = ws + (int64_t)kt * KH * ldn;
+    // One K-tile: fragment reads, then (PIPE) the staging of tile kt + 1 and the loads of tile kt + 2 placed among the MFMAs, or (plain)
+    // the MFMAs and then the staging of tile kt + 1, loaded at the top of the iteration.
+    auto tile = [&](const int kt, auto do_store, auto do_load) {
+        constexpr bool DO_STORE = decltype(do_store)::value, DO_LOAD = decltype(do_load)::value;
+        const int cur = kt & 1;
+        if (!PIPE && DO_STORE) load_tile();
+        const u32x4 *as = As + cur * A_TILE;
+        const u32x4 *bs = Bs + cur * B_TILE + lh * SB + wn0 + li;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
+            for (int o = 0; o < 3; ++o) {
+                const int pa = ORD ? (o == 0 ? 0 : 3 - o) : o;  // consumption order of the pairs: A planes 0, 2, 1 with W planes 2, 0, 1
+                const int pb = ORD ? (o == 0 ? 2 : o - 1) : o;
 #pragma unroll
-                for (int ni = 0; ni < TN; ++ni) bnext[ks][pl][ni] = wk[(int64_t)(pl * K8 + 2 * ks) * ldn + bcol[ni]];
-    };
-    // One K-tile: fragment reads, then (PIPE) the staging of tile kt + 1 and the loads of tile kt + 2 scheduled among the MFMAs.
-    auto tile = [&](const int kt, auto do_store, auto do_load, auto par_c) {
-        constexpr bool DO_STORE = decltype(do_store)::value, DO_LOAD = decltype(do_load)::value;
-        // VAR bit 4096: the steady loop runs two K-tiles per trip with the LDS buffer parity as a compile-time constant, so that
-        // every ds_read / ds_write address is a loop-invariant register plus an immediate (the run-time parity cost a multiply and
-        // an add3 per access: 11 VALU and 5 SALU per K-tile)
-        constexpr int PAR = decltype(par_c)::value;
-        const int cur = PAR < 0 ? (kt & 1) : PAR;
-        if (!PIPE && DO_STORE && !X_NOLOAD) load_tile();
-        const u32x4 *as = As + cur * A_TILE;
-        const u32x4 *bs = Bs + cur * B_TILE + lh * SB + wn0 + li;
-        if (!X_NOFRAG || kt == 0) {
+                for (int mi = 0; mi < TM; ++mi)
+                    af[ks][pa][mi] = __builtin_bit_cast(bf16x8, as[(pa * KH + 2 * ks + lh) * SA + ((wm0 + mi * 32 + li) ^ split_swz<BK>(2 * ks + lh))]);
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int o = 0; o < 3; ++o) {
-                    const int pa = ORD ? (o == 0 ? 0 : 3 - o) : o;  // consumption order of the pairs: A planes 0, 2, 1 with W planes 2, 0, 1
-                    const int pb = ORD ? (o == 0 ? 2 : o - 1) : o;
-#pragma unroll
-                    for (int mi = 0; mi < TM; ++mi)
-                        af[ks][pa][mi] = __builtin_bit_cast(bf16x8, as[(pa * KH + 2 * ks + lh) * SA + ((wm0 + mi * 32 + li) ^ split_swz<BK>(2 * ks + lh))]);
-#pragma unroll
-                    for (int ni = 0; ni < TN; ++ni)
-                        bf[ks][pb][ni] = BDIR ? __builtin_bit_cast(bf16x8, bnext[BDIR ? ks : 0][pb][BDIR ? ni : 0]) : __builtin_bit_cast(bf16x8, bs[(pb * KH + 2 * ks) * SB + ni * 32]);
-                }
-        }
-        if (BDIR && DO_STORE) load_bnext(kt + 1);  // (the fragments just taken are copies: their registers are free for the next tile's)
-        if (PIPE && MID) {
+                for (int ni = 0; ni < TN; ++ni) bf[ks][pb][ni] = __builtin_bit_cast(bf16x8, bs[(pb * KH + 2 * ks) * SB + ni * 32]);
+            }
+        if (PIPE) {
             constexpr int NM = KS * NPROD * TM * TN;
             constexpr int NSTEP = DO_STORE ? (DO_LOAD ? STAGE_STEPS : STAGE_WRITE_STEPS) : 0;
 #pragma unroll
@@ -345,48 +297,28 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             }
 #pragma unroll
             for (int st = NM - 1; st < NSTEP; ++st) stage_step(st, cur ^ 1, DO_LOAD);  // more steps than MFMAs (3-pair tiles)
-            if (!X_NOBAR) __syncthreads();
-            return;
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int pr = 9 - NPROD; pr < 9; ++pr)
+#pragma unroll
+                    for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                        for (int ni = 0; ni < TN; ++ni)
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][kSplitPA[pr]][mi], bf[ks][kSplitPB[pr]][ni], acc[mi][ni], 0, 0, 0);
+            if (DO_STORE) store_tile(cur ^ 1);
         }
-        if (PIPE && DO_STORE && !X_NOWRITE) store_tile(cur ^ 1);  // tile kt + 1 (in registers since the previous iteration) -> the other buffer
-        if (PIPE && DO_LOAD && !X_NOLOAD) load_tile();           // tile kt + 2 on its way while this tile's MFMAs issue
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-            for (int pr = 9 - NPROD; pr < 9; ++pr)
-#pragma unroll
-                for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < TN; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][kSplitPA[pr]][mi], bf[ks][kSplitPB[pr]][ni], acc[mi][ni], 0, 0, 0);
-        if (PIPE && DO_STORE) {
-            // wanted order: the fragment reads, then per MFMA a few VALU of the split, an LDS write every other MFMA, the global
-            // loads behind the second half of the MFMAs
-            constexpr int NM = KS * NPROD * TM * TN;
-            __builtin_amdgcn_sched_group_barrier(0x100, KS * 3 * (TM + TN), 0);  // DS read
-#pragma unroll
-            for (int i = 0; i < NM; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // VALU
-                if (i & 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                 // DS write
-                if (DO_LOAD && i >= NM / 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
-            }
-        }
-        if (!PIPE && DO_STORE && !X_NOWRITE) store_tile(cur ^ 1);
-        if (!X_NOBAR) __syncthreads();
+        __syncthreads();
     };
     const std::integral_constant<bool, true> yes;
     const std::integral_constant<bool, false> no;
-    const std::integral_constant<int, 0> par0;
-    const std::integral_constant<int, 1> par1;
-    const std::integral_constant<int, -1> parx;
 
     constexpr int EPI_FLOATS = (BM * (int)sizeof(RowOff) + 15) / 16 * 4 + 4 * 32 * EPI_PITCH + BM * (int)sizeof(LutOff) / 4;
     constexpr int STAGE_FLOATS = (2 * A_TILE + 2 * B_TILE) * 4;
     constexpr int SMEM_F = STAGE_FLOATS > EPI_FLOATS ? STAGE_FLOATS : EPI_FLOATS;
 
     load_tile();
-    if (BDIR) load_bnext(0);
 #pragma unroll
     for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
@@ -399,25 +331,18 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     {
         int kt = 0;
         if (PIPE) {
-            if (UNR2) {
-                for (; kt + 3 < KT; kt += 2) {
-                    tile(kt, yes, yes, par0);
-                    tile(kt + 1, yes, yes, par1);
-                }
-            }
-            for (; kt + 2 < KT; ++kt) tile(kt, yes, yes, parx);
-            if (kt + 1 < KT) tile(kt++, yes, no, parx);
+            for (; kt + 2 < KT; ++kt) tile(kt, yes, yes);
+            if (kt + 1 < KT) tile(kt++, yes, no);
         } else {
-            for (; kt + 1 < KT; ++kt) tile(kt, yes, no, parx);
+            for (; kt + 1 < KT; ++kt) tile(kt, yes, no);
         }
-        tile(kt, no, no, parx);
+        tile(kt, no, no);
     }
-    if (X_NOBAR) __syncthreads();  // the epilogue reuses the staging area
     // the thread index rebuilt from the SGPR wave index and mbcnt: nothing derived from threadIdx.x has to survive the K loop (the
     // 128 x 128 tile otherwise spilled eight such registers to scratch memory; see DESIGN §7 on why no kernel of this library may use
     // scratch)
     const int tid_e = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    epilogue<BM, TM, TN, 0, SMEM_F>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
+    epilogue<BM, TM, TN, SMEM_F>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
 }
 
 // (A one-wave-per-32x32-block form with register-streamed operands for few-row GEMMs — a page's decoder Linears, M = 160 — was built and
@@ -451,7 +376,7 @@ static __global__ __launch_bounds__(256) void gemm_split_pack_kernel(const float
     o[2 * plane] = u32x4{l[0], l[1], l[2], l[3]};
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR = 0>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
 void launch_split(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {
     constexpr int KH = BK / 8;
     constexpr int SA = BM, SB = BN;

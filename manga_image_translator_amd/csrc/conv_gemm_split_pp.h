@@ -19,7 +19,7 @@
 
 namespace mitcg {
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR = 0>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
 __global__ __launch_bounds__(512, MINW) void conv_gemm_split_pp_kernel(const MitConvGemm p, const int M, const int MT, const int NT,
                                                                      const int KT) {
     constexpr int NTHR = 512;
@@ -32,8 +32,7 @@ __global__ __launch_bounds__(512, MINW) void conv_gemm_split_pp_kernel(const Mit
     constexpr int SA = BM, SB = BN;
     constexpr int A_TILE = 3 * KH * SA, B_TILE = 3 * KH * SB;
     constexpr int B_CPP = KH * BN, B_CELLS = 3 * B_CPP, B_ITERS = (B_CELLS + NTHR - 1) / NTHR;
-    constexpr bool X_NOSPLIT = (VAR & 4) != 0, X_NOMFMA = (VAR & 8) != 0;  // timing ablations (WRONG results; MIT_CONV_EXPERIMENTS builds)
-    constexpr bool PRIO = (VAR & 2) == 0;
+    static_assert(VAR == 0, "one schedule");
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     u32x4 *As = reinterpret_cast<u32x4 *>(smem);             // [2][3][KH][SA]
@@ -138,12 +137,7 @@ __global__ __launch_bounds__(512, MINW) void conv_gemm_split_pp_kernel(const Mit
             const int ml = (am + i * A_MSTEP) ^ split_swz<BK>(kh);
             u32x2 h, m, l;
             const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            if (X_NOSPLIT) {
-                const u32x4 raw = __builtin_bit_cast(u32x4, a_reg[i]);
-                h = u32x2{raw.x, raw.y}, m = u32x2{raw.z, raw.w}, l = u32x2{raw.x ^ raw.z, raw.y ^ raw.w};
-            } else {
-                split3<true>(a_off[i] < 0 ? zero : a_reg[i], h, m, l);
-            }
+            split3<true>(a_off[i] < 0 ? zero : a_reg[i], h, m, l);
             as2[((0 * KH + kh) * SA + ml) * 2 + half] = h;
             as2[((1 * KH + kh) * SA + ml) * 2 + half] = m;
             as2[((2 * KH + kh) * SA + ml) * 2 + half] = l;
@@ -198,25 +192,15 @@ __global__ __launch_bounds__(512, MINW) void conv_gemm_split_pp_kernel(const Mit
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
         // ---- compute segment
-        if (PRIO) __builtin_amdgcn_s_setprio(1);
-        if (!X_NOMFMA) {
+        __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int pr = 3; pr < 9; ++pr)
+        for (int pr = 3; pr < 9; ++pr)
 #pragma unroll
-                for (int mi = 0; mi < TM; ++mi)
+            for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-                    for (int ni = 0; ni < TN; ++ni)
-                        acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kSplitPA[pr]][mi], bf[kSplitPB[pr]][ni], acc[mi][ni], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-                for (int mi = 0; mi < TM; ++mi) asm volatile("" ::"v"(af[pl][mi]));
-#pragma unroll
-                for (int ni = 0; ni < TN; ++ni) asm volatile("" ::"v"(bf[pl][ni]));
-            }
-        }
-        if (PRIO) __builtin_amdgcn_s_setprio(0);
+                for (int ni = 0; ni < TN; ++ni)
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kSplitPA[pr]][mi], bf[kSplitPB[pr]][ni], acc[mi][ni], 0, 0, 0);
+        __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();  // nothing of this segment touched memory: a bare barrier
         __builtin_amdgcn_sched_barrier(0);
@@ -232,10 +216,10 @@ __global__ __launch_bounds__(512, MINW) void conv_gemm_split_pp_kernel(const Mit
     if (!second) __builtin_amdgcn_s_barrier();  // the halves meet again
     __syncthreads();                            // the epilogue reuses the staging area
     const int tid_e = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    epilogue<BM, TM, TN, 0, SMEM_F, NTHR>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
+    epilogue<BM, TM, TN, SMEM_F, NTHR>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR = 0>
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
 void launch_split_pp(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {
     constexpr int KH = BK / 8, NW = 8;
     size_t staging = (size_t)(2 * 3 * KH * BM + 2 * 3 * KH * BN) * 16 + (size_t)p.ntaps * BM * sizeof(int);

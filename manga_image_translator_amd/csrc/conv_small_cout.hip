@@ -326,14 +326,12 @@ extern "C" int mit_conv_small_cout(const float *in_dev, int64_t in_pixstride, in
     const f32x4 *w4 = reinterpret_cast<const f32x4 *>(w4_dev);
     const int refl = pad_mode == MIT_PAD_REFLECT;
     // VALU-bound: algorithmic FLOPs 2 k^2 Cin Cout per pixel; bytes: input read once + Cout outputs written
-    MitProbeScope probe(Cout <= 3 && w_pairs_dev && !getenv("MIT_SMALL_COUT_PLAIN") ? (k == 7 ? "conv_small_cout3_kernel<7>" : k == 5 ? "conv_small_cout3_kernel<5>" : "conv_small_cout3_kernel<3>")
+    MitProbeScope probe(Cout <= 3 && w_pairs_dev ? (k == 7 ? "conv_small_cout3_kernel<7>" : k == 5 ? "conv_small_cout3_kernel<5>" : "conv_small_cout3_kernel<3>")
                                                                     : (k == 7 ? "conv_small_cout_kernel<7>" : k == 5 ? "conv_small_cout_kernel<5>" : "conv_small_cout_kernel<3>"), s, 4.0 * (double)B * H * W * (Cin + Cout), 2.0 * k * k * (double)Cin * Cout * (double)B * H * W);
     // Cout <= 3: the packed-FMA kernel (2.7x fewer VALU instructions).  With 4-channel slices loaded straight from HBM it fetched
     // every 128-byte input line 8 times and was slower than the plain kernel (25 vs 17.7 ms per 16 pages); staging 16-channel groups
-    // in registers brought it to 15.9 ms (same-box A/B).  MIT_SMALL_COUT_PLAIN=1 selects the plain kernel for comparison.
-    static const bool use_pk = getenv("MIT_SMALL_COUT_PLAIN") == nullptr;
-    if (in_planestride && !use_pk) return mit_set_error("mit_conv_small_cout: MIT_SMALL_COUT_PLAIN cannot read planar input");
-    if (Cout <= 3 && use_pk && w_pairs_dev) {
+    // in registers brought it to 15.9 ms (same-box A/B).
+    if (Cout <= 3 && w_pairs_dev) {
         dim3 grid3(mit_div_up(W, TW3), mit_div_up(H, TH3), B);
         const f32x2 *wp = reinterpret_cast<const f32x2 *>(w_pairs_dev);
         if (Cin & 3) return mit_set_error("mit_conv_small_cout: Cin %% 4");

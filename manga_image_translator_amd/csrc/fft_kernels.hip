@@ -180,12 +180,11 @@ extern "C" int mit_fft_cols(const float *in_dev, int64_t in_bs, int64_t in_ts, i
     } while (0)
     // 64 KB of LDS per workgroup at h = 256 allows two workgroups per CU; 512 threads each (instead of 256) double the waves that
     // keep loads and stores in flight while the other workgroup is in its butterfly passes
-    static const bool nt256 = getenv("MIT_FFT_256") != nullptr;  // A/B knob for scripts/
     if (h <= 32) MIT_FFT_LAUNCH(1, 256);
     else if (h <= 64) MIT_FFT_LAUNCH(2, 256);
     else if (h <= 128) MIT_FFT_LAUNCH(4, 256);
-    else if (h <= 256) { if (nt256) MIT_FFT_LAUNCH(8, 256); else MIT_FFT_LAUNCH(4, 512); }
-    else { if (nt256) MIT_FFT_LAUNCH(16, 256); else MIT_FFT_LAUNCH(8, 512); }
+    else if (h <= 256) MIT_FFT_LAUNCH(4, 512);
+    else MIT_FFT_LAUNCH(8, 512);
 #undef MIT_FFT_LAUNCH
     MIT_CHECK_LAUNCH("mit_fft_cols");
     return 0;

@@ -27,14 +27,14 @@
 namespace {
 using namespace mitcg;
 
-// ABL (timing ablations, WRONG results, MIT_MLP_ABLATE=<n> in the environment of a MIT_CONV_EXPERIMENTS build only): 1 = no GELU (bias add
-// only), 2 = no weight staging after the first block, 4 = no second contraction, 8 = no first contraction
-template <int C, int ABL = 0>
+// VAR = 0: the one form built; it stays in the template-id, which the profiles name (convnext_mlp_kernel<80, 0>)
+template <int C, int VAR = 0>
 __global__ __launch_bounds__(256, 2) void convnext_mlp_kernel(const float *__restrict__ x, const int64_t ldx, const u32x4 *__restrict__ w1p,
                                                               const float *__restrict__ b1, const u32x4 *__restrict__ w2p, const int ldn2,
                                                               const float *__restrict__ scale2, const float *__restrict__ bias2,
                                                               const float *post, const int64_t ldp, float *out, const int64_t ldo, const int M) {
     static_assert(C % 16 == 0 && C <= 96, "stage width");
+    static_assert(VAR == 0, "one form");
     constexpr int KS1 = C / 16;        // MFMA steps of GEMM 1
     constexpr int K81 = C / 8;         // k cells of W1 per plane
     constexpr int HID = 4 * C;
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256, 2) void convnext_mlp_kernel(const float *__res
         const int cur = hb & 1;
         const u32x4 *w1s = wbuf + cur * BUF_CELLS;
         const u32x4 *w2s = w1s + W1_CELLS;
-        const bool more = hb + 1 < NHB && !(ABL & 2);
+        const bool more = hb + 1 < NHB;
         if (more) {  // the next block's weights are requested now and parked in LDS at the end of this block: a whole block of latency cover
             load_w1(hb + 1);
             load_w2(hb + 1);
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256, 2) void convnext_mlp_kernel(const float *__res
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) a[pl] = w1s[(pl * K81 + lh) * 32 + li];
 #pragma unroll
-        for (int ks = 0; ks < ((ABL & 8) ? 1 : KS1); ++ks) {
+        for (int ks = 0; ks < KS1; ++ks) {
             if (ks + 1 < KS1) {
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) an[pl] = w1s[(pl * K81 + 2 * (ks + 1) + lh) * 32 + li];
@@ -182,13 +182,13 @@ __global__ __launch_bounds__(256, 2) void convnext_mlp_kernel(const float *__res
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float v = acc1[8 * s + j] * 1.f + bb[8 * s + j];  // the tile's epilogue: acc * scale (none) + bias
-                g[j] = (ABL & 1) ? v : gelu_fast(v);
+                g[j] = gelu_fast(v);
             }
             split8(f32x4{g[0], g[1], g[2], g[3]}, f32x4{g[4], g[5], g[6], g[7]}, hh[s], hm[s], hl[s]);
         }
         // ---- GEMM 2: Y += H block · W2p block ------------------------------------------------------------------------------
 #pragma unroll
-        for (int i = 0; i < ((ABL & 4) ? 1 : 2 * NB); ++i) {
+        for (int i = 0; i < 2 * NB; ++i) {
             const int s = i / NB, nb = i - s * NB;
             if (i + 1 < 2 * NB) {
                 const int s1 = (i + 1) / NB, nb1 = (i + 1) - s1 * NB;
@@ -251,12 +251,12 @@ __global__ __launch_bounds__(256, 2) void convnext_mlp_kernel(const float *__res
     }
 }
 
-template <int C, int ABL = 0>
+template <int C>
 int launch_mlp(const float *x, int64_t ldx, const uint16_t *w1p, const float *b1, const uint16_t *w2p, int ldn2, const float *scale2,
                const float *bias2, const float *post, int64_t ldp, float *out, int64_t ldo, int M, hipStream_t s) {
     constexpr int NPAD = (C + 31) / 32 * 32;
     const size_t smem = (size_t)2 * (3 * (C / 8) * 32 + 3 * 4 * NPAD) * 16 + (size_t)4 * C * sizeof(float);
-    auto kern = convnext_mlp_kernel<C, ABL>;
+    auto kern = convnext_mlp_kernel<C>;
     static DynSmemOptIn optin;
     optin.ensure(reinterpret_cast<const void *>(kern), smem);
     hipLaunchKernelGGL(kern, dim3((M + 127) / 128), dim3(256), smem, s, x, ldx, reinterpret_cast<const u32x4 *>(w1p), b1,
@@ -285,12 +285,6 @@ extern "C" int mit_convnext_mlp(const float *x_dev, int64_t ldx, int M, int C, c
     // algorithmic bytes: the block input and the residual read once, the output written once (the hidden activations stay on chip);
     // FLOPs: both contractions
     MitProbeScope probe("convnext_mlp_kernel<80>", s, (double)M * C * 4.0 * 3.0, 2.0 * 2.0 * (double)M * C * (4.0 * C));
-#ifdef MIT_CONV_EXPERIMENTS
-    static const int abl = getenv("MIT_MLP_ABLATE") ? atoi(getenv("MIT_MLP_ABLATE")) : 0;
-#define MIT_MLP_ABL(n) if (abl == n) { launch_mlp<80, n>(x_dev, ldx, w1_planes_dev, b1_dev, w2perm_planes_dev, (int)ldn2, scale2_dev, bias2_dev, post_dev, ldp, out_dev, ldo, M, s); MIT_CHECK_LAUNCH("mit_convnext_mlp"); return 0; }
-    MIT_MLP_ABL(1) MIT_MLP_ABL(2) MIT_MLP_ABL(4) MIT_MLP_ABL(8) MIT_MLP_ABL(3) MIT_MLP_ABL(12) MIT_MLP_ABL(15)
-#undef MIT_MLP_ABL
-#endif
     switch (C) {
         case 80: launch_mlp<80>(x_dev, ldx, w1_planes_dev, b1_dev, w2perm_planes_dev, (int)ldn2, scale2_dev, bias2_dev, post_dev, ldp, out_dev, ldo, M, s); break;
         default: return mit_set_error("mit_convnext_mlp: C = %d", C);

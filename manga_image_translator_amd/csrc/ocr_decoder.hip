@@ -28,20 +28,12 @@ constexpr int FF = 2048;
 constexpr int FF2_SPLITK_MAX_ROWS = 640;   // rows (lines x beams) up to which the few-row FFN output Linear cuts K across four waves
 
 struct Ws {
-    float *tgt, *nrm, *qkv, *att, *q2, *ffh, *decoded, *p1, *logits, *vals, *logp, *cfeat, *part;
+    float *tgt, *nrm, *qkv, *att, *q2, *ffh, *decoded, *p1, *logits, *vals, *logp, *cfeat;
     int *idx, *hist, *done, *done_count, *dstep;
     // the few-row form (rows_path): activations that only feed a Linear live as bf16 planes [3][K / 8][Rp][8] (pgemm_rows.h)
     uint16_t *nrm_p, *att_p, *ffh_p, *dec_p, *p1_p;
     int64_t Rp;
 };
-
-// Few rows, long contraction (the FFN's second Linear, K = 2048, at one page: R = lines x beams = 160 rows): a 64-row tiling is
-// (R / 64) x (320 / 64) = 15 workgroups that each walk all 128 K-tiles — 45 us of a 256-CU chip for 0.2 GFLOP.  Up to SPLITK_MAX_M
-// rows such a GEMM is cut along K into slices of SPLITK_SLICE, computed as batch entries of ONE launch into a partial buffer
-// [S][M][Np], and summed in slice order by splitk_reduce_kernel, which applies the epilogue.  Deterministic; the sum order differs
-// from the k-sequential chain of the single-launch form (fp32 rounding only) — which is why it is an opt-in experiment
-// (MIT_OCR_SPLITK=1, see gemm()): measured 44 -> 50 ms per page of the B = 1 OCR call without it.
-constexpr int SPLITK_MAX_M = 2048, SPLITK_MIN_K = 1024, SPLITK_SLICE = 128;
 
 inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
@@ -66,7 +58,6 @@ int64_t carve(Ws *w, char *base, int N, int T, int D) {
     float *vals = (float *)take(R * 5 * 4);
     float *logp = (float *)take(2 * R * 4);
     float *cfeat = (float *)take(R * T * 64 * 4);
-    float *part = (float *)take(R <= SPLITK_MAX_M ? (int64_t)(FF / SPLITK_SLICE) * R * E * 4 : 0);
     int *idx = (int *)take(R * 5 * 4);
     int *hist = (int *)take(2 * R * (T + 1) * 4);
     int *done = (int *)take((int64_t)N * 4);
@@ -78,46 +69,15 @@ int64_t carve(Ws *w, char *base, int N, int T, int D) {
     uint16_t *ffh_p = (uint16_t *)take(3 * FF * Rp * 2);
     uint16_t *dec_p = (uint16_t *)take(3 * E * Rp * 2);
     uint16_t *p1_p = (uint16_t *)take(3 * E * Rp * 2);
-    if (w) *w = Ws{tgt, nrm, qkv, att, q2, ffh, decoded, p1, logits, vals, logp, cfeat, part, idx, hist, done, done_count, dstep,
+    if (w) *w = Ws{tgt, nrm, qkv, att, q2, ffh, decoded, p1, logits, vals, logp, cfeat, idx, hist, done, done_count, dstep,
                    nrm_p, att_p, ffh_p, dec_p, p1_p, Rp};
     return off;
 }
 
-// sum of the S partial products in slice order + the epilogue of mit_conv_gemm: C = act(sum * scale + bias) + post
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restrict__ part, const int S, const int M, const int N4, const int Np,
-                                                           float *C, const int64_t ldc, const float *__restrict__ scale,
-                                                           const float *__restrict__ bias, const int act, const float *post, const int64_t ldpost) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= M * N4) return;
-    const int m = idx / N4, n = (idx - m * N4) * 4;
-    const int64_t slice = (int64_t)M * Np;
-    const float *p = part + (int64_t)m * Np + n;
-    float4 v = *reinterpret_cast<const float4 *>(p);
-    for (int z = 1; z < S; ++z) {
-        const float4 t = *reinterpret_cast<const float4 *>(p + z * slice);
-        v.x += t.x, v.y += t.y, v.z += t.z, v.w += t.w;
-    }
-    if (scale) {
-        const float4 sc = *reinterpret_cast<const float4 *>(scale + n);
-        v.x *= sc.x, v.y *= sc.y, v.z *= sc.z, v.w *= sc.w;
-    }
-    if (bias) {
-        const float4 b = *reinterpret_cast<const float4 *>(bias + n);
-        v.x += b.x, v.y += b.y, v.z += b.z, v.w += b.w;
-    }
-    if (act == MIT_ACT_RELU) v.x = fmaxf(v.x, 0.f), v.y = fmaxf(v.y, 0.f), v.z = fmaxf(v.z, 0.f), v.w = fmaxf(v.w, 0.f);
-    if (post) {
-        const float4 r = *reinterpret_cast<const float4 *>(post + (int64_t)m * ldpost + n);
-        v.x += r.x, v.y += r.y, v.z += r.z, v.w += r.w;
-    }
-    *reinterpret_cast<float4 *>(C + (int64_t)m * ldc + n) = v;
-}
-
-// C[M x N] = act((A[M x K] @ W) * scale + bias) + post, rows of A / C / post strided.  ``part``: partial-sum scratch for the
-// split-K form (NULL = never split).
+// C[M x N] = act((A[M x K] @ W) * scale + bias) + post, rows of A / C / post strided.
 // dyn / a_dyn / c_dyn: device-resident step counter and the per-step strides of A and C (MitConvGemm.dyn), for the graph-replayed steps.
 int gemm(const MitLinear &lin, const float *A, int64_t lda, float *Cp, int64_t ldc, int M, int act, const float *post,
-         int64_t ldpost, hipStream_t s, int nsplit = 0, int64_t nhi = 0, float *part = nullptr, const int *dyn = nullptr,
+         int64_t ldpost, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr,
          int64_t a_dyn = 0, int64_t c_dyn = 0) {
     MitConvGemm d;
     memset(&d, 0, sizeof(d));
@@ -128,25 +88,6 @@ int gemm(const MitLinear &lin, const float *A, int64_t lda, float *Cp, int64_t l
     d.ntaps = 1; d.pad_mode = MIT_PAD_ZERO;
     d.w = lin.w; d.ldw = lin.ldw; d.Nw = lin.Np;
     d.N = lin.N;
-    // Opt-in (MIT_OCR_SPLITK=1): the slice-wise sum is deterministic but rounds differently from the k-sequential chain of the
-    // single-launch form, and with it a page decoded alone would no longer give bit for bit the logits it gives inside a batch — beam
-    // search turns such last-bit differences into different tokens whenever two hypotheses score within them.  Off by default.
-    static const bool splitk_on = getenv("MIT_OCR_SPLITK") != nullptr && atoi(getenv("MIT_OCR_SPLITK")) != 0;
-    if (part && splitk_on && !dyn && M <= SPLITK_MAX_M && lin.K >= SPLITK_MIN_K && lin.K % SPLITK_SLICE == 0 && lin.Kp == lin.K && !nsplit &&
-        (lin.N & 3) == 0 && (act == MIT_ACT_NONE || act == MIT_ACT_RELU) && !(ldc & 3) && !(ldpost & 3)) {
-        const int S = lin.K / SPLITK_SLICE;
-        d.Cin = SPLITK_SLICE; d.Kw = SPLITK_SLICE;
-        d.Z = S; d.zdiv = 1 << 30;                       // z1 = 0, z0 = slice
-        d.a_zs0 = SPLITK_SLICE;                          // A rows are k-contiguous: slice z starts SPLITK_SLICE floats further
-        d.w_zs0 = (int64_t)SPLITK_SLICE * lin.ldw;
-        d.c.base = part; d.c.xs = lin.Np; d.c.zs0 = (int64_t)M * lin.Np;
-        d.act = MIT_ACT_NONE;
-        if (mit_conv_gemm(&d, s)) return 1;
-        const int N4 = lin.N / 4;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((M * N4 + 255) / 256), dim3(256), 0, s, part, S, M, N4, lin.Np, Cp, ldc, lin.scale,
-                           lin.bias, act, post, ldpost);
-        return 0;
-    }
     d.Cin = lin.K; d.Kw = lin.Kp;
     d.Z = 1; d.zdiv = 1;
     d.w_split = lin.w_split;  // planes attached by the packer in a split GEMM mode (NULL otherwise); the launcher decides by the mode of the moment
@@ -295,9 +236,8 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
     // rows_path: the few-row form of a step (see body).  mit_ocr48_decode_rows_max_set: largest R = 5 N it is used for; measured equal to
     // the 64 x 64 split tiles at R = 2560 (16 pages) and 2-3.5x faster per Linear at R = 160 .. 640 (profiles/r04u_pgemm_rows.log)
     const int rows_max = rows_max_now();
-    static const bool splitk_env = getenv("MIT_OCR_SPLITK") != nullptr && atoi(getenv("MIT_OCR_SPLITK")) != 0;
     const int gmode = mit_gemm_mode_get();
-    bool rows_path = (gmode == 6 || gmode == 9) && R <= rows_max && !splitk_env && rows_ok(dec->pred1) && dec->pred.w_split &&
+    bool rows_path = (gmode == 6 || gmode == 9) && R <= rows_max && rows_ok(dec->pred1) && dec->pred.w_split &&
                      dec->pred.Kp == dec->pred.K && (dec->pred.K % 16) == 0 && (dec->pred.N % 4) == 0;
     for (int l = 0; l < 5 && rows_path; ++l) {
         const MitOcrDecoderLayer &ly = dec->layers[l];
@@ -380,7 +320,7 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 float *vc = w.qkv + (int64_t)(l * 3 + 2) * R * TE;
                 // self attention (:565)
                 if (ocrk_layernorm(w.tgt, E, ly.ln1_w, ly.ln1_b, w.nrm, E, R, E, 1e-5f, st)) return 1;
-                if (gemm(ly.qkv, w.nrm, E, qc + so, TE, R, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE, nullptr, dyn, 0, E)) return 1;
+                if (gemm(ly.qkv, w.nrm, E, qc + so, TE, R, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE, dyn, 0, E)) return 1;
                 // (the XPOS rotation of the step's query and of the key history 0 .. step happens inside the attention kernel)
                 OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1, E};
                 ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, w.att, E, E, nullptr, R, 1, Tk, 1, st, 4, 80, dyn, &xs);
@@ -397,12 +337,12 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 if (ocrk_layernorm(w.tgt, E, ly.ln3_w, ly.ln3_b, w.nrm, E, R, E, 1e-5f, st)) return 1;
                 if (gemm(ly.ff1, w.nrm, E, w.ffh, FF, R, MIT_ACT_RELU, nullptr, 0, st)) return 1;
                 if (l < 4) {
-                    if (gemm(ly.ff2, w.ffh, FF, w.tgt, E, R, MIT_ACT_NONE, w.tgt, E, st, 0, 0, w.part)) return 1;
+                    if (gemm(ly.ff2, w.ffh, FF, w.tgt, E, R, MIT_ACT_NONE, w.tgt, E, st)) return 1;
                 } else {  // last layer writes the step's output straight into the activation cache (:570)
-                    if (gemm(ly.ff2, w.ffh, FF, w.decoded + so, TE, R, MIT_ACT_NONE, w.tgt, E, st, 0, 0, dyn ? nullptr : w.part, dyn, 0, E)) return 1;
+                    if (gemm(ly.ff2, w.ffh, FF, w.decoded + so, TE, R, MIT_ACT_NONE, w.tgt, E, st, 0, 0, dyn, 0, E)) return 1;
                 }
             }
-            if (gemm(dec->pred1, w.decoded + so, TE, w.p1, E, R, MIT_ACT_GELU, nullptr, 0, st, 0, 0, nullptr, dyn, E, 0)) return 1;
+            if (gemm(dec->pred1, w.decoded + so, TE, w.p1, E, R, MIT_ACT_GELU, nullptr, 0, st, 0, 0, dyn, E, 0)) return 1;
             if (gemm(dec->pred, w.p1, E, w.logits, Dp, R, MIT_ACT_NONE, nullptr, 0, st)) return 1;
         }
         if (a->trace_logits)

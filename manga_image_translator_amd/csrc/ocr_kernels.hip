@@ -21,16 +21,6 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-#ifdef MIT_CONV_EXPERIMENTS   // phase stamps of workgroup (0, 0) of the cross-attention kernel (100 MHz clock): scripts/dev only
-__device__ unsigned long long g_att_stamps[32];
-#define MIT_ATT_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { g_att_stamps[i] = wall_clock64(); g_att_stamps[8 + (i)] = clock64(); } } while (0)
-#define MIT_ATT_STAMP2(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_att_stamps[16 + (i)] = wall_clock64(); } while (0)
-extern "C" int mit_dev_att_stamps(unsigned long long *out16) { return hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_att_stamps), sizeof(g_att_stamps)) == hipSuccess ? 0 : 1; }
-#else
-#define MIT_ATT_STAMP(i) do { } while (0)
-#define MIT_ATT_STAMP2(i) do { } while (0)
-#endif
-
 namespace {
 
 // eight consecutive fp32 values (16-byte aligned, LDS) -> the three cells of (k-cell k8, row) of a planar output
@@ -562,7 +552,7 @@ __global__ void attention_kernel(const float *__restrict__ Q, int64_t q_rs, int6
 // runs, parked in LDS with a pitch of heads * HD + 4 floats (lane t's float4 reads then fall on distinct banks), and every head's wave
 // evaluates exactly attention_kernel's expressions on it — per-key dot products in d order with the rotation folded in, the
 // lane-strided softmax, the t-ordered weighted sum — so the results are bitwise the same.
-// Round 6 (scripts/dev/att_stamps.py: 12.3 us inside the kernel at Tk = 32, of which 4.6 staging the keys, 2.2 scores, 4.7 weighted sum):
+// Round 6 (phase stamps, since removed: 12.3 us inside the kernel at Tk = 32, of which 4.6 staging the keys, 2.2 scores, 4.7 weighted sum):
 // every global load of a phase is now in flight at once — the keys and, behind them, the values travel to REGISTERS first (up to
 // SELF_ST float4 per thread; the values are parked in the key area once the scores are done), and the rotation factors cos * iscale,
 // sin * iscale of (key t, pair j) — the same for all four heads, read by every lane from three tables inside its dot-product loop
@@ -577,7 +567,6 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
                                                              float *__restrict__ O, int64_t o_rs, OcrAttXpos xp, OcrPlanes opl) {
     constexpr int64_t k_ts = (int64_t)heads * HD, v_ts = k_ts;
     static_assert(heads * 64 == 256 && HD % 8 == 0, "one wave per head");
-    MIT_ATT_STAMP2(4);
     const int Tk = dstep ? *dstep + 1 : TkCap;
     const int step = dstep ? *dstep : xp.step;
     const int minpos = -((step + 2) / 2);
@@ -595,7 +584,7 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
     // ---- every global load of the kernel is requested here, in one batch: the key history, the value history (it waits in registers
     // until the scores are done), the query and the table entries of the rotations.  The pins below keep them here: the loads are from
     // read-only memory, so left alone the optimiser sinks each one to its use — the values' became eleven round trips in a row inside
-    // the store loop behind the scores (3.3 us of a 12 us workgroup, scripts/dev/att_stamps.py).
+    // the store loop behind the scores (3.3 us of a 12 us workgroup, phase stamps).
     f32x4 stk[SELF_ST], stv[SELF_ST];
     const float *kb = K + (int64_t)r * k_rs, *vbase = V + (int64_t)r * v_rs;
     auto stage_load = [&](f32x4 (&st)[SELF_ST], const float *base, const int64_t ts) __attribute__((always_inline)) {
@@ -665,7 +654,6 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
     }
     stage_store(stk, kb, k_ts);
     __syncthreads();
-    MIT_ATT_STAMP2(5);
     float mx = -INFINITY;
     for (int t = lane; t < Tk; t += 64) {
         const float4 *kp = reinterpret_cast<const float4 *>(ks + t * KP + h * HD);
@@ -686,7 +674,6 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
         ws[t] = dot;
         mx = fmaxf(mx, dot);
     }
-    MIT_ATT_STAMP2(6);
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     float sum = 0.f;
     for (int t = lane; t < Tk; t += 64) {
@@ -697,13 +684,9 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
     const float inv = 1.0f / sum;
     for (int t = lane; t < Tk; t += 64) ws[t] *= inv;
-    MIT_ATT_STAMP2(10);
     __syncthreads();           // every head is done with the keys (and the weights are visible)
-    MIT_ATT_STAMP2(11);
     stage_store(stv, vbase, v_ts);  // the values take their place
-    MIT_ATT_STAMP2(12);
     __syncthreads();
-    MIT_ATT_STAMP2(7);
     float *ob = O ? O + (int64_t)r * o_rs + h * HD : nullptr;
     const float *vs = ks + h * HD;
     for (int d = lane; d < HD; d += 64) {
@@ -712,12 +695,10 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
         if (opl.p) qs[d] = acc;
         else ob[d] = acc;
     }
-    MIT_ATT_STAMP2(8);
     if (opl.p) {
         wave_lds_fence();
         for (int c = lane; c < (HD >> 3); c += 64) store_cells(opl, h * (HD >> 3) + c, r, qs + c * 8);
     }
-    MIT_ATT_STAMP2(9);
 }
 
 // ---- the same attention for ONE query position of G = kv_div consecutive rows that share a K / V block (the beams of a line
@@ -792,7 +773,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
     // the first keys travel while the queries are prepared; the latency form does not even wait for the line's length (rows past it are
     // padding inside the line's block: loaded, stored, never used)
     constexpr bool EAGER = KCHUNK > 64;
-    MIT_ATT_STAMP(0);
     if (EAGER) att_chunk_load<STAGE>(stage, kb, k_ts, 0, min(KCHUNK, Tk), HD4, tid);
     const int valid = klen ? min(klen[kr], Tk) : Tk;
     if (!EAGER) att_chunk_load<STAGE>(stage, kb, k_ts, 0, min(KCHUNK, valid), HD4, tid);
@@ -852,7 +832,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
             }
         }
         __syncthreads();
-        MIT_ATT_STAMP2(0);
         if (wave < 3) {
             f32x16 acc;
 #pragma unroll
@@ -877,7 +856,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
                 if (kstep + D < KTS) issue(d, kstep + D);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            MIT_ATT_STAMP2(1);
 #pragma unroll
             for (int pq = 0; pq < 2; ++pq) {   // after the swap: beam li, the head's columns c0 .. c0 + 7
                 float val[8];
@@ -922,7 +900,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
         for (int i = tid; i < G * HD; i += ATT_THREADS) qs[i] = Q[(int64_t)(r0 + i / HD) * q_rs + h * HD + (i % HD)];
     }
 
-    MIT_ATT_STAMP(1);
     // ---- pass 1: scores.  The next chunk's keys travel to registers while this chunk's dot products run; behind the last chunk of keys
     // the first chunk of VALUES does (its latency is hidden by the last dot products and the softmax).  A thread owns one key of the
     // chunk — its row read from LDS once, into registers — and every KT-th ... query of the line.
@@ -936,7 +913,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
         __syncthreads();  // previous chunk consumed (and qs visible)
         if (!v_ahead) att_chunk_store<STAGE>(stage, ks, (EAGER && t0 == 0) ? min(KCHUNK, Tk) : nk, HD4, KP, tid);
         __syncthreads();
-        MIT_ATT_STAMP(2);
         if (t0 + KCHUNK < valid) {
             att_chunk_load<STAGE>(stage, kb, k_ts, t0 + KCHUNK, min(KCHUNK, valid - t0 - KCHUNK), HD4, tid);
         } else if (!v_ahead) {
@@ -956,7 +932,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
                 for (int qi = 0; qi < NQ; ++qi) dot[qi] = 0.f;
                 // The queries' values (one address for every lane: a broadcast read) run ONE d-group ahead of their products, fenced: left
                 // to itself the compiler issues each read right before its use and waits for it — a hundred LDS round trips in a row, 4.6 us
-                // of a 12 us workgroup (scripts/dev/att_stamps.py) — although the five sums of a group are 40 independent VALU
+                // of a 12 us workgroup (phase stamps) — although the five sums of a group are 40 independent VALU
                 // instructions that cover the next group's latency.
                 float4 qv[2][NQ];
 #pragma unroll
@@ -994,7 +970,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
         }
     }
     __syncthreads();
-    MIT_ATT_STAMP(3);
     {   // softmax: one wave per query, lanes strided over the keys; a wave with two queries (G = 5: wave 0) runs them side by side so
         // that their shuffle and exp latencies overlap (2.0 -> 1 us of the workgroup); per query the same operations in the same order
         constexpr int NW = ATT_THREADS / 64, QW = (G + NW - 1) / NW;
@@ -1033,7 +1008,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
                 if (on[i]) wq[i][t] *= iv[i];  // the (weight * 1/sum) factor of the weighted sum, formed once
     }
 
-    MIT_ATT_STAMP(4);
     // ---- pass 2: weighted sum of the values, t-ordered per (query, d); thread (d, half) owns the queries g = half, half + 2, ...
     // Waves 0 / 1: half = wave, d = lane; wave 2: d = 64 .. 79 of both halves (a wave's weight reads are then one address: a broadcast).
     // Branch-free inner loop: a (d, half) whose last query index falls past G sums a duplicate of query G - 1 that is never stored.
@@ -1054,7 +1028,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
         __syncthreads();  // previous chunk consumed (and the softmax weights visible)
         att_chunk_store<STAGE>(stage, ks, nk, HD4, KP, tid);
         __syncthreads();
-        MIT_ATT_STAMP(5);
         if (t0 + KCHUNK < valid) att_chunk_load<STAGE>(stage, vb, v_ts, t0 + KCHUNK, min(KCHUNK, valid - t0 - KCHUNK), HD4, tid);
         if (owner) {
             constexpr int U = 8;  // values and weights of U keys read ahead of their (t-ordered) multiply-adds
@@ -1080,7 +1053,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
             }
         }
     }
-    MIT_ATT_STAMP(6);
     if (opl.p) {  // planar output: the G x HD block passes through LDS (qs: last read in pass 1) to become cells of 8
         if (owner) {
 #pragma unroll
@@ -1095,7 +1067,6 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
             const int g = i / HC, c = i - g * HC;
             store_cells(opl, h * HC + c, r0 + g, qs + g * HD + c * 8);
         }
-        MIT_ATT_STAMP(7);
         return;
     }
     if (owner) {
@@ -1726,9 +1697,9 @@ __global__ void memory_kv_lines_kernel(const float *__restrict__ Kf, const float
     }
 }
 
-// the decoder's self-attention on attention_self_kernel (1, default; MIT_ATT_NO_SELF in the environment starts with 0) or on
-// attention_kernel (0): same bits either way (tests/test_ocr_gpu.py), a switch for A/B runs
-static std::atomic<int> g_att_self_rows{getenv("MIT_ATT_NO_SELF") ? 0 : 1};
+// the decoder's self-attention on attention_self_kernel (1, default) or on attention_kernel (0): same bits either way
+// (tests/test_ocr_gpu.py), a switch for A/B runs
+static std::atomic<int> g_att_self_rows{1};
 extern "C" int mit_attention_self_rows_set(int on) {
     const int prev = g_att_self_rows.load(std::memory_order_relaxed);
     if (on >= 0) g_att_self_rows.store(on ? 1 : 0, std::memory_order_relaxed);

@@ -33,14 +33,6 @@
 
 using namespace mitcg;
 
-#ifdef MIT_CONV_EXPERIMENTS   // phase stamps of workgroup 0 of the few-row GEMM (100 MHz clock): scripts/dev only
-__device__ unsigned long long g_rows_stamps[16];
-#define MIT_ROWS_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_rows_stamps[i] = wall_clock64(); } while (0)
-extern "C" int mit_dev_rows_stamps(unsigned long long *out16) { return hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_rows_stamps), sizeof(g_rows_stamps)) == hipSuccess ? 0 : 1; }
-#else
-#define MIT_ROWS_STAMP(i) do { } while (0)
-#endif
-
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -280,8 +272,7 @@ __device__ __forceinline__ void pg_epilogue(const MitPGemm &p, f32x16 (&acc)[TM]
     }
 }
 
-// VAR: variants for scripts/pgemm_check.  Timing ablations (WRONG results): 1 = no DMA pieces, 2 = no MFMAs, 4 = no barriers.  Schedules
-// (same results): 16 = all DMA pieces of an iteration right behind the first fragment reads, in the shadow of their latency, instead of
+// VAR: schedule variants for scripts/pgemm_check (same results): 16 = all DMA pieces of an iteration right behind the first fragment reads, in the shadow of their latency, instead of
 // spread behind the MFMA groups; 32 = s_setprio 1 around the MFMAs
 template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NPROD, int OUTP, int MINW, int VAR = 0>
 __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(const MitPGemm p, const int MT, const int NT, const int KT,
@@ -424,9 +415,7 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
             for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < TN; ++ni) {
-                    if constexpr ((VAR & 2) != 0) {  // timing ablation: no MFMAs (the fragments stay live)
-                        asm volatile("" ::"v"(af[kSplitPA[pr]][mi]), "v"(bf[kSplitPB[pr]][ni]));
-                    } else if constexpr (OUTP == 0)
+                    if constexpr (OUTP == 0)
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kSplitPA[pr]][mi], bf[kSplitPB[pr]][ni], acc[mi][ni], 0, 0, 0);
                     else  // transposed result: rows = output columns
                         acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[kSplitPB[pr]][ni], af[kSplitPA[pr]][mi], acc[mi][ni], 0, 0, 0);
@@ -438,10 +427,8 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
             if ((VAR & 16) != 0 && dma_calls++ >= 3) return;  // VAR & 16: the first three calls (ahead of the MFMAs) issue, the ones behind the MFMA groups are empty
             __builtin_amdgcn_sched_barrier(0);
             if (do_issue) {  // wave-uniform: a scalar branch around the pieces; ONE instance of the MFMA chain keeps the accumulators in place
-                if constexpr ((VAR & 1) == 0) {
 #pragma unroll
-                    for (int i = g * PER; i < (g + 1) * PER && i < G; ++i) issue_piece(dma_slot, i);
-                }
+                for (int i = g * PER; i < (g + 1) * PER && i < G; ++i) issue_piece(dma_slot, i);
                 if (g == 2) issue_done();
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -600,7 +587,7 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
     for (int ti = 0;; ++ti) {              // one pass more than there are tiles: the last one only stores the last tile
         if (ti > 0) {
             wait_vmcnt<0>();
-            if constexpr ((VAR & 4) == 0) wg_barrier();
+            wg_barrier();
             const int t = tile_lo + (ti - 1) * tile_step;
             const int z = uni(t / tiles_per_z), tt = t - z * tiles_per_z;
             const int mt = uni(tt / NT), nt = tt - mt * NT;
@@ -615,15 +602,15 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
         for (int kt = 0; kt < KT; ++kt, ++it) {
             if (kt >= steady_lo && kt < steady_hi) {
                 wait_vmcnt<(NS - 2) * G>();
-                if constexpr ((VAR & 4) == 0) wg_barrier();
+                wg_barrier();
             } else if (kt >= steady_lo) {  // the tail of the run
                 const int ahead = issued - it - 1;
                 if (ahead <= 0) wait_vmcnt<0>();
                 else if (ahead == 1) wait_vmcnt<G>();
                 else wait_vmcnt<2 * G>();
-                if constexpr ((VAR & 4) == 0) wg_barrier();
+                wg_barrier();
             } else if (kt > 0) {  // covered by the drain ahead of the epilogue; kt == 0 has passed its barrier there too
-                if constexpr ((VAR & 4) == 0) wg_barrier();
+                wg_barrier();
             }
             const bool do_issue = issued < total;
             compute(slot, fslot, do_issue);
@@ -702,7 +689,6 @@ __global__ __launch_bounds__(256) void join_planes_kernel(const u32x4 *__restric
 template <int NPROD, int D, int KTS>
 __global__ __launch_bounds__(64) void pgemm_rows_kernel(const uint16_t *pa, const uint16_t *pw, const unsigned int lda_u, const unsigned int ldw_u, const int Kq,
                                                         const int MT, const int NT, const int KT, const MitPGemm p, const PgRowsExt x) {
-    MIT_ROWS_STAMP(0);
     const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
     // block -> (column block, row block): the row blocks of a column block (same W cells) on one XCD, blocks dealt round-robin to the XCDs
     const int total = MT * NT, per = (total + 7) >> 3;
@@ -744,20 +730,12 @@ __global__ __launch_bounds__(64) void pgemm_rows_kernel(const uint16_t *pa, cons
 #pragma unroll
         for (int d = 0; d < D && d < KTS; ++d) issue(d, d);
         __builtin_amdgcn_sched_barrier(0);   // (the fences keep the loads D steps ahead: left alone the scheduler sinks each load to its use)
-        MIT_ROWS_STAMP(1);
 #pragma unroll
         for (int ks = 0; ks < KTS; ++ks) {
             consume(ks % D);
             if (ks + D < KTS) issue(ks % D, ks + D);
             __builtin_amdgcn_sched_barrier(0);
-#ifdef MIT_CONV_EXPERIMENTS
-            if (ks == 0) { asm volatile("" : "+v"(acc)); MIT_ROWS_STAMP(2); }
-#endif
         }
-#ifdef MIT_CONV_EXPERIMENTS
-        asm volatile("" : "+v"(acc));
-        MIT_ROWS_STAMP(3);
-#endif
     } else {
 #pragma unroll
         for (int d = 0; d < D; ++d)
@@ -782,7 +760,6 @@ __global__ __launch_bounds__(64) void pgemm_rows_kernel(const uint16_t *pa, cons
     }
 
     pg_rows_epilogue(p, x, acc, m0, n0, z, lane);
-    MIT_ROWS_STAMP(4);
 }
 
 // ---- the same block with K cut into four: the FFN's second Linear (K = 2048) at one page is ONE accumulator chain of 768 MFMAs per
@@ -916,15 +893,6 @@ const PgTile kPgTiles[] = {
     PG_ROWS_TILE("pgrows32d6p9P", 9, 6, 1),   // 21
     PG_ROWS_TILE("pgrows32d4p6", 6, 4, 0),    // 22: prefetch depth 4 (scripts/pgemm_check: 4 / 6 / 8 within 10 % of each other, 10 slower)
     PG_ROWS_TILE("pgrows32d8p6", 6, 8, 0),    // 23: ... 8
-#ifdef MIT_CONV_EXPERIMENTS  // timing ablations of tile 0 (WRONG results; scripts/pgemm_check prints their times only)
-    {"xpgNoDma", "pgemm_kernel<xpgNoDma>", 128, 128, 6, 0, 2, pg_launch<128, 128, 2, 2, 3, 6, 0, 2, 1>},
-    {"xpgNoMfma", "pgemm_kernel<xpgNoMfma>", 128, 128, 6, 0, 2, pg_launch<128, 128, 2, 2, 3, 6, 0, 2, 2>},
-    {"xpgNoBar", "pgemm_kernel<xpgNoBar>", 128, 128, 6, 0, 2, pg_launch<128, 128, 2, 2, 3, 6, 0, 2, 4>},
-    {"xpgNoDmaNoBar", "pgemm_kernel<xpgNoDmaNoBar>", 128, 128, 6, 0, 2, pg_launch<128, 128, 2, 2, 3, 6, 0, 2, 5>},
-    {"xpgNoMfmaNoBar", "pgemm_kernel<xpgNoMfmaNoBar>", 128, 128, 6, 0, 2, pg_launch<128, 128, 2, 2, 3, 6, 0, 2, 6>},
-    {"xpg256NoDmaP", "pgemm_kernel<xpg256NoDmaP>", 256, 256, 6, 1, 1, pg_launch<256, 256, 2, 4, 3, 6, 1, 2, 1>},
-    {"xpg256NoMfmaP", "pgemm_kernel<xpg256NoMfmaP>", 256, 256, 6, 1, 1, pg_launch<256, 256, 2, 4, 3, 6, 1, 2, 2>},
-#endif
 };
 constexpr int kNumPgTiles = sizeof(kPgTiles) / sizeof(kPgTiles[0]);
 
@@ -951,15 +919,6 @@ int pg_check(const MitPGemm &p) {
     if ((a != MIT_ACT_NONE && a != MIT_ACT_RELU && a != MIT_ACT_GELU) || (p.act & ~(0xff | MIT_ACT_POST_FIRST)))
         return mit_set_error("mit_pgemm: activation %d is not one of none / relu / gelu", p.act);
     return 0;
-}
-
-// workgroups per CU of the persistent grid: -1 = the tile's own figure, 0 = one workgroup per output tile, n > 0 = n per CU
-int pg_wgs_override() {
-    static const int v = [] {
-        const char *e = getenv("MIT_PGEMM_WGS");
-        return (e && *e) ? atoi(e) : -1;
-    }();
-    return v;
 }
 
 int g_num_cus = 0;
@@ -1034,8 +993,7 @@ extern "C" int mit_pgemm(const MitPGemm *d, void *stream) {
     const int64_t tiles = (int64_t)MT * NT * p.Z;
     if (tiles > 0x7fffffffLL) return mit_set_error("mit_pgemm: too many tiles");
     // persistent grid: wgs_per_cu workgroups on every CU when there is more than that much work, else one workgroup per tile
-    const int ov = pg_wgs_override();
-    const int wgs = ov >= 0 ? ov : t.wgs_per_cu;
+    const int wgs = t.wgs_per_cu;
     int64_t grid = wgs > 0 ? (int64_t)wgs * num_cus() : tiles;
     if (grid > tiles) grid = tiles;
     grid = (grid + 7) / 8 * 8;
@@ -1043,10 +1001,7 @@ extern "C" int mit_pgemm(const MitPGemm *d, void *stream) {
     const double flops = 2.0 * p.M * (double)p.N * p.K * p.Z;
     const double bytes = (double)p.Z * ((double)p.M * p.K * 6.0 + (double)p.K * p.N * 6.0 + (double)p.M * p.N * (planar ? 6.0 : 4.0));
     MitProbeScope probe(t.probe, hs, bytes, flops);
-    static const int order = [] {  // MIT_PGEMM_ORDER: 0 = a contiguous run of tiles per workgroup, 1 (default) = interleaved within the XCD
-        const char *e = getenv("MIT_PGEMM_ORDER");
-        return (e && *e) ? atoi(e) : 1;
-    }();
+    constexpr int order = 1;  // tiles interleaved within the XCD (the kernel's order 0: a contiguous run of tiles per workgroup)
     t.launch(p, MT, NT, KT, (int)tiles, (int)grid, order, hs);
     MIT_CHECK_LAUNCH("mit_pgemm");
     return 0;

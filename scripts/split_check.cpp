@@ -42,14 +42,13 @@ static int find_cfg(const char *name) {
 int main(int argc, char **argv) {
     setvbuf(stdout, nullptr, _IOLBF, 0);  // a GPU fault kills the process: keep what was printed
     const int reps = argc > 1 ? atoi(argv[1]) : 10;
-    const bool ablate = argc > 2 && !strcmp(argv[2], "--ablate");  // time the xs* ablation tiles of an MIT_CONV_EXPERIMENTS build (no checks)
     const int f_wide = find_cfg("fast128x128x16w4c"), f_narrow = find_cfg("fast128x64x16w5c");
     const int s6 = find_cfg("split128x128x16p6"), s9 = find_cfg("split128x128x16p9"), s3 = find_cfg("split128x128x16p3");
     const int n6 = find_cfg("split128x64x16p6"), n9 = find_cfg("split128x64x16p9"), s6k32 = find_cfg("split128x128x32p6");
     const int s6s = find_cfg("split128x128x16p6s"), s9s = find_cfg("split128x128x16p9s"), n6s = find_cfg("split128x64x16p6s"), s6k32s = find_cfg("split128x128x32p6s");
     const int s6m = find_cfg("split128x128x16p6m"), s9m = find_cfg("split128x128x16p9m"), n6m = find_cfg("split128x64x16p6m"), s6k32m = find_cfg("split128x128x32p6m");
     const int s6o = find_cfg("split128x128x16p6o"), n6o = find_cfg("split128x64x16p6o");
-    if (s6o < 0 || n6o < 0) return 2;  // (tiles of MIT_CONV_EXPERIMENTS builds come back as -1 from a default build and are skipped below)
+    if (s6o < 0 || n6o < 0) return 2;  // (names of removed experiment tiles come back as -1 and are skipped below)
     const int s64 = find_cfg("split64x64x16p6o"), s32 = find_cfg("split128x32x16p6o"), f32t = find_cfg("fast128x32x16w4c");  // small / narrow tiles (-1: skipped)
     const int w6o = find_cfg("split64x256x16p6o");
     const int t192 = find_cfg("split128x192x16p6o"), t256 = find_cfg("split256x64x16p6o");
@@ -305,17 +304,6 @@ int main(int argc, char **argv) {
             printf("  %-22s %9.3f ms %8.1f TFLOP/s   err vs f64 %.2e   vs fp32 tile %.2e   nan %lld   %s  (x%.2f)%s\n", nm.c_str(), ms, flops / ms * 1e-9, e,
                    dmax / ymax, (long long)nan, ok ? "ok" : "FAIL", ms_ref / ms, same);
             bad += !ok;
-        }
-        if (ablate && (strstr(cs.name, "pw1") || strstr(cs.name, "3x3 reflect") || strstr(cs.name, "pw2"))) {
-            for (const char *nm : {"split128x128x16p6", "split128x128x16p6s", "xsAsmSub", "xsAsmSubNP", "xsNoLoad", "xsNoSplit", "xsNoWrite", "xsNoFrag", "xsNoBar",
-                                   "xsMfmaOnly", "xsNoLoadNP", "xsNoWriteNP", "xsNoFragNP", "xsNoLoadWriteNP", "xsMfmaOnlyNP"}) {
-                const int cfg = find_cfg(nm);
-                float ms = 0.f;
-                if (cfg < 0) continue;
-                printf("  ablation %-20s ...\n", nm);
-                if (run(cfg, dc, &ms)) continue;
-                printf("  ablation %-20s %9.3f ms %8.1f TFLOP/s-equivalent\n", nm, ms, flops / ms * 1e-9);
-            }
         }
         CK(hipFree(da)); CK(hipFree(dw)); CK(hipFree(dc)); CK(hipFree(dref)); CK(hipFree(dbias)); CK(hipFree(dscale)); CK(hipFree(dsplit));
     }

@@ -31,8 +31,8 @@ def _rel(a, b, ymax):
 
 
 CASES = [
-    # B, Cin, Cout, H, W, k, stride, pad mode, act, fp32 tile, split tiles (every tile of the default build; the rejected schedules of
-    # MIT_CONV_EXPERIMENTS builds are checked by scripts/split_check)
+    # B, Cin, Cout, H, W, k, stride, pad mode, act, fp32 tile, split tiles (every split tile of the library; scripts/split_check times
+    # them on the network shapes)
     (2, 128, 128, 40, 56, 3, 1, "reflect", 1, "fast128x128x16w4c", ("split128x128x16p6", "split128x128x16p9", "split128x128x16p3", "split128x128x16p9m", "split128x128x16p6o",
       "split64x64x16p6o", "split64x64x16p9m", "split64x64x32p6o", "split64x64x32p9m", "split128x256x16p6pp", "split128x128x16p6u", "split64x64x16p6u", "split64x64x32p6u")),
     (1, 320, 1280, 12, 200, 1, 1, "zero", 5, "fast128x128x16w4c", ("split128x128x16p6", "split128x128x16p9", "split128x128x16p9m", "split128x128x16p6o", "split64x64x32p6o")),
