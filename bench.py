@@ -3,6 +3,9 @@
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: one rank per GPU; started outside torch.distributed.run it launches
                                                         its own N ranks through it on 127.0.0.1 — the driver's command shape works as is)
+                                                        set-up, warm-up, the K timed steps, the line: nothing else
+  python bench.py ... --full                           also the extra legs below, after the timed steps (each can still be left out
+                                                        with its --no-* option)
   python bench.py --gpus 2 --launch-rehearsal          the launch / rendezvous / weight broadcast / verified gather / max-over-ranks
                                                         plumbing alone on gloo, no GPU work (a rehearsal line, not a measurement)
   python bench.py --config4 ...                        BASELINE config 4 preset: 128 pages per GPU
@@ -16,7 +19,7 @@ timed region; weak scaling (every rank owns ``--pages`` pages; global page g has
 rank 0 broadcasts the weights over RCCL at load and gathers the per-page result records of every step (inside the timed
 region; a failing gather is a hard error).  Prints ONE JSON line on rank 0.
 
-Extra legs (outside the timed region, rank 0):
+Extra legs (--full only; outside the timed region, rank 0):
   * roofline     — one instrumented pass per stage: HIP events (the C-ABI's mit_prof_* probe, on the launch stream) around
                    every conv_gemm launch and every transform / FFT / element-wise kernel.  ``roofline`` prices the
                    dominant kernel (the conv_gemm tile configuration with the most GPU time, MFMA-bound) against the fp32
@@ -30,6 +33,8 @@ Extra legs (outside the timed region, rank 0):
   * parity_checked — the GPU results of those same pages against the oracle outputs the CPU leg just produced.
   * dropin       — the three plugins called page by page (B = 1) with the native host glue included: what a user of the
                    reference's plugin API gets.
+  * fp32_mfma, two_streams, coupled, other_configs — the same batch in the fp32-MFMA GEMM mode and on two streams, the coupled
+                   path (stages feeding each other), and short runs of BASELINE configs 1, 2 and 5 (N = 1 only).
 """
 from __future__ import annotations
 
@@ -100,8 +105,12 @@ def parse(argv=None):
     ap.add_argument("--overlap", action="store_true",
                     help="two HIP streams for the HEADLINE: LaMa on the caller's stream, detector + OCR on a side stream that joins at the end of the step "
                          "(+3-4 %% pages/s, same results).  Not the default: concurrent kernels stretch each other, so the roofline leg's per-kernel "
-                         "durations would no longer be those of the timed steps; the default run reports it as the two_streams sub-measurement instead")
+                         "durations would no longer be those of the timed steps; a --full run reports it as the two_streams sub-measurement instead")
     ap.add_argument("--no-overlap", dest="overlap", action="store_false", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every extra leg (fp32_mfma, two_streams, config 2, roofline, cpu_baseline + "
+                         "parity_checked, dropin, coupled, other_configs; the --no-* options below leave single legs out).  Without it a "
+                         "run does only what the headline needs")
     ap.add_argument("--mode", choices=["batch", "dropin"], default="batch", help="dropin: time the plugin path (B = 1) and print its line instead of the headline")
     ap.add_argument("--dropin-pages", type=int, default=6)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -112,7 +121,7 @@ def parse(argv=None):
     ap.add_argument("--coupled-mask-workers", type=int, default=4, help="host threads of the coupled path's per-page mask stages")
     ap.add_argument("--coupled-only", action="store_true", help="only the coupled batch measurement (A/B runs of its knobs)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short sub-measurements of BASELINE configs 1, 2 and 5 (other_configs) the default one-GPU run appends")
+                    help="skip the short sub-measurements of BASELINE configs 1, 2 and 5 (other_configs) a --full one-GPU run appends")
     ap.add_argument("--no-two-streams", action="store_true", help="skip the two-stream sub-measurement (two_streams)")
     ap.add_argument("--no-fp32-leg", action="store_true", help="skip the fp32-MFMA sub-measurement (fp32_mfma) taken beside a split-mode headline")
     ap.add_argument("--fp32-steps", type=int, default=3, help="timed steps of the fp32_mfma sub-measurement (after 1 warm-up step)")
@@ -127,10 +136,14 @@ def parse(argv=None):
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.config1 or args.config5 or args.coupled_only or args.launch_rehearsal or args.mode != "batch"):
         ap.error("--dump-outputs applies to the headline batch path only")
+    if args.prof_dump and not args.full:
+        ap.error("--prof-dump records the roofline leg's passes: it needs --full")
     if args.config4 or (args.pages is None and args.gpus == 8):
         args.pages = 128   # BASELINE config 4: 1024 pages over 8 GPUs; --gpus 8 without --pages IS that configuration
     if args.pages is None:
         args.pages = 64
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line; every leg after them needs --full
+        args.no_fp32_leg = args.no_two_streams = args.no_other_configs = args.no_roofline = args.no_cpu_baseline = args.no_dropin = True
     return args
 
 

@@ -227,3 +227,42 @@ def test_steps_and_dump_outputs_arguments():
     for bad in (["--steps", "0"], ["--config1", "--dump-outputs", "out"], ["--mode", "dropin", "--dump-outputs", "out"]):
         with pytest.raises(SystemExit):
             bench.parse(bad)
+
+
+def test_plain_run_leaves_every_extra_leg_to_full():
+    """A plain run (no --full) does the set-up, warm-up, timed steps and the line only; --full turns every leg on, and a --no-* option
+    still leaves its leg out of a --full run."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    legs = ("no_fp32_leg", "no_two_streams", "no_other_configs", "no_roofline", "no_cpu_baseline", "no_dropin")
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, k) for k in legs)
+    full = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not any(getattr(full, k) for k in legs)
+    some = bench.parse(["--full", "--no-roofline", "--no-dropin"])
+    assert [k for k in legs if getattr(some, k)] == ["no_roofline", "no_dropin"]
+    assert bench.parse(["--full", "--prof-dump", "layers.csv"]).prof_dump == "layers.csv"
+    with pytest.raises(SystemExit):
+        bench.parse(["--prof-dump", "layers.csv"])     # its records come from the roofline leg
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_alone(cuda, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` end to end on two pages: one line with the headline's keys, the last step's
+    outputs dumped, and no leg of --full in the line or the details record."""
+    details = tmp_path / "details.json"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pages", "2",
+                          "--details", str(details), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("pages/sec end-to-end") and d["unit"] == "pages/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 2 * 2 / (d["ms_per_step"] * 2e-3)) < 0.02 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["parity_checked"] is None and "leg_errors" not in d
+    full = json.load(open(details))
+    for k in ("roofline", "fp32_mfma", "two_streams", "cpu_baseline", "parity_checked", "dropin", "coupled", "other_configs", "conv_gemm_by_tile"):
+        assert full[k] is None, k
+    assert json.load(open(tmp_path / "dump" / "manifest.json"))["arrays"]["inpainted"]["shape"][0] == 2
