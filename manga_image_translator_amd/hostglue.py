@@ -54,8 +54,12 @@ def dbnet_boxes(db: np.ndarray, h: int, w: int, text_threshold: float, box_thres
 def boxes_from_bitmap_gpu_launch(pred, thresh: float, dest_width: int, dest_height: int, *, unclip_ratio: float, min_sside: float, box_thresh: float = 0.0,
                                  min_sside_out: float = 0.0, roll_start: bool = False, max_candidates: int = 1000):
     """Enqueue ``boxes_from_bitmap`` for a batch of maps that are ON THE DEVICE (csrc/ctd_boxes.hip: labelling, border walk, minAreaRect,
-    score, round-join offset — all on the GPU) on the current stream; nothing is waited for.  pred f32 [B,H,W] (any page stride, rows
-    dense: ``lines[:, 0]`` of an NCHW map as it is).  -> a handle for ``boxes_from_bitmap_gpu_collect``."""
+    score, round-join offset — all on the GPU) on the current stream; nothing is waited for.  pred f32 [B,H,W], any strides
+    (``lines[:, 0]`` of an NCHW map as it is).  -> a handle for ``boxes_from_bitmap_gpu_collect``.
+
+    Ownership: the handle holds a private dense copy of ``pred``, queued on the current stream ahead of anything the caller enqueues
+    after this call.  The kernel and collect's host fallback read that copy, so the caller may overwrite ``pred``'s memory (a reused
+    workspace slab, the next micro-batch's map) as soon as launch returns: a flagged page is recomputed from the map as it was here."""
     import torch
 
     from . import ops
@@ -63,8 +67,7 @@ def boxes_from_bitmap_gpu_launch(pred, thresh: float, dest_width: int, dest_heig
     if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
         raise ValueError(f"boxes_from_bitmap_gpu expects a float32 CUDA tensor [B,H,W], got {pred.dtype} {tuple(pred.shape)} on {pred.device}")
     B, H, W = pred.shape
-    if pred.stride(2) != 1 or pred.stride(1) != W:
-        pred = pred.contiguous()
+    pred = pred.clone(memory_format=torch.contiguous_format)   # owned by the handle (see above); one B x H x W copy on the stream
     lib = _lib.load()
     dev = pred.device
     ws_bytes = int(lib.mit_boxes_from_bitmap_dev_workspace_bytes(B, H, W, max_candidates))
@@ -87,7 +90,12 @@ def boxes_from_bitmap_gpu_launch(pred, thresh: float, dest_width: int, dest_heig
 
 def boxes_from_bitmap_gpu_collect(h) -> List[Tuple[np.ndarray, np.ndarray]]:
     """Wait for a launched extraction and bring the boxes over: per page (boxes int64 [n,4,2], scores f32 [n]), the arrays the host routine
-    returns for that page.  A page with a border longer than a wave's LDS holds (8192 points) is computed by the host routine (same results)."""
+    returns for that page.  The kernel flags a page when one of its borders does not fit a workgroup's LDS; that page is computed by the
+    host routine (same results) on the handle's copy of the map taken at launch.  The causes of a flag:
+    * a border of more than 8192 contour points (BFB_CAP);
+    * a border with more than 4096 corner points, i.e. points whose incoming and outgoing steps differ (BFB_HCAP);
+    * a round-join offset polygon (unclip) with a point outside the 16-bit key range (-32768, 32768), or with more than 4096 points;
+    * a hull of more than 4096 vertices (of the corners or of the offset polygon; the point caps above are reached first)."""
     h["ev"].synchronize()
     meta_h, max_candidates = h["meta_h"], h["kw"]["max_candidates"]
     B = meta_h.shape[1]
@@ -97,7 +105,7 @@ def boxes_from_bitmap_gpu_collect(h) -> List[Tuple[np.ndarray, np.ndarray]]:
     scores_h = h["scores"][:, :kmax].cpu().numpy() if kmax else np.zeros((B, 0), np.float32)
     out = []
     for b in range(B):
-        if int(meta_h[1, b]) != 0:    # a border that does not fit a wave's LDS: this page on the host routine
+        if int(meta_h[1, b]) != 0:    # a border that does not fit a workgroup's LDS: this page on the host routine
             out.append(boxes_from_bitmap(h["pred"][b].cpu().numpy(), *h["args"], **h["kw"]))
         else:
             n = int(counts[b])

@@ -101,3 +101,54 @@ def test_coupled_batch_equals_the_plugin_chain_page_by_page(cuda):
             assert np.array_equal(res.inpainted[k].cpu().numpy(), np.asarray(out).astype(np.uint8))
         for p in (det, ocr, inp):
             run(p.unload())
+
+
+def _comb(h, w):
+    """A comb of 3-pixel teeth with 1-pixel gaps under a 10-row spine: one border far longer than the GPU extraction's 8192-point cap
+    (its page is flagged and recomputed on the host), scored ~0.9, above BOX_THRESH."""
+    m = np.zeros((h, w), np.float32)
+    m[:10] = 0.9
+    for x in range(0, w - 3, 4):
+        m[10:, x:x + 3] = 0.9
+    return m
+
+
+@pytest.mark.gpu
+def test_coupled_boxes_of_flagged_pages_come_from_their_own_maps(cuda):
+    """Five pages in micro-batches of two (the last one partial), pages 0 and 4 carrying a border over the GPU extraction's cap: every
+    page's text lines are the host routine's boxes of its OWN injected map, although later micro-batches rewrite the detector's output
+    slab before the boxes are collected.  Landscape pages (map rows dense: ``lines[:, 0]`` is a view of the slab) and portrait ones
+    (padded map rows), unpipelined and in pipeline slots of one page."""
+    from manga_image_translator_amd import coupled, ctd as CTD, hostglue as HG, pipeline, synth
+
+    T, D, B = 6, 211, 5
+    weights = pipeline.synthetic_weights(dict_size=D)
+    dictionary = ["<PAD>", "<S>", "</S>", "<SP>"] + [chr(0x4E00 + i) for i in range(D - 4)]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        eng = coupled.CoupledPageEngine(weights, dictionary, device=cuda, ctd_mb=2, lama_mb=2, host_workers=4)
+        for H, W in ((728, 1024), (1024, 728)):
+            _, _, dw, dh = CTD.CtdEngine.letterbox_geometry(H, W)
+            mh, mw = CTD.INPUT_SIZE - dh, CTD.INPUT_SIZE - dw
+            gen = [synth.synth_page(40 + b, H, W, n_boxes=4, disjoint=True) for b in range(B)]
+            heads = [coupled.synthetic_head_outputs(g[0], g[1], (mh, mw)) for g in gen]
+            prob = np.stack([h[0] for h in heads])
+            prob[0, 40:300, 40:440] = _comb(260, 400)                    # two different overflowing borders: a page that took its
+            prob[4, mh - 320:mh - 40, mw - 460:mw - 40] = _comb(280, 420)  # fallback on another page's map would show it
+            assert HG.contour_count(_comb(260, 400) > 0.3)[1] > 8192
+            inj = {"prob": torch.from_numpy(prob).to(cuda), "mask": torch.from_numpy(np.stack([h[1] for h in heads])).to(cuda)}
+            pages_dev = torch.from_numpy(np.stack([g[0] for g in gen])).to(cuda)
+            want = []
+            for b in range(B):
+                lm = np.zeros((1, 2, mh, mw), np.float32)
+                lm[0, 0] = prob[b]
+                boxes, scores = HG.ctd_boxes(lm, H, W)
+                boxes = boxes[scores > coupled.BOX_THRESH].astype(np.int64)
+                want.append(sorted(p.tolist() for p in boxes))
+            assert len(want[0]) >= 1 and want[0] != want[4]
+            for group in (None, 1):
+                res = eng.run(pages_dev, max_seq_length=T, suppress_eos=True, prob_threshold=0.0, inject=inj, group=group)
+                torch.cuda.synchronize()
+                for b in range(B):   # (OCR hands the lines of a page back in its chunk order)
+                    assert sorted(np.asarray(q.pts).tolist() for q in res.textlines[b]) == want[b], (H, W, group, b)
+        eng.close()
