@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 11
+#define MIT_ABI_VERSION 12
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -454,6 +454,42 @@ int mit_lama_mpe_rows(const uint8_t *mask_dev, const uint8_t *relpos_dev, const 
  * back to the page size before compositing there (:112-117) when the page had to be resized. */
 int mit_lama_post(const float *pred_dev, int64_t pred_pixstride, const uint8_t *img_dev, const uint8_t *mask_dev,
                   uint8_t *out_dev, int B, int H, int W, int composite, void *stream);
+
+/* AOT inpainter (the reference's ``Inpainter.default``): memory-bound pieces ---------------------------------------------
+ * Reference: manga_translator/inpainting/inpainting_aot.py (AOTGenerator :240-274) and the plugin path it inherits,
+ * inpainting_lama_mpe.py:_infer :82-117.  The convolutions run on mit_conv_gemm; every gated layer is ONE launch whose 2C
+ * output columns are (signal | gate). */
+
+/* u8 page [B,H,W,3] + u8 mask [B,H,W] -> fp32 NHWC [B,H,W,4] = (m, (rgb / 127.5f - 1) * (1 - m)), m = (mask / 255.0f >= 0.5):
+ * the inputs of AOTGenerator.forward, torch.cat([mask, img]) (:266), as _infer builds them (inpainting_lama_mpe.py:84-92). */
+int mit_aot_prep(const uint8_t *img_dev, const uint8_t *mask_dev, float *out_dev, int B, int H, int W, void *stream);
+
+/* The gate of GatedWSConvPadded / GatedWSTransposeConvPadded (:128-133, :142-146): per pixel, in [.., 2C] = (signal | gate) ->
+ * out [.., C] = signal * sigmoid(gate) * 1.8, then relu_nf (relu(x) * 1.7139588594436646, :35-36) when relu_nf != 0.  npix pixels
+ * with pixel strides in floats (the output may be a channel slice of a wider tensor).  C % 4 == 0, 16-byte aligned operands. */
+int mit_aot_gate(const float *in_dev, int64_t in_pixstride, float *out_dev, int64_t out_pixstride, int64_t npix, int C, int relu_nf,
+                 void *stream);
+
+/* Bytes of the workspace mit_aot_plane_stats needs for B planes of hw pixels x C channels. */
+int64_t mit_aot_plane_stats_ws(int B, int hw, int C);
+/* The plane statistics of my_layer_norm (:163-168) on NHWC x [B, hw, C] (batch / pixel strides in floats): mean [B, C] and
+ * istd [B, C] = 1 / (std + 1e-9) with the unbiased std over the hw pixels of each (b, c).  Two passes (the second sums around
+ * the mean of the first, so |mean| >> std stays accurate), double partial sums over fixed 512-pixel chunks reduced in a fixed
+ * order: deterministic, and a page's result does not depend on the batch it is in.  C a power of two in [4, 1024]. */
+int mit_aot_plane_stats(const float *x_dev, int64_t batch_stride, int64_t pixstride, int B, int hw, int C, void *ws_dev, int64_t ws_bytes,
+                        float *mean_dev, float *istd_dev, void *stream);
+
+/* AOTBlock's output (:189-192), in place over x: m = sigmoid(5 * (2 * (gate - mean) * istd - 1)), x = x * (1 - m) + fuse * m.
+ * x / fuse / gate [B, hw, C] with their own batch / pixel strides (floats); mean / istd [B, C] from mit_aot_plane_stats. */
+int mit_aot_blend(float *x_dev, int64_t x_bs, int64_t x_ps, const float *fuse_dev, int64_t f_bs, int64_t f_ps, const float *gate_dev,
+                  int64_t g_bs, int64_t g_ps, const float *mean_dev, const float *istd_dev, int B, int hw, int C, void *stream);
+
+/* The last gated layer's pair (tail[8], 3 signal + 3 gate channels at pixel stride pre_pixstride) -> signal * sigmoid(gate) * 1.8
+ * -> clip(-1, 1) (:274) -> ((x + 1) * 127.5f) truncated to u8 (inpainting_lama_mpe.py:114), composited with the page through
+ * mask >= 127 (:57-61,117).  composite == 0 stops after the truncation (``img_inpainted``, every pixel from the network), as in
+ * mit_lama_post.  preclip_dev (NULL = off): the value before the clip, [B,H,W,3]. */
+int mit_aot_post(const float *pre_dev, int64_t pre_pixstride, const uint8_t *img_dev, const uint8_t *mask_dev, uint8_t *out_dev,
+                 float *preclip_dev, int B, int H, int W, int composite, void *stream);
 
 /* Text-detection stage (ctd): memory-bound pieces and NHWC helpers ---------------------------
  * Reference: manga_translator/detection/ctd.py, ctd_utils/. */

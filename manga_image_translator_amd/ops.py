@@ -348,18 +348,22 @@ class Conv2d:
     """nn.Conv2d (+ folded eval BatchNorm2d + activation) as one ``mit_conv_gemm`` launch.
 
     weight: [Cout, Cin, kh, kw] (torch layout).  Input channels are zero-padded to a multiple
-    of 4 (``cin_pad``); the input tensor must then carry that many channels.
+    of 4 (``cin_pad``); the input tensor must then carry that many channels.  ``dilation`` d spreads
+    the taps: tap (ky, kx) reads offset (ky*d - py, kx*d - px).
     """
 
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, stride=1, padding=0,
                  pad_mode: int = PAD_ZERO, bn=None, act: int = ACT_NONE, alpha: float = 0.0, device="cuda",
-                 out_scale: Optional[torch.Tensor] = None):
+                 out_scale: Optional[torch.Tensor] = None, dilation: int = 1):
         Cout, Cin, kh, kw = weight.shape
         self.Cout, self.Cin_raw = Cout, Cin
         self.Cin = _round_up(Cin, 4)
         self.kh, self.kw = kh, kw
         self.sy, self.sx = (stride, stride) if isinstance(stride, int) else stride
         self.py, self.px = (padding, padding) if isinstance(padding, int) else padding
+        self.d = int(dilation)
+        if self.d < 1:
+            raise ValueError(f"Conv2d: dilation must be >= 1 (got {dilation})")
         self.pad_mode = pad_mode
         self.act, self.alpha = act, alpha
         w = weight.detach().to(torch.float32)
@@ -367,7 +371,7 @@ class Conv2d:
             w = torch.cat([w, torch.zeros(Cout, self.Cin - Cin, kh, kw)], dim=1)
         w_kn = w.permute(2, 3, 1, 0).reshape(kh * kw * self.Cin, Cout)  # K = (ky, kx, ci)
         self.w, self.Kp, self.Np = pack_weight_kn(w_kn, device)
-        self.taps = [(ky - self.py, kx - self.px, 0) for ky in range(kh) for kx in range(kw)]
+        self.taps = [(ky * self.d - self.py, kx * self.d - self.px, 0) for ky in range(kh) for kx in range(kw)]
         scale = bias_t = None
         if bn is not None:
             scale, bias_t = fold_bn(*bn, conv_bias=bias)
@@ -382,7 +386,8 @@ class Conv2d:
         self.bias = None if bias_t is None else bias_t.to(device).contiguous()
 
     def out_hw(self, H: int, W: int) -> Tuple[int, int]:
-        return ((H + 2 * self.py - self.kh) // self.sy + 1, (W + 2 * self.px - self.kw) // self.sx + 1)
+        d = self.d
+        return ((H + 2 * self.py - d * (self.kh - 1) - 1) // self.sy + 1, (W + 2 * self.px - d * (self.kw - 1) - 1) // self.sx + 1)
 
     def desc(self, x: torch.Tensor, out: torch.Tensor, pre: Optional[torch.Tensor] = None,
              post: Optional[torch.Tensor] = None) -> MitConvGemm:

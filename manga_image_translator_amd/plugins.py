@@ -8,6 +8,7 @@ Each class honours the contract of its reference counterpart:
   HipModel48pxCTCOCR     <- Model48pxCTCOCR     (ocr/model_48px_ctc.py:30-160)
   HipLamaMPEInpainter    <- LamaMPEInpainter    (inpainting/inpainting_lama_mpe.py:26-118)
   HipLamaLargeInpainter  <- LamaLargeInpainter  (inpainting/inpainting_lama_mpe.py:121-136)
+  HipAotInpainter        <- AotInpainter        (inpainting/inpainting_aot.py:11-33), the reference's ``Inpainter.default``
   HipESRGANUpscaler      <- ESRGANUpscalerPytorch (upscaling/esrgan_pytorch.py:512-549)
 
 Same lifecycle (``__init__`` touches no GPU; ``await load(device)`` / ``unload()`` / ``infer(...)``; infer before load
@@ -657,6 +658,30 @@ class HipLamaLargeInpainter(HipLamaMPEInpainter):
     N_BLOCKS, USE_MPE, CKPT = 18, False, "lama_large_512px.ckpt"
 
 
+class HipAotInpainter(HipLamaMPEInpainter):
+    """``--inpainter default``: the AOT generator (inpainting_aot.py:11-33).  Like the reference's AotInpainter it subclasses the
+    LaMa-MPE plugin and reuses its ``_infer`` unchanged (input / 127.5 - 1, output (x + 1) * 127.5 truncated: the model is not a
+    LamaFourier, inpainting_lama_mpe.py:84,114); only the model and its checkpoint differ.  ``weights``: {"aot": state_dict}."""
+    _KEY = _key = "default_hip"
+    _MODEL_MAPPING: Dict = {  # inpainting/inpainting_aot.py:12-18
+        "model": {
+            "url": _RELEASE + "inpainting.ckpt",
+            "hash": "878d541c68648969bc1b042a6e997f3a58e49b6c07c5636ad55130736977149f",
+            "file": ".",
+        },
+    }
+    CKPT = "inpainting.ckpt"
+    MB = 4   # pages per micro-batch of the engine: 16 full 2048 x 1456 pages run as four of them within one workspace
+
+    async def _load(self, device: str):
+        from . import aot
+
+        dev = _gpu_device(device)
+        w = self._weights or _load_aot_checkpoint(self)
+        self.engine = aot.AotEngine(w["aot"], device=dev, mb=self.MB)
+        self.device = device
+
+
 class HipESRGANUpscaler(_UpBase):
     """``--upscaler 4xultrasharp`` (RRDBNet 4x) on the HIP engine."""
     _KEY = _key = "4xultrasharp_hip"
@@ -898,6 +923,15 @@ def _load_lama_checkpoint(plugin):
     return out
 
 
+def _load_aot_checkpoint(plugin):
+    """inpainting.ckpt: {'model': state_dict} or a bare state_dict (inpainting_aot.py:27-28), schema-checked."""
+    from . import aot_schema, synth
+
+    ck = torch.load(_ckpt_path(plugin, plugin.CKPT), map_location="cpu")
+    sd = ck["model"] if "model" in ck else ck
+    return {"aot": synth.check_state_dict(sd, aot_schema.aot_generator_schema(), plugin.CKPT)}
+
+
 def _load_esrgan_checkpoint(plugin):
     """4xESRGAN.pth: a bare RRDBNet state_dict; the block count comes from its keys (esrgan_pytorch.py:526-528, infer_params :476-510)."""
     from . import esrgan_schema, synth
@@ -933,5 +967,6 @@ def register() -> None:
     for reg, enum_name, cls in ((DETECTORS, "Detector", HipComicTextDetector), (DETECTORS, "Detector", HipDefaultDetector),
                                 (OCRS, "Ocr", HipModel48pxOCR), (OCRS, "Ocr", HipModel48pxCTCOCR),
                                 (INPAINTERS, "Inpainter", HipLamaMPEInpainter), (INPAINTERS, "Inpainter", HipLamaLargeInpainter),
+                                (INPAINTERS, "Inpainter", HipAotInpainter),
                                 (UPSCALERS, "Upscaler", HipESRGANUpscaler)):
         reg[key(enum_name, cls._KEY)] = cls

@@ -16,7 +16,7 @@ import torch
 
 # schema entry: (name, shape, kind)
 #   kind: conv (OIHW), convT (IOHW, stride 2), linear (out,in), bias, bn_w, bn_b, bn_rm, bn_rv, nbt,
-#         embed, gamma (layer scale), scalar:<value>, buffer:<tag>
+#         embed, gamma (layer scale), gain (scaled-WS gain), scalar:<value>, buffer:<tag>
 Schema = List[Tuple[str, Tuple[int, ...], str]]
 
 
@@ -69,6 +69,8 @@ def synth_state_dict(schema: Schema, seed: int = 0, gain: float = 1.0) -> Dict[s
             t = torch.rand(shape, generator=g) * 0.4 + 0.8
         elif kind == "gamma":
             t = torch.rand(shape, generator=g) * 0.4 + 0.1
+        elif kind == "gain":  # gain of a scaled weight-standardised conv (inpainting_aot.py:63-64,99-100)
+            t = torch.rand(shape, generator=g) * 0.4 + 0.8
         elif kind == "nbt":
             t = torch.zeros(shape, dtype=torch.int64)
         elif kind.startswith("scalar:"):
