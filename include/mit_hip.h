@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 12
+#define MIT_ABI_VERSION 13
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -307,8 +307,12 @@ int mit_prof_kernels_read(MitProfKernelStat *stats, int max_stats, int *n_stats)
  *            (inpainting_lama_mpe.py:77-79,112-113), detection/common.py:79-84
  *   mode 1 = exact 2x shrink = 2x2 box mean (what OpenCV substitutes for both linear flavours at scale 1/2)
  *   mode 2 = cv2.INTER_LINEAR_EXACT (8.8 fixed point)             — resize_keep_aspect (utils/generic.py:251-255, _infer :64-66)
- * Tap tables (modes 0, 2) come from the host (manga_image_translator_amd/imgproc.py): per destination index the first source
- * index (int32) and two uint16 weights {w(idx), w(idx+1)}; idx+1 is clamped to the last row / column by the kernel. */
+ *   mode 3 = cv2.INTER_AREA at any ratio, both directions (ABI 13)  — the colorizer's denoiser cap and resize_pad
+ *            (colorization/manga_colorization_v2_utils/denoising/denoiser.py:75-77, utils/utils.py:17-38)
+ * Tap tables (modes 0, 2, 3) come from the host (manga_image_translator_amd/imgproc.py): per destination index the first source
+ * index (int32) and two uint16 weights {w(idx), w(idx+1)}; idx+1 is clamped to the last row / column by the kernel.  Mode 3: K
+ * uint16 numerators per destination index over the source length (K = ceil(src / dst) + 1 when both sides shrink, else 2; H, W
+ * <= 65535), result (2 N + H W) / (2 H W) with N the integer weighted sum. */
 int mit_resize_u8(const uint8_t *src_dev, int B, int H, int W, int C, uint8_t *dst_dev, int dh, int dw, int mode, const int *yidx_dev,
                   const uint16_t *ycoef_dev, const int *xidx_dev, const uint16_t *xcoef_dev, void *stream);
 /* cv2.bilateralFilter on 8-bit RGB pages [B,H,W,3] (mask_refinement/text_mask_utils.py:159 and detection/default.py:64 call it
@@ -490,6 +494,49 @@ int mit_aot_blend(float *x_dev, int64_t x_bs, int64_t x_ps, const float *fuse_de
  * mit_lama_post.  preclip_dev (NULL = off): the value before the clip, [B,H,W,3]. */
 int mit_aot_post(const float *pre_dev, int64_t pre_pixstride, const uint8_t *img_dev, const uint8_t *mask_dev, uint8_t *out_dev,
                  float *preclip_dev, int B, int H, int W, int composite, void *stream);
+
+/* manga-colorization-v2 colorizer (the reference's ``Colorizer.mc2``) -----------------------------------------------------
+ * Reference: manga_translator/colorization/manga_colorization_v2.py:_infer :42-74 and manga_colorization_v2_utils/.  The dense
+ * convolutions run on mit_conv_gemm; these are the grouped convolution, squeeze-and-excitation and the u8 glue (ABI 13). */
+
+/* Grouped 3x3 convolution of the ResNeXt blocks (networks/extractor.py:37-38, networks/models.py:131-133): NHWC fp32, Cin = Cout = C
+ * (a multiple of 16) in groups of cpg = 2 | 4 | 8 | 16 channels, stride 1 | 2, dilation d = padding = 1 | 2 | 4, zero padding, torch
+ * weight layout [C][cpg][3][3]; then v * scale[c] (optional) + bias[c] (optional) and act (MIT_ACT_NONE | RELU | LEAKY with alpha).
+ * Input and output are strided channel views: batch and pixel strides in floats (multiples of 4; rows are W pixels), 16-byte aligned.
+ * Each output is one fmaf chain over (tap, input channel) in that order: deterministic and independent of B. */
+int mit_grouped_conv3x3(const float *in_dev, int64_t in_bs, int64_t in_ps, int B, int H, int W, int C, int cpg, int stride, int dilation,
+                        const float *w_dev, const float *scale_dev, const float *bias_dev, int act, float alpha, float *out_dev,
+                        int64_t out_bs, int64_t out_ps, void *stream);
+/* LDS bytes one workgroup of mit_grouped_conv3x3 stages at that stride / dilation / group width. */
+int64_t mit_grouped_conv3x3_lds_bytes(int stride, int dilation, int cpg);
+
+/* Squeeze of Selayer (global_avgpool, networks/models.py:88-106): double partial sums per (sample, fixed 256-pixel chunk, channel)
+ * of x [B, hw, C] (batch / pixel strides in floats) into the workspace; C a power of two in [4, 1024]. */
+int64_t mit_se_squeeze_ws(int B, int hw, int C);
+int mit_se_squeeze(const float *x_dev, int64_t bs, int64_t ps, int B, int hw, int C, void *ws_dev, int64_t ws_bytes, void *stream);
+/* Excite, one workgroup per sample: mean = (sum of the chunks in index order) / hw, s = sigmoid(w2 relu(w1 mean + b1) + b2) with
+ * w1 [C/16][C], w2 [C][C/16] (the 1x1 convolutions conv1 / conv2); s [B][C]. */
+int mit_se_excite(const void *ws_dev, int B, int hw, int C, const float *w1_dev, const float *b1_dev, const float *w2_dev,
+                  const float *b2_dev, float *s_dev, void *stream);
+/* out = act(x * s[b][c] + residual), act MIT_ACT_RELU (encoder blocks, extractor.py:64-67) or MIT_ACT_NONE (tunnel blocks,
+ * models.py:150).  Each operand has its own batch / pixel strides (floats, multiples of 4); out may alias x or residual. */
+int mit_se_apply(const float *x_dev, int64_t x_bs, int64_t x_ps, const float *s_dev, const float *res_dev, int64_t r_bs, int64_t r_ps,
+                 float *out_dev, int64_t o_bs, int64_t o_ps, int B, int hw, int C, int act, void *stream);
+
+/* FFDNet input (denoiser.py:79-103, functions.py:16-56): u8 RGB(A) pages [B,H,W,Cin] -> fp32 [B,ceil(H/2),ceil(W/2),16] =
+ * (sigma, sigma, sigma, space-to-depth channel 3 + c*4 + (i*2 + j), 0).  Values are divided by 255 only on a page whose max
+ * (over RGB, found on the device into pmax_dev [B]) exceeds 1.2; odd sides repeat their last row / column. */
+int mit_mc2_ffd_pack(const uint8_t *img_dev, int B, int H, int W, int Cin, float sigma, unsigned *pmax_dev, float *out_dev, void *stream);
+/* FFDNet output (functions.py:58-83, denoiser.py:107-118, utils.py:17-33): depth-to-space of the 12-channel noise estimate (pixel
+ * stride in floats), clamp(x - noise, 0, 1), crop to H x W, RGB -> BGR, (v * 255) truncated to u8.  plane_dev [B,H,W] receives B (the
+ * channel the colorizer keeps, utils/utils.py:44), bgr_dev [B,H,W,3] the whole page; either may be NULL. */
+int mit_mc2_ffd_unpack(const uint8_t *img_dev, int B, int H, int W, int Cin, const unsigned *pmax_dev, const float *noise_dev,
+                       int64_t noise_pixstride, uint8_t *plane_dev, uint8_t *bgr_dev, void *stream);
+/* Generator input (utils/utils.py:27-38, ToTensor, manga_colorization_v2.py:58-59): u8 plane [B,h,w] -> fp32 [B,Hp,Wp,4] =
+ * (v / 255, 0, 0, 0) with np.pad(.., 'maximum') on the one padded side (rows: column max; columns: row max). */
+int mit_mc2_gen_in(const uint8_t *plane_dev, int B, int h, int w, float *out_dev, int Hp, int Wp, void *stream);
+/* Generator output (manga_colorization_v2.py:61-74): tanh(pre) * 0.5 + 0.5, crop to h x w, * 255 truncated -> u8 RGB [B,h,w,3]. */
+int mit_mc2_post(const float *pre_dev, int64_t pre_pixstride, int B, int Hp, int Wp, uint8_t *out_dev, int h, int w, void *stream);
 
 /* Text-detection stage (ctd): memory-bound pieces and NHWC helpers ---------------------------
  * Reference: manga_translator/detection/ctd.py, ctd_utils/. */

@@ -11,7 +11,10 @@
 //           (a + b + c + d + 2) >> 2
 //   mode 2  cv2.INTER_LINEAR_EXACT (resize_bitExact, ufixedpoint16): 8.8 coefficients, horizontal c0*a + c1*b in 16 bits,
 //           vertical (r0*h0 + r1*h1 + 32768) >> 16
-// Coefficient tables come from the host (imgproc.py): per destination index the first source index and two 16-bit weights.
+//   mode 3  cv2.INTER_AREA at any ratio (the colorizer's page resizes, colorization/manga_colorization_v2_utils): every weight is an
+//           integer over the source length, so the result is round-half-up of N / (H * W) computed exactly in integers
+// Coefficient tables come from the host (imgproc.py): per destination index the first source index and two 16-bit weights (mode 3:
+// ceil(src / dst) + 1 weights when both sides shrink, else 2).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mit_hip.h"
@@ -34,6 +37,30 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t *__restric
         if (mode == 1) {
             const uint8_t *q = p + ((int64_t)(2 * y) * W + 2 * x) * C;
             for (int k = 0; k < C; ++k) o[k] = (uint8_t)((q[k] + q[C + k] + q[(int64_t)W * C + k] + q[(int64_t)W * C + C + k] + 2) >> 2);
+            continue;
+        }
+        if (mode == 3) {   // INTER_AREA: integer weights over the source lengths, round-half-up of N / (H * W) in integers
+            const bool area = dh <= H && dw <= W;
+            const int ky_n = area ? (H + dh - 1) / dh + 1 : 2, kx_n = area ? (W + dw - 1) / dw + 1 : 2;
+            const int y0 = yidx[y], x0 = xidx[x];
+            const int64_t D = (int64_t)H * W;
+            for (int k = 0; k < C; ++k) {
+                int64_t N = 0;
+                for (int a = 0; a < ky_n; ++a) {
+                    const uint32_t cy = ycoef[(int64_t)y * ky_n + a];
+                    const int yy = y0 + a;
+                    if (cy == 0 || yy >= H) continue;
+                    const uint8_t *row = p + (int64_t)yy * W * C + k;
+                    uint32_t rs = 0;
+                    for (int e = 0; e < kx_n; ++e) {
+                        const uint32_t cx = xcoef[(int64_t)x * kx_n + e];
+                        const int xx = x0 + e;
+                        if (cx != 0 && xx < W) rs += cx * row[(int64_t)xx * C];
+                    }
+                    N += (int64_t)cy * rs;
+                }
+                o[k] = (uint8_t)((2 * N + D) / (2 * D));
+            }
             continue;
         }
         const int y0 = yidx[y], y1 = min(y0 + 1, H - 1), x0 = xidx[x], x1 = min(x0 + 1, W - 1);
@@ -72,7 +99,9 @@ extern "C" int mit_resize_u8(const uint8_t *src_dev, int B, int H, int W, int C,
                              const int *yidx_dev, const uint16_t *ycoef_dev, const int *xidx_dev, const uint16_t *xcoef_dev, void *stream) {
     if (!src_dev || !dst_dev) return mit_set_error("mit_resize_u8: null pointer");
     if (B <= 0 || H <= 0 || W <= 0 || dh <= 0 || dw <= 0 || C < 1 || C > 4) return mit_set_error("mit_resize_u8: bad shape (1 <= C <= 4)");
-    if (mode < 0 || mode > 2) return mit_set_error("mit_resize_u8: mode must be 0 (INTER_LINEAR), 1 (2x box mean) or 2 (INTER_LINEAR_EXACT)");
+    if (mode < 0 || mode > 3)
+        return mit_set_error("mit_resize_u8: mode must be 0 (INTER_LINEAR), 1 (2x box mean), 2 (INTER_LINEAR_EXACT) or 3 (INTER_AREA)");
+    if (mode == 3 && (H > 65535 || W > 65535)) return mit_set_error("mit_resize_u8: mode 3 takes sides up to 65535 (16-bit weights)");
     if (mode == 1 && (H != 2 * dh || W != 2 * dw)) return mit_set_error("mit_resize_u8: mode 1 needs an exact 2x shrink");
     if (mode != 1 && (!yidx_dev || !ycoef_dev || !xidx_dev || !xcoef_dev)) return mit_set_error("mit_resize_u8: missing tap tables");
     const int64_t total = (int64_t)B * dh * dw;

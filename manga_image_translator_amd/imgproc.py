@@ -22,7 +22,63 @@ from typing import Tuple
 import numpy as np
 import torch
 
-INTER_LINEAR, BOX_2X, INTER_LINEAR_EXACT = 0, 1, 2
+INTER_LINEAR, BOX_2X, INTER_LINEAR_EXACT, INTER_AREA = 0, 1, 2, 3
+
+
+@lru_cache(maxsize=64)
+def area_taps(n_src: int, n_dst: int, area: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """INTER_AREA taps of one axis as oracle.lama.resize_area_u8 states them, every weight an integer over ``n_src``: per destination
+    index the first source index (int32) and K uint16 numerators.  ``area`` (both sides shrink): the box [d s, (d + 1) s) with
+    s = n_src / n_dst, numerators = overlaps in units of 1 / n_dst, K = ceil(n_src / n_dst) + 1.  Otherwise OpenCV's bilinear branch
+    with the INTER_AREA coefficient rule sx = floor(d s), f = (d + 1) - (sx + 1) / s (f <= 0 -> 0), K = 2."""
+    if n_src > 65535:
+        raise ValueError("INTER_AREA taps: sides up to 65535")
+    if area:
+        K = -(-n_src // n_dst) + 1
+        idx = np.zeros(n_dst, np.int32)
+        coef = np.zeros((n_dst, K), np.uint16)
+        for d in range(n_dst):
+            lo, hi = d * n_src, (d + 1) * n_src          # in units of 1 / n_dst
+            s0 = lo // n_dst
+            idx[d] = s0
+            for k in range(K):
+                s = s0 + k
+                if s >= n_src:
+                    break
+                coef[d, k] = max(0, min(hi, (s + 1) * n_dst) - max(lo, s * n_dst))
+    else:
+        scale = n_src / n_dst
+        idx = np.zeros(n_dst, np.int32)
+        coef = np.zeros((n_dst, 2), np.uint16)
+        for d in range(n_dst):
+            s = int(np.floor(d * scale))
+            fn = (d + 1) * n_src - (s + 1) * n_dst       # f * n_src, exact
+            fn = 0 if fn <= 0 else fn
+            if s < 0:
+                s, fn = 0, 0
+            if s >= n_src - 1:
+                s, fn = n_src - 1, 0
+            idx[d] = s
+            coef[d] = (n_src - fn, fn)
+    idx.setflags(write=False)
+    coef.setflags(write=False)
+    return idx, coef
+
+
+def _area_host(s: np.ndarray, dh: int, dw: int) -> np.ndarray:
+    sh, sw = s.shape[:2]
+    area = dh <= sh and dw <= sw
+    yi, yc = area_taps(sh, dh, area)
+    xi, xc = area_taps(sw, dw, area)
+    t = s.astype(np.int64)
+    rows = np.zeros((sh, dw, s.shape[2]), np.int64)
+    for k in range(xc.shape[1]):
+        rows += t[:, np.minimum(xi + k, sw - 1)] * xc[None, :, k, None].astype(np.int64)
+    N = np.zeros((dh, dw, s.shape[2]), np.int64)
+    for k in range(yc.shape[1]):
+        N += rows[np.minimum(yi + k, sh - 1)] * yc[:, k, None, None].astype(np.int64)
+    D = sh * sw
+    return ((2 * N + D) // (2 * D)).astype(np.uint8)
 
 
 @lru_cache(maxsize=64)
@@ -69,15 +125,17 @@ def pick_mode(sh: int, sw: int, dh: int, dw: int, exact: bool) -> int:
     return INTER_LINEAR_EXACT if exact else INTER_LINEAR
 
 
-def resize_u8_host(src: np.ndarray, dsize: Tuple[int, int], exact: bool = False) -> np.ndarray:
-    """cv2.resize(src, (w, h), INTER_LINEAR / INTER_LINEAR_EXACT) for uint8 [H,W] or [H,W,C] in numpy, from the same tables the
-    device kernel uses."""
+def resize_u8_host(src: np.ndarray, dsize: Tuple[int, int], exact: bool = False, area: bool = False) -> np.ndarray:
+    """cv2.resize(src, (w, h), INTER_LINEAR / INTER_LINEAR_EXACT, or INTER_AREA with ``area``) for uint8 [H,W] or [H,W,C] in numpy,
+    from the same tables the device kernel uses."""
     dw, dh = int(dsize[0]), int(dsize[1])
     squeeze = src.ndim == 2
     s = src[..., None] if squeeze else src
     sh, sw = s.shape[:2]
-    mode = pick_mode(sh, sw, dh, dw, exact)
-    if (sh, sw) == (dh, dw):
+    mode = INTER_AREA if area else pick_mode(sh, sw, dh, dw, exact)
+    if mode == INTER_AREA:
+        out = _area_host(s, dh, dw)
+    elif (sh, sw) == (dh, dw):
         out = s.copy()
     elif mode == BOX_2X:
         t = s.astype(np.int32)
@@ -107,8 +165,9 @@ def resize_keep_aspect_host(img: np.ndarray, size: int) -> np.ndarray:
     return resize_u8_host(img, keep_aspect_size(img.shape[0], img.shape[1], size), exact=True)
 
 
-def resize_u8(src: torch.Tensor, dsize: Tuple[int, int], exact: bool = False) -> torch.Tensor:
-    """Device resize of a uint8 tensor [B,H,W,C] (or [B,H,W]) to (w, h) = ``dsize`` through ``mit_resize_u8``."""
+def resize_u8(src: torch.Tensor, dsize: Tuple[int, int], exact: bool = False, area: bool = False) -> torch.Tensor:
+    """Device resize of a uint8 tensor [B,H,W,C] (or [B,H,W]) to (w, h) = ``dsize`` through ``mit_resize_u8``; ``area``: INTER_AREA
+    (mode 3)."""
     from . import lib as _lib
     from . import ops
 
@@ -122,10 +181,20 @@ def resize_u8(src: torch.Tensor, dsize: Tuple[int, int], exact: bool = False) ->
     dw, dh = int(dsize[0]), int(dsize[1])
     if (sh, sw) == (dh, dw):
         return src.clone()
-    mode = pick_mode(sh, sw, dh, dw, exact)
+    mode = INTER_AREA if area else pick_mode(sh, sw, dh, dw, exact)
     out = torch.empty(B, dh, dw, Cc, dtype=torch.uint8, device=s.device)
     tabs = [None] * 4
-    if mode != BOX_2X:
+    if mode == INTER_AREA:
+        both = dh <= sh and dw <= sw
+        yi, yc = area_taps(sh, dh, both)
+        xi, xc = area_taps(sw, dw, both)
+        blob = np.concatenate([yi.view(np.uint8), xi.view(np.uint8), yc.reshape(-1).view(np.uint8), xc.reshape(-1).view(np.uint8)])
+        dev = torch.from_numpy(blob.copy()).to(s.device)
+        o1, o2 = 4 * dh, 4 * dh + 4 * dw
+        o3 = o2 + 2 * yc.size
+        tabs = [dev.data_ptr(), dev.data_ptr() + o2, dev.data_ptr() + o1, dev.data_ptr() + o3]
+        keep = dev  # noqa: F841 - alive until the launch is queued (same stream as the free)
+    elif mode != BOX_2X:
         yi, yc = linear_taps(sh, dh, exact)
         xi, xc = linear_taps(sw, dw, exact)
         blob = np.concatenate([yi.view(np.uint8), xi.view(np.uint8), yc.reshape(-1).view(np.uint8), xc.reshape(-1).view(np.uint8)])

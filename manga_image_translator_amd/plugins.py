@@ -10,6 +10,7 @@ Each class honours the contract of its reference counterpart:
   HipLamaLargeInpainter  <- LamaLargeInpainter  (inpainting/inpainting_lama_mpe.py:121-136)
   HipAotInpainter        <- AotInpainter        (inpainting/inpainting_aot.py:11-33), the reference's ``Inpainter.default``
   HipESRGANUpscaler      <- ESRGANUpscalerPytorch (upscaling/esrgan_pytorch.py:512-549)
+  HipMangaColorizer      <- MangaColorizationV2 (colorization/manga_colorization_v2.py:13-74), the reference's ``Colorizer.mc2``
 
 Same lifecycle (``__init__`` touches no GPU; ``await load(device)`` / ``unload()`` / ``infer(...)``; infer before load
 raises), same ``_infer`` signatures, argument meaning and return types, errors as Python exceptions.  When the
@@ -36,6 +37,7 @@ try:  # inside the reference's environment: be a real plugin
     from manga_translator.inpainting.common import OfflineInpainter as _InpBase  # type: ignore
     from manga_translator.ocr.common import OfflineOCR as _OcrBase  # type: ignore
     from manga_translator.upscaling.common import OfflineUpscaler as _UpBase  # type: ignore
+    from manga_translator.colorization.common import OfflineColorizer as _ColBase  # type: ignore
     from manga_translator.utils import Quadrilateral as _RefQuadrilateral  # type: ignore
 
     HAVE_REFERENCE = True
@@ -110,6 +112,7 @@ except Exception:  # stand-alone: mirror the ModelWrapper lifecycle
     _OcrBase = type("_OcrBase", (_Wrapper,), {"_MODEL_SUB_DIR": "ocr"})
     _InpBase = type("_InpBase", (_Wrapper,), {"_MODEL_SUB_DIR": "inpainting"})
     _UpBase = type("_UpBase", (_Wrapper,), {"_MODEL_SUB_DIR": "upscaling"})
+    _ColBase = type("_ColBase", (_Wrapper,), {"_MODEL_SUB_DIR": "colorization"})
 
 
 _RELEASE = "https://github.com/zyddnys/manga-image-translator/releases/download/beta-0.3/"
@@ -729,6 +732,54 @@ class HipESRGANUpscaler(_UpBase):
         return out
 
 
+class HipMangaColorizer(_ColBase):
+    """``--colorizer mc2`` (manga-colorization-v2: FFDNet denoiser + SE-ResNeXt generator) on the HIP engine.  Same ``_infer(image,
+    colorization_size, denoise_sigma=25)`` -> RGB ``PIL.Image`` at the network's size, like the reference.  ``weights``:
+    {"generator": state_dict, "denoiser": state_dict}."""
+    _KEY = _key = "mc2_hip"
+    _MODEL_SUB_DIR = os.path.join(_ColBase._MODEL_SUB_DIR, "manga-colorization-v2")
+    _MODEL_MAPPING: Dict = {  # colorization/manga_colorization_v2.py:15-27
+        "generator": {
+            "url": _RELEASE + "manga-colorization-v2-generator.zip",
+            "file": "generator.zip",
+            "hash": "087e6a0bc02770e732a52f33878b71a272a6123c9ac649e9b5bfb75e39e5c1d5",
+        },
+        "denoiser": {
+            "url": _RELEASE + "manga-colorization-v2-net_rgb.pth",
+            "file": "net_rgb.pth",
+            "hash": "0fe98bfd2ac870b15f360661b1c4789eecefc6dc2e4462842a0dd15e149a0433",
+        },
+    }
+
+    def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._weights = weights
+        self.engine = None
+        _weights_handed_over(self, weights)
+
+    async def _load(self, device: str):
+        from . import mc2
+
+        dev = _gpu_device(device)
+        w = self._weights or _load_mc2_checkpoint(self)
+        self.engine = mc2.Mc2Engine(w["generator"], w["denoiser"], device=dev)
+        self.device = device
+
+    async def _unload(self):
+        if self.engine is not None:
+            self.engine.release_workspace()
+        self.engine = None
+
+    @torch.no_grad()
+    async def _infer(self, image, colorization_size: int, denoise_sigma=25, **kwargs):
+        """PIL page -> colorized RGB PIL image (manga_colorization_v2.py:42-74); ``kwargs`` takes the context keys dispatch passes."""
+        from PIL import Image
+
+        page = np.ascontiguousarray(np.array(image.convert("RGBA")))
+        out = self.engine.forward(torch.from_numpy(page).to(self.engine.device)[None], colorization_size, denoise_sigma)
+        return Image.fromarray(out[0].cpu().numpy())
+
+
 # ---- pieces taken from the reference package when it is importable ---------------------------------------------
 
 def _native_ctd_boxes(lines_map, im_h, im_w):
@@ -943,6 +994,17 @@ def _load_esrgan_checkpoint(plugin):
     return synth.check_state_dict(sd, esrgan_schema.rrdbnet_schema(nb), "4xESRGAN.pth")
 
 
+def _load_mc2_checkpoint(plugin):
+    """generator.zip (a bare Generator state_dict, manga_colorization_v2.py:33-34) and net_rgb.pth (FFDNet, with or without the
+    DataParallel ``module.`` prefix, denoising/denoiser.py:36-48), schema-checked."""
+    from . import mc2_schema, synth
+
+    g = torch.load(_ckpt_path(plugin, "generator.zip"), map_location="cpu")
+    d = mc2_schema.strip_dataparallel(torch.load(_ckpt_path(plugin, "net_rgb.pth"), map_location="cpu"))
+    return {"generator": synth.check_state_dict(g, mc2_schema.generator_schema(), "generator.zip"),
+            "denoiser": synth.check_state_dict(d, mc2_schema.ffdnet_schema(), "net_rgb.pth")}
+
+
 def register() -> None:
     """Add the HIP backends to the reference's registries (needs the reference package; INTEGRATION.md shows the
     matching enum members)."""
@@ -953,6 +1015,7 @@ def register() -> None:
     from manga_translator.ocr import OCRS  # type: ignore
 
     from manga_translator.upscaling import UPSCALERS  # type: ignore
+    from manga_translator.colorization import COLORIZERS  # type: ignore
     from manga_translator import config as _cfg  # type: ignore
 
     def key(enum_name: str, value: str):
@@ -968,5 +1031,5 @@ def register() -> None:
                                 (OCRS, "Ocr", HipModel48pxOCR), (OCRS, "Ocr", HipModel48pxCTCOCR),
                                 (INPAINTERS, "Inpainter", HipLamaMPEInpainter), (INPAINTERS, "Inpainter", HipLamaLargeInpainter),
                                 (INPAINTERS, "Inpainter", HipAotInpainter),
-                                (UPSCALERS, "Upscaler", HipESRGANUpscaler)):
+                                (UPSCALERS, "Upscaler", HipESRGANUpscaler), (COLORIZERS, "Colorizer", HipMangaColorizer)):
         reg[key(enum_name, cls._KEY)] = cls
