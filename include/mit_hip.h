@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 13
+#define MIT_ABI_VERSION 14
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -129,15 +129,6 @@ int mit_abi_version(void);
  * binding refuses (or rebuilds) a library whose digest differs from the tree's, so stale kernels are never measured. */
 const char *mit_source_digest(void);
 
-/* The mitigation that shipped before the co-tenancy failure was understood: mit_rfft_rows / mit_irfft_rows were
- * seen returning wrong workgroups while ANOTHER queue's kernel (a second process on the GPU, a second stream) that issues MFMAs was
- * resident on the same CU; with this on they read LDS with 4-byte loads and take a whole CU's LDS, so nothing fits beside them (about 3 %
- * of a LaMa forward).  The cause was the SLP vectoriser's packed-fp32 instructions; the library is built without them now and gives
- * the one-stream bytes beside any co-tenant in its DEFAULT launch form (tests/test_cotenant_gpu.py), so this switch is no longer needed —
- * it stays for A/B runs.  Off by default; initial value from MIT_COTENANT_SAFE in the environment.  on < 0 only queries.  Returns the
- * previous value.  Nothing in the reference corresponds to it. */
-int mit_cotenant_safe_set(int on);
-
 /* device / runtime ------------------------------------------------------------------- */
 int mit_device_count(int *count);
 int mit_device_name(int device, char *buf, int buflen);
@@ -175,8 +166,8 @@ int mit_gemm_split_pack(const float *w_dev, int64_t w_zs, int nz, int Kw, int64_
 int mit_gemm_mode_set(int mode);
 int mit_gemm_mode_get(void);
 /* Smallest launch, counted in 128 x 64 output tiles (x Z), that the automatic choice hands to the split tiles (default 0 — every
- * eligible launch, which keeps a page's result independent of the batch it is part of — or MIT_GEMM_SPLIT_MIN_TILES); n >= 0 sets it,
- * n < 0 only queries.  Returns the previous value.  A tuning knob: 1280 = one full wave of workgroups. */
+ * eligible launch, which keeps a page's result independent of the batch it is part of); n >= 0 sets it, n < 0 only queries.  Returns
+ * the previous value.  A tuning knob: 1280 = one full wave of workgroups. */
 int64_t mit_gemm_split_min_tiles(int64_t n);
 
 /* ---- planar operands: the plain GEMMs of the split-bf16 mode with activations that ARRIVE split ---------------------------------
@@ -698,9 +689,9 @@ typedef struct MitOcr48DecodeArgs {
     float *trace_logits;        /* optional [T][N*5][dict] raw logits (pred(pred1(decoded)), :713); NULL in production */
     int32_t *trace_hist;        /* optional [T][N*5][T+1] beam tokens after each step */
     int32_t steps_run;          /* out: steps executed */
-    int32_t graph_mode;         /* 1: replay the steps from a hipGraph (one launch per step instead of 74); 2: never; 0: as
-                                 * MIT_OCR_DECODE_GRAPH says (default off: measured 50.2 vs 50.6 ms per page, the loop is bound by its
-                                 * kernels' latency, not by launches).  Same kernels either way: identical results. */
+    int32_t graph_mode;         /* 1: replay the steps from a hipGraph (one launch per step instead of 74); else launch by launch
+                                 * (the default: measured 50.2 vs 50.6 ms per page, the loop is bound by its kernels' latency, not by
+                                 * launches).  Same kernels either way: identical results. */
 } MitOcr48DecodeArgs;
 
 /* One text line to rectify: cv2.warpPerspective of the page crop [y1:y1+ch, x1:x1+cw] to (dw, dh) with inverse map minv
@@ -797,8 +788,8 @@ int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *args, void 
 /* Largest number of decoder rows (5 N: lines x beams) whose steps run in the few-row form — every Linear of a step as one wave per
  * 32 x 32 output block on bf16-plane activations (pgemm_rows_kernel), the LayerNorm / attention kernels producing the planes — instead
  * of the tiled form that pays off on full batches.  Both forms give identical results (tests/test_ocr_gpu.py); the few-row one takes a
- * third of the time per Linear at one page.  Needs GEMM mode 6 | 9.  rows < 0 only queries; 0 = never.  Initial value: MIT_OCR_ROWS_MAX in
- * the environment, else 2560 (16 pages of 32 lines).  Returns the previous value.  Nothing in the reference corresponds to it. */
+ * third of the time per Linear at one page.  Needs GEMM mode 6 | 9.  rows < 0 only queries; 0 = never.  Initial value 2560 (16 pages of
+ * 32 lines).  Returns the previous value.  Nothing in the reference corresponds to it. */
 int mit_ocr48_decode_rows_max_set(int rows);
 
 #ifdef __cplusplus

@@ -33,7 +33,6 @@ from . import ctd, hostglue, imgproc, lama, mask_refinement as MR, ocr48, textli
 from .textline import Quadrilateral
 
 BOX_THRESH = 0.6          # ctd.py:157-159
-GPU_BOXES = os.environ.get("MIT_BOXES_HOST", "0") in ("", "0")   # MIT_BOXES_HOST=1: the per-page host extraction of rounds 3-5 (A/B)
 MASK_DILATION_OFFSET = 20  # config.py:344
 KERNEL_SIZE = 3            # config.py:342
 
@@ -99,7 +98,6 @@ class CoupledPageEngine:
         self._side = None
         self.stage_streams = bool(int(os.environ.get("MIT_COUPLED_STAGE_STREAMS", "0")))
         self._stage = None
-        self.ocr_slots = int(os.environ.get("MIT_COUPLED_OCR_SLOTS", "1"))   # pipeline slots recognised together (the OCR stage's own granularity)
 
     def _mask_backend(self):
         be = getattr(self._tls, "backend", None)
@@ -116,7 +114,6 @@ class CoupledPageEngine:
     def detect(self, pages_u8: torch.Tensor, inject=None):
         """-> (textlines per page, refined mask u8 [B,H,W] on the device): ComicTextDetector._infer (ctd.py:129-179) for a batch."""
         B, H, W, _ = pages_u8.shape
-        futures: List[Optional[cf.Future]] = [None] * B
         mask_full = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
         keep = []
         for i in range(0, B, self.ctd_mb):
@@ -125,26 +122,14 @@ class CoupledPageEngine:
             if inject is not None:   # benchmark stand-in for trained weights: the maps a trained head would emit REPLACE the random-init
                 lines[:, 0] = inject["prob"][i:j]     # network's (its sigmoid output hovers around 0.5 everywhere: one page-sized blob);
                 mask_u8 = inject["mask"][i:j]         # the network has run in full by now, its cost is in the measurement
-            if GPU_BOXES:   # SegDetectorRepresenter (db_utils.py:40-216) where the map is (csrc/ctd_boxes.hip): enqueued behind the network,
-                keep.append((i, j, hostglue.boxes_from_bitmap_gpu_launch(lines[:, 0], 0.3, W, H, unclip_ratio=1.5, min_sside=2.0)))   # collected below
-                mask_full[i:j] = imgproc.resize_u8(mask_u8.contiguous(), (W, H))      # cv2.resize(mask, (w, h), INTER_LINEAR) (ctd.py:162)
-                continue
-            host = torch.empty(lines.shape, dtype=torch.float32, pin_memory=True)   # [b,2,h,w]: box_score_fast needs the float map
-            host.copy_(lines, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            mask_full[i:j] = imgproc.resize_u8(mask_u8.contiguous(), (W, H))          # cv2.resize(mask, (w, h), INTER_LINEAR) (ctd.py:162)
-            keep.append(host)
-            for b in range(i, j):
-                futures[b] = self.pool.submit(self._boxes_of_page, host, b - i, ev, H, W)
-        if GPU_BOXES:
-            textlines = [None] * B
-            for i, j, h in keep:
-                for b, (boxes, scores) in zip(range(i, j), hostglue.boxes_from_bitmap_gpu_collect(h)):
-                    k = scores > BOX_THRESH
-                    textlines[b] = [Quadrilateral(pts.astype(np.int64), "", float(s)) for pts, s in zip(boxes[k], scores[k])]
-        else:
-            textlines = [f.result() for f in futures]
+            # SegDetectorRepresenter (db_utils.py:40-216) where the map is (csrc/ctd_boxes.hip): enqueued behind the network, collected below
+            keep.append((i, j, hostglue.boxes_from_bitmap_gpu_launch(lines[:, 0], 0.3, W, H, unclip_ratio=1.5, min_sside=2.0)))
+            mask_full[i:j] = imgproc.resize_u8(mask_u8.contiguous(), (W, H))      # cv2.resize(mask, (w, h), INTER_LINEAR) (ctd.py:162)
+        textlines = [None] * B
+        for i, j, h in keep:
+            for b, (boxes, scores) in zip(range(i, j), hostglue.boxes_from_bitmap_gpu_collect(h)):
+                k = scores > BOX_THRESH
+                textlines[b] = [Quadrilateral(pts.astype(np.int64), "", float(s)) for pts, s in zip(boxes[k], scores[k])]
         refined = torch.empty_like(mask_full)
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
 
@@ -161,13 +146,6 @@ class CoupledPageEngine:
         # for the whole queue): no table keyed by address that a failed stage could leave behind for an unrelated tensor to inherit
         refined.mit_ready_event = torch.cuda.current_stream().record_event()
         return textlines, refined
-
-    @staticmethod
-    def _boxes_of_page(host_lines: torch.Tensor, k: int, ev, H: int, W: int) -> List[Quadrilateral]:
-        ev.synchronize()
-        boxes, scores = hostglue.ctd_boxes(host_lines[k:k + 1].numpy(), H, W)    # SegDetectorRepresenter (db_utils.py:40-216), native C++
-        keep = scores > BOX_THRESH
-        return [Quadrilateral(pts.astype(np.int64), "", float(s)) for pts, s in zip(boxes[keep], scores[keep])]
 
     # ---- stage 2: OCR ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -318,18 +296,12 @@ class CoupledPageEngine:
             inj = None if inject is None else {k: v[a:b] for k, v in inject.items()}
             return timed("detect+boxes+refine_mask", self.detect, pages_u8[a:b], inj)
 
-        def st_ocr(first, futs):   # ``ocr_slots`` consecutive slots in one recognition: its beam search sees that many more rows per launch
-            dets = [f.result() for f in futs]
-            a, b = spans[first][0], spans[first + len(futs) - 1][1]
-            tl = timed("ocr", self.recognize, pages_u8[a:b], [t for d in dets for t in d[0]], max_seq_length, suppress_eos, prob_threshold)
-            out, k = [], 0
-            for (sa, sb), d in zip(spans[first:first + len(futs)], dets):
-                out.append((tl[k:k + sb - sa], d[1]))
-                k += sb - sa
-            return out
+        def st_ocr(a, b, f_det):
+            tl, mraw = f_det.result()
+            return timed("ocr", self.recognize, pages_u8[a:b], tl, max_seq_length, suppress_eos, prob_threshold), mraw
 
-        def st_tail(a, b, f_ocr, k):
-            tl, mraw = f_ocr.result()[k]
+        def st_tail(a, b, f_ocr):
+            tl, mraw = f_ocr.result()
             regions, m = timed("textline_merge+mask_refinement", self.merge_and_refine, pages_u8[a:b], tl, mraw)
             with torch.cuda.stream(st["tail"]):
                 mask[a:b] = m
@@ -338,9 +310,8 @@ class CoupledPageEngine:
 
         with cf.ThreadPoolExecutor(1, "mit-st-det") as e1, cf.ThreadPoolExecutor(1, "mit-st-ocr") as e2, cf.ThreadPoolExecutor(1, "mit-st-tail") as e3:
             f1 = [e1.submit(st_detect, a, b) for a, b in spans]
-            ns = max(1, int(self.ocr_slots))
-            f2 = [e2.submit(st_ocr, i, f1[i:i + ns]) for i in range(0, len(spans), ns)]
-            f3 = [e3.submit(st_tail, a, b, f2[i // ns], i % ns) for i, (a, b) in enumerate(spans)]
+            f2 = [e2.submit(st_ocr, a, b, f) for (a, b), f in zip(spans, f1)]
+            f3 = [e3.submit(st_tail, a, b, f) for (a, b), f in zip(spans, f2)]
             done = [f.result() for f in f3]
         for x in st.values():
             if x is not caller:

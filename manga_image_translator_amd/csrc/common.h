@@ -45,11 +45,6 @@ struct DynSmemOptIn {
     }
 };
 
-// MIT_COTENANT_SAFE (mit_cotenant_safe_set): the pre-fix mitigation of the co-tenancy failure — the FFT rows kernels take a
-// whole CU's LDS so that no other queue's kernel can be co-resident.  Not needed since the library is built without SLP-packed fp32
-// instructions; off by default, kept as a switch.
-bool mit_cotenant_safe();
-
 // ---- generic kernel-time probe (mit_prof_kernels_read): while mit_prof_enable(1) is in force, a MitProbeScope around a
 // launch brackets it with HIP events on its stream and files it under `name` with the caller's algorithmic bytes / FLOPs.
 bool mit_probe_on();

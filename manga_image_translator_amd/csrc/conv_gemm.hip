@@ -19,7 +19,6 @@ const CfgEntry kCfgs[] = {
 #define KNAME_launch_fast "conv_gemm_fast_kernel"
 #define KNAME_launch_gemv "conv_gemv_kernel"
 #define KNAME_launch_split "conv_gemm_split_kernel"
-#define KNAME_launch_split_pp "conv_gemm_split_pp_kernel"
 #define X(g, name, fast, BM, BN, BK, fn, ...) \
     {name, BM, BN, BK, fn<BM, BN, BK, __VA_ARGS__>, fast, KNAME_##fn "<" #BM ", " #BN ", " #BK ", " #__VA_ARGS__ ">"},
 #include "conv_gemm_cfgs.inc"
@@ -105,33 +104,15 @@ int gemm_mode_now() {
     return m;
 }
 
-// smallest launch (in 128 x 64 tiles) the automatic choice gives to the split tiles.  Default 0: every eligible launch takes them, so
-// that a layer's arithmetic — and with it a page's result — does not depend on how many pages share the batch (a size threshold made
-// the same layer run on the fp32 tiles at B = 1 and on the split tiles at B = 16).  -1 = not read yet (MIT_GEMM_SPLIT_MIN_TILES)
-std::atomic<long long> g_split_min{-1};
-int64_t split_min_now() {
-    long long m = g_split_min.load(std::memory_order_relaxed);
-    if (m < 0) {
-        const char *v = getenv("MIT_GEMM_SPLIT_MIN_TILES");
-        m = (v && *v) ? atoll(v) : 0;
-        if (m < 0) m = 0;
-        g_split_min.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
-
-int env_cfg(const char *name, const char *dflt_name) {  // tuning knob for scripts/: replaces a default fast tile by another fast tile, BY NAME
-    const int dflt = dflt_name ? cfg_by_name(dflt_name) : -1;  // -1: rule off
-    const char *v = getenv(name);
-    if (!v || !*v) return dflt;
-    const int c = cfg_by_name(v);
-    return (c >= 0 && kCfgs[c].fast == 1 && kCfgs[c].BK == 16) ? c : dflt;
-}
+// smallest launch (in 128 x 64 tiles) the automatic choice gives to the split tiles (mit_gemm_split_min_tiles).  Default 0: every
+// eligible launch takes them, so that a layer's arithmetic — and with it a page's result — does not depend on how many pages share the
+// batch (a size threshold made the same layer run on the fp32 tiles at B = 1 and on the split tiles at B = 16)
+std::atomic<long long> g_split_min{0};
+int64_t split_min_now() { return g_split_min.load(std::memory_order_relaxed); }
 
 int pick_cfg(const MitConvGemm &p, int64_t M) {
     // measured on MI355X (scripts/bench_conv.py)
-    static const int wide = env_cfg("MIT_CONV_TILE_WIDE", "fast128x128x16w4c"), narrow = env_cfg("MIT_CONV_TILE_NARROW", "fast128x64x16w5c");
-    static const int m192 = env_cfg("MIT_CONV_TILE_M192", "fast192x64x16w4c"), bigk = env_cfg("MIT_CONV_TILE_BIGK", nullptr);
+    static const int wide = cfg_by_name("fast128x128x16w4c"), narrow = cfg_by_name("fast128x64x16w5c"), m192 = cfg_by_name("fast192x64x16w4c");
     static const int kCfgGemv16 = cfg_by_name("gemv16"), kCfgGemv4 = cfg_by_name("gemv4"), kCfgGemv16N1 = cfg_by_name("gemv16n1"), kCfgGemv4N1 = cfg_by_name("gemv4n1");
     static const int kCfgSmall = cfg_by_name("fast64x64x16w8c"), kCfgGen128 = cfg_by_name("128x128x16"), kCfgGen64 = cfg_by_name("128x64x16"), kCfgGen32 = cfg_by_name("128x32x16");
     const bool f16 = fast_eligible(p, 16);
@@ -165,23 +146,13 @@ int pick_cfg(const MitConvGemm &p, int64_t M) {
         //   N = 160, K = 640 (ConvNeXt stage-2 pw2): 1.36x of 3 x 64;   N = 320, K = 1280 (stage-3 pw2): 1.13x of 5 x 64;
         //   N = 80, K = 320 (stage-1 pw2): 1.08x of the 128-column tile;   N = 192, K = 384 (LaMa spectral conv1): 1.09x of 3 x 64.
         // The short-K expansions (pw1: K = 80 / 160 / 320 into N = 4K) are 5-10 % SLOWER on them and keep the tiles above.
-        static const bool exact_n_off = getenv("MIT_CONV_NO_EXACT_N") != nullptr;  // A/B knob
-        if (split == 6 && p.Z == 1 && !exact_n_off) {
+        if (split == 6 && p.Z == 1) {
             static const int t160 = cfg_by_name("split128x160x16p6o"), t96 = cfg_by_name("split128x96x16p6o"), t192 = cfg_by_name("split128x192x16p6o");
             const int K = p.ntaps * p.Cin;
             if (t160 >= 0 && (p.N == 160 || p.N == 320) && K >= 512) c = t160;
             else if (t96 >= 0 && p.N > 64 && p.N <= 96 && K >= 256) c = t96;
             else if (t192 >= 0 && p.N == 192 && K >= 256) c = t192;
         }
-        // Ping-pong tile (round 6; conv_gemm_split_pp.h: eight waves, one workgroup per CU, compute and load segments alternating on
-        // every SIMD): 1.12-1.15x of the 128 x 128 tile on long-K layers whose N is a multiple of 256 (LaMa's stride-2 and transposed
-        // convolutions at 256 / 512 channels, the detector's 2048 -> 256 layers), 0.8-1.0x on short K (an 8-32 step loop does not
-        // amortise a lone workgroup's prologue and 128 KB epilogue) — profiles/r10d_split_check_pp.log.  Same bits as every p6 tile.
-        // OPT-IN (MIT_CONV_PP=1): those layers are 7 % of a step's GEMM time, the step gains 0.6 % (inside the box-to-box noise,
-        // profiles/r10e_ab_pp_end_to_end.log), and they are the best launches of the tile the bench's roofline is priced on.
-        static const bool pp_on = getenv("MIT_CONV_PP") != nullptr && atoi(getenv("MIT_CONV_PP")) != 0;
-        static const int pp256 = cfg_by_name("split128x256x16p6pp");
-        if (split == 6 && p.Z == 1 && pp_on && pp256 >= 0 && p.N % 256 == 0 && p.ntaps * p.Cin >= 1024 && ((M + 127) / 128) * (p.N / 256) >= 512) c = pp256;
         // under-filled launches (one page through the plugins, the decoder's Linears): 64 x 64 tiles quadruple the workgroup count;
         // the arithmetic per output element is that of the large tiles, so a result does not depend on the choice
         const int sm = split == 6 ? small6 : small9;
@@ -197,7 +168,6 @@ int pick_cfg(const MitConvGemm &p, int64_t M) {
         if (c >= 0) return buf_eligible(p) ? buf_twin(c) : c;  // same arithmetic, operand loads through buffer instructions where offsets fit
     }
     if (f16 && m192 >= 0 && M > 128 && M <= 192 && p.Z >= 8) return m192;  // batched launches (Z entries of M = 184 rows: W-axis DFTs): 2 x 128 rows would run a 40 % empty second tile.  Unbatched, one row of 192 x 64 tiles leaves the chip empty (the decoder at B = 1: M = 160)
-    if (f16 && bigk >= 0 && p.N % 128 == 0 && p.N <= 128 && p.ntaps * p.Cin >= 4096 && M >= 256 * 1024) return bigk;
     // under-filled launches (the decoder's GEMMs: M = lines x beams = 10240): a 128-row tiling leaves most CUs with one workgroup or
     // none, 64 x 64 tiles double the count
     constexpr int64_t small_max = 1280;  // swept 640 .. 5120 on the OCR and detector stages (same-box A/B): 1280 = one full wave of workgroups

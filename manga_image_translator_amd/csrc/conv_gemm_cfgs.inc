@@ -6,7 +6,6 @@
 //   launcher : launch_cfg<BM,BN,BK,WAVES_M,WAVES_N>, launch_fast<BM,BN,BK,WAVES_M,WAVES_N,MINW,VAR> or
 //              launch_gemv<ROWS_PER_ITERATION,NMAX,KVEC,LANES_PER_ROW> (fast = 3; the BM/BN/BK columns hold its first three arguments)
 //              launch_split<BM,BN,BK,WAVES_M,WAVES_N,MINW,NPROD,VAR> (fast = 4: conv_gemm_split_kernel, needs MitConvGemm.w_split)
-//              launch_split_pp<same arguments> (fast = 4: conv_gemm_split_pp_kernel, 512 threads)
 // The table holds what pick_cfg() can return plus the reference forms the tests compare against.  The schedules that were measured and
 // rejected, and the timing ablations, were removed; DESIGN.md and profiles/ keep their measurements, git history (e7f35b0) their code.
 // ---- generic kernel (any Cin % 4 == 0, any number of taps, 64-bit offsets)
@@ -51,8 +50,6 @@ X(5, "split128x32x16p6u", 4, 128, 32, 16, launch_split, 4, 1, 4, 6, 2433)
 X(5, "split128x160x16p6u", 4, 128, 160, 16, launch_split, 4, 1, 2, 6, 2433)
 X(5, "split128x96x16p6u", 4, 128, 96, 16, launch_split, 4, 1, 3, 6, 2433)
 X(5, "split128x192x16p6u", 4, 128, 192, 16, launch_split, 4, 1, 2, 6, 2433)
-// ---- ping-pong split tiles (round 6): 512 threads, two waves per SIMD alternating compute and load segments (conv_gemm_split_pp.h)
-X(5, "split128x256x16p6pp", 4, 128, 256, 16, launch_split_pp, 2, 4, 2, 6, 0)   // wave tile 64 x 64, the A tile split once for 256 columns: long-K layers with N % 256 == 0 (pick_cfg, MIT_CONV_PP=1)
 // reference forms for the tests: the plain (unpipelined) schedule of the same arithmetic, and the 3-pair rung of the accuracy ladder
 X(3, "split128x128x16p6", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 0)
 X(3, "split128x128x16p9", 4, 128, 128, 16, launch_split, 2, 2, 2, 9, 0)

@@ -711,6 +711,7 @@ constexpr int ATT_THREADS = 256;
 // for launches that leave CUs idle (one page: 4 heads x 32 lines) — a line's keys in ONE chunk, so one load round trip per pass
 constexpr int ATT_KCHUNK = 64, ATT_STAGE = 8;
 constexpr int ATT_KCHUNK_L = 160, ATT_STAGE_L = 13;
+constexpr int64_t ATT_LATENCY_MAX_WGS = 512;  // launches of up to this many workgroups (heads x lines) take the latency form
 
 // chunk [nk keys x HD] of one head, global -> registers (coalesced: consecutive threads walk a key row)
 template <int STAGE>
@@ -1718,8 +1719,7 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
         const double bytes = 4.0 * heads * head_dim * ((double)(R / kv_div) * 2.0 * Tk + 2.0 * R), flops = 4.0 * (double)R * heads * Tk * head_dim;
         auto lds_bytes = [&](const int kchunk) { return ((size_t)kv_div * head_dim + (size_t)kchunk * (head_dim + 4) + (size_t)kv_div * Tk) * sizeof(float); };
         // few workgroups (one page .. a few): the latency form, a line's keys in one chunk; else the throughput form.  Same arithmetic.
-        static const int64_t lat_max = getenv("MIT_ATT_LATENCY_MAX_WGS") ? atoll(getenv("MIT_ATT_LATENCY_MAX_WGS")) : 512;
-        if ((int64_t)heads * (R / kv_div) <= lat_max && ATT_KCHUNK_L * (head_dim / 4) <= ATT_STAGE_L * ATT_THREADS && lds_bytes(ATT_KCHUNK_L) <= 64 * 1024) {
+        if ((int64_t)heads * (R / kv_div) <= ATT_LATENCY_MAX_WGS && ATT_KCHUNK_L * (head_dim / 4) <= ATT_STAGE_L * ATT_THREADS && lds_bytes(ATT_KCHUNK_L) <= 64 * 1024) {
             MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops);
             hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK_L, ATT_STAGE_L, 80, 5>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes(ATT_KCHUNK_L), s, Q, q_rs,
                                K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, dstep, xp, opl, OcrAttQProj{});
@@ -1732,22 +1732,14 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
             return;
         }
     }
-    static const bool no_rows = getenv("MIT_ATT_NO_ROWS") != nullptr;
-    if (!no_rows && !dstep && !xp.cos_t && !opl.p && kv_div == 1 && Tq >= 2 * ATTR_GQ && R <= 65535 && Tq <= 65535 * 32 && head_dim <= 128 && ((q_rs | q_ts | k_rs | k_ts | v_rs | v_ts) & 3) == 0) {
+    if (!dstep && !xp.cos_t && !opl.p && kv_div == 1 && Tq >= 2 * ATTR_GQ && R <= 65535 && Tq <= 65535 * 32 && head_dim <= 128 && ((q_rs | q_ts | k_rs | k_ts | v_rs | v_ts) & 3) == 0) {
         const size_t sm = ((size_t)Tk * (head_dim + 4) + (size_t)(ATTR_THREADS / 64) * ATTR_GQ * (head_dim + Tk)) * sizeof(float);
         if (sm <= 150 * 1024 && head_dim % 8 == 0) {
             // algorithmic bytes: q, k, v read once and o written once per row; FLOPs 4 Tk d per query and head
             MitProbeScope probe("attention_rows_kernel", s, 4.0 * (double)R * heads * head_dim * (2.0 * Tq + 2.0 * Tk),
                                 4.0 * (double)R * Tq * heads * Tk * head_dim);
-            static size_t granted[16] = {0};
-            if (sm > 64 * 1024) {
-                int dev = 0;
-                (void)hipGetDevice(&dev);
-                if (granted[dev & 15] < sm) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(attention_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-                    granted[dev & 15] = sm;
-                }
-            }
+            static DynSmemOptIn optin;
+            optin.ensure(reinterpret_cast<const void *>(attention_rows_kernel), sm);
             hipLaunchKernelGGL(attention_rows_kernel, dim3(heads, R, (Tq + (ATTR_THREADS / 64) * ATTR_GQ - 1) / ((ATTR_THREADS / 64) * ATTR_GQ)), dim3(ATTR_THREADS), sm, s, Q, q_rs, q_ts, K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs,
                                o_ts, klen, Tq, Tk, head_dim);
             return;
@@ -1782,9 +1774,8 @@ bool ocrk_cross_attention_qproj(const OcrAttQProj &qp, const float *K, int64_t k
     if ((reinterpret_cast<uintptr_t>(qp.x) | reinterpret_cast<uintptr_t>(qp.w_planes) | reinterpret_cast<uintptr_t>(qp.ln_w) | reinterpret_cast<uintptr_t>(qp.ln_b)) & 15) return false;
     if ((uint64_t)3 * (mitln::LN_K / 8) * (uint64_t)qp.ldw * 16u >= (1ull << 32)) return false;
     if (R % kv_div || R / kv_div > 65535) return false;
-    static const int64_t lat_max = getenv("MIT_ATT_LATENCY_MAX_WGS") ? atoll(getenv("MIT_ATT_LATENCY_MAX_WGS")) : 512;
     const size_t lds_bytes = ((size_t)kv_div * head_dim + (size_t)ATT_KCHUNK_L * (head_dim + 4) + (size_t)kv_div * Tk) * sizeof(float);
-    if ((int64_t)heads * (R / kv_div) > lat_max || lds_bytes > 64 * 1024) return false;
+    if ((int64_t)heads * (R / kv_div) > ATT_LATENCY_MAX_WGS || lds_bytes > 64 * 1024) return false;
     const double bytes = 4.0 * heads * head_dim * ((double)(R / kv_div) * 2.0 * Tk + 2.0 * R), flops = 4.0 * (double)R * heads * Tk * head_dim;
     MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops + 2.0 * R * 320.0 * 320.0);
     hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK_L, ATT_STAGE_L, 80, 5, true>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes, s, nullptr, 0,
@@ -1887,10 +1878,9 @@ extern "C" int mit_dwconv_nhwc_ragged(const float *in_dev, const float *w_dev, c
 extern "C" int mit_dwconv_nhwc_ragged_rows(const float *in_dev, const float *w_dev, const float *scale_dev, const float *bias_dev,
                                            float *out_dev, const MitRaggedSeg *segs_dev, int nsegs, int64_t total_groups, int C, int k,
                                            int common_H, void *stream) {
-    static const bool off = getenv("MIT_DWCONV_NO_ROWS") != nullptr;  // A/B knob for scripts/
     const int yt = (common_H > 0 && common_H % 4 == 0) ? 4 : (common_H > 0 && common_H % 2 == 0) ? 2 : 0;
     const size_t smem = (size_t)k * k * C * sizeof(float);
-    if (off || yt == 0 || smem > 64 * 1024 || (k != 3 && k != 5 && k != 7))
+    if (yt == 0 || smem > 64 * 1024 || (k != 3 && k != 5 && k != 7))
         return mit_dwconv_nhwc_ragged(in_dev, w_dev, scale_dev, bias_dev, out_dev, segs_dev, nsegs, total_groups, C, k, stream);
     if (!in_dev || !w_dev || !scale_dev || !bias_dev || !out_dev || !segs_dev) return mit_set_error("mit_dwconv_nhwc_ragged_rows: null pointer");
     if ((C & 3) || nsegs <= 0 || total_groups < 0 || total_groups % yt) return mit_set_error("mit_dwconv_nhwc_ragged_rows: bad arguments");

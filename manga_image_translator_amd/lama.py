@@ -19,7 +19,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -258,10 +257,9 @@ class LamaEngine:
                 t2[bits] = acc * a6
             self.mpe["lut1"], self.mpe["lut2"] = (emb * a5).contiguous().to(dev), t2.contiguous().to(dev)
         # layout between the last up-convolution and the 7x7 output convolution: 4 = sixteen 4-channel planes (the output convolution's
-        # LDS-DMA kernel, round 6), 16 (or 1) = four 16-channel planes (its register-staged kernel, round 5), 0 = NHWC — same values
-        pt = os.environ.get("MIT_LAMA_PLANAR_TAIL", "4")
-        self.planar_tail = {"": 0, "0": 0, "1": 16, "16": 16, "4": 4}.get(pt, 4)
-        self.mpe_in_stem = os.environ.get("MIT_LAMA_MPE_SEPARATE", "") in ("", "0")   # False: the separate mit_lama_mpe_add pass (A/B, tests)
+        # LDS-DMA kernel, round 6), 16 = four 16-channel planes (its register-staged kernel, round 5), 0 = NHWC — same values
+        self.planar_tail = 4
+        self.mpe_in_stem = True   # False: the separate mit_lama_mpe_add pass (tests)
         self._ws = ops.Workspace(self.device)
         self._tw: Dict[int, torch.Tensor] = {}
         self._tw_rows: Dict[int, torch.Tensor] = {}
@@ -475,7 +473,7 @@ class LamaEngine:
             _lib.check(lib.mit_lama_prep(img_u8.data_ptr(), mask_u8.data_ptr(), x4.data_ptr(), B, H, W, st), "mit_lama_prep")
             self.stem(x4, out=s64)
         if self.mpe is not None:
-            if lut is None:   # the separate pass (MIT_LAMA_MPE_SEPARATE=1, or the unpacked stem): bit-identical to the epilogue form
+            if lut is None:   # the separate pass (mpe_in_stem = False, or the unpacked stem): bit-identical to the epilogue form
                 _lib.check(lib.mit_lama_mpe_add(s64.data_ptr(), mask_u8.data_ptr(), rel.data_ptr(), dr.data_ptr(),
                                                 tb["ymap"].data_ptr(), tb["xmap"].data_ptr(), self.mpe["emb"].data_ptr(),
                                                 self.mpe["dirw"].data_ptr(), self.mpe["alpha5"], self.mpe["alpha6"], B, H, W,
@@ -510,7 +508,7 @@ class LamaEngine:
             u3 = self._buf("full64", 64 // P, B, H, W, P)
             self.ups[2](u2, out=u3, planes=64 // P, parity_major=pm)
             self.out_conv(u3, out=pred, parity_major=pm)
-        else:                  # MIT_LAMA_PLANAR_TAIL=0: NHWC between the two (A/B, tests) — same values, other addresses
+        else:                  # planar_tail = 0: NHWC between the two (tests) — same values, other addresses
             u3 = self._buf("full64", B, H, W, 64)
             self.ups[2](u2, out=u3)
             self.out_conv(u3, out=pred)

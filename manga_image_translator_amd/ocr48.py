@@ -16,7 +16,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -165,7 +164,7 @@ class _Block:
         self.pw2(h4, out=x4, post=x4)
 
 
-_FUSED_MLP = [os.environ.get("MIT_OCR_FUSED_MLP", "1") not in ("", "0")]
+_FUSED_MLP = [True]
 
 
 def fused_mlp_enabled() -> bool:
@@ -173,8 +172,8 @@ def fused_mlp_enabled() -> bool:
 
 
 def set_fused_mlp(on: bool) -> bool:
-    """Switch the one-launch ConvNeXt pointwise pair (tests, A/B); returns the previous setting.  MIT_OCR_FUSED_MLP=0 in the environment
-    starts with it off."""
+    """Switch the one-launch ConvNeXt pointwise pair (on by default; tests compare it with the two launches); returns the previous
+    setting."""
     prev, _FUSED_MLP[0] = _FUSED_MLP[0], bool(on)
     return prev
 
@@ -516,7 +515,7 @@ class Ocr48Engine:
 
     @torch.no_grad()
     def decode(self, mem_k: torch.Tensor, mem_v: torch.Tensor, mem_len: torch.Tensor, max_seq_length: int = 255,
-               suppress_eos: bool = False, trace: bool = False, graph: Optional[bool] = None):
+               suppress_eos: bool = False, trace: bool = False, graph: bool = False):
         """Beam search (:691-801) over N lines at once. mem_k/mem_v [5,N,L,320], mem_len [N] int32.
 
         Returns a dict of device tensors: tokens [N,T+1] int32, length [N], prob [N], colors [N,T,10]
@@ -537,7 +536,7 @@ class Ocr48Engine:
         a.mem_k, a.mem_v, a.mem_len = mem_k.contiguous().data_ptr(), mem_v.contiguous().data_ptr(), mem_len.data_ptr()
         a.max_seq_length, a.start_tok, a.end_tok, a.max_finished, a.suppress_eos = T, 1, 2, 2, int(suppress_eos)
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-        a.graph_mode = 0 if graph is None else (1 if graph else 2)   # None: off unless MIT_OCR_DECODE_GRAPH=1 (hipGraph replay of the steps: no gain measured)
+        a.graph_mode = 1 if graph else 0   # hipGraph replay of the steps: off by default (no gain measured)
         a.res_tok, a.res_len, a.res_prob, a.res_row, a.colors = (t.data_ptr() for t in (res_tok, res_len, res_prob, res_row, colors))
         out = {}
         if trace:

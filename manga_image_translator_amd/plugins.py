@@ -206,8 +206,8 @@ class HipComicTextDetector(_DetBase):
             mask_full = imgproc.resize_u8(mask_u8[:1].contiguous(), (im_w, im_h))[0]
         # SegDetectorRepresenter(thresh=0.3) (:102,156): on the GPU where the map already is (csrc/ctd_boxes.hip: only the boxes cross
         # PCIe); an injected extractor, or a rearranged strip whose stitched map was assembled on the host, takes the numpy map
-        if self._boxes is None and lines_map is None and lines.is_cuda and not os.environ.get("MIT_BOXES_HOST"):   # (MIT_BOXES_HOST=1: the host routine, A/B;
-            # a map that lives on the host — an injected stand-in engine, tests/boundary_checks.py — goes to the host routine as well)
+        if self._boxes is None and lines_map is None and lines.is_cuda:   # (a map that lives on the host — an injected stand-in engine,
+            # tests/boundary_checks.py — goes to the host routine as well)
             boxes, scores = hostglue.ctd_boxes_gpu(lines, im_h, im_w)[0]
         else:
             boxes_fn = self._boxes or _native_ctd_boxes
@@ -301,7 +301,7 @@ class HipDefaultDetector(_DetBase):
             ratio = 1 / target_ratio
             h, w = int(page.shape[1]), int(page.shape[2])
             db, mask = self.engine.forward(page)
-            if self._boxes is None and db.is_cuda and not os.environ.get("MIT_BOXES_HOST"):   # SegDetectorRepresenter (:73-77) where the map is: csrc/ctd_boxes.hip
+            if self._boxes is None and db.is_cuda:   # SegDetectorRepresenter (:73-77) where the map is: csrc/ctd_boxes.hip
                 from . import hostglue
 
                 boxes_fn = lambda d, hh, ww, tt, bt, ur: hostglue.dbnet_boxes_gpu(d, hh, ww, tt, bt, ur)[0]   # noqa: E731
@@ -780,7 +780,7 @@ class HipMangaColorizer(_ColBase):
         return Image.fromarray(out[0].cpu().numpy())
 
 
-# ---- pieces taken from the reference package when it is importable ---------------------------------------------
+# ---- host / device helpers of the detector plugins ---------------------------------------------------------------
 
 def _native_ctd_boxes(lines_map, im_h, im_w):
     """SegDetectorRepresenter(thresh=0.3)(None, lines_map, height, width) on the native host routines (hostglue.py)."""
@@ -789,44 +789,10 @@ def _native_ctd_boxes(lines_map, im_h, im_w):
     return hostglue.ctd_boxes(lines_map, im_h, im_w)
 
 
-def _native_refine(image, mask, textlines, im_h, im_w):
-    """cv2.resize(mask, (w, h), INTER_LINEAR) + refine_mask(image, mask, textlines, refine_mode=None) (ctd.py:162,177)."""
-    from . import hostglue
-
-    return hostglue.refine_mask(image, hostglue.resize_linear_u8(mask, (im_w, im_h)), textlines, None)
-
-
 def _native_dbnet_boxes(db, h, w, text_threshold, box_threshold, unclip_ratio):
     from . import hostglue
 
     return hostglue.dbnet_boxes(db, h, w, text_threshold, box_threshold, unclip_ratio)
-
-
-def _reference_boxes():
-    if not HAVE_REFERENCE:
-        raise RuntimeError("box extraction needs the reference's SegDetectorRepresenter (OpenCV/pyclipper); pass boxes_from_maps=")
-    from manga_translator.detection.ctd_utils.utils.db_utils import SegDetectorRepresenter  # type: ignore
-
-    rep = SegDetectorRepresenter(thresh=0.3)
-
-    def fn(lines_map, im_h, im_w):
-        lines, scores = rep(None, lines_map, height=im_h, width=im_w)
-        return lines[0], scores[0]
-
-    return fn
-
-
-def _reference_refine():
-    if not HAVE_REFERENCE:
-        raise RuntimeError("mask refinement needs the reference's refine_mask (OpenCV); pass refine=")
-    import cv2  # type: ignore
-    from manga_translator.detection.ctd_utils.textmask import refine_mask  # type: ignore
-
-    def fn(image, mask, textlines, im_h, im_w):
-        mask = cv2.resize(mask, (im_w, im_h), interpolation=cv2.INTER_LINEAR)
-        return refine_mask(image, mask, textlines, refine_mode=None)
-
-    return fn
 
 
 def default_preprocess_gpu(image: torch.Tensor, detect_size: int):
@@ -849,33 +815,6 @@ def default_preprocess_gpu(image: torch.Tensor, detect_size: int):
     return proc, ratio, pad_w, pad_h
 
 
-def _reference_default_preprocess():
-    if not HAVE_REFERENCE:
-        raise RuntimeError("the default detector's bilateral filter + resize need OpenCV; pass preprocess=")
-    import cv2  # type: ignore
-    from manga_translator.detection.default_utils import imgproc  # type: ignore
-
-    def fn(image, detect_size):
-        img, ratio, _, pad_w, pad_h = imgproc.resize_aspect_ratio(cv2.bilateralFilter(image, 17, 80, 80), detect_size,
-                                                                  cv2.INTER_LINEAR, mag_ratio=1)
-        return img, ratio, pad_w, pad_h
-
-    return fn
-
-
-def _reference_default_boxes():
-    if not HAVE_REFERENCE:
-        raise RuntimeError("box extraction needs the reference's dbnet_utils.SegDetectorRepresenter; pass boxes_from_maps=")
-    from manga_translator.detection.default_utils import dbnet_utils  # type: ignore
-
-    def fn(db, h, w, text_threshold, box_threshold, unclip_ratio):
-        det = dbnet_utils.SegDetectorRepresenter(text_threshold, box_threshold, unclip_ratio=unclip_ratio)
-        boxes, scores = det({"shape": [(h, w)]}, db)
-        return boxes[0], scores[0]
-
-    return fn
-
-
 def _resize2x_f32(m: np.ndarray) -> np.ndarray:
     """cv2.resize(mask, (2w, 2h), INTER_LINEAR) on a float32 map (default.py:89): plain bilinear at pixel centres with edge
     replication — float data takes OpenCV's unquantised path (coefficients 1 - f, f in float32)."""
@@ -895,28 +834,6 @@ def _resize2x_f32(m: np.ndarray) -> np.ndarray:
     m = m.astype(np.float32)
     rows = m[:, x0] * wx0[None, :] + m[:, x1] * wx1[None, :]
     return (rows[y0] * wy0[:, None] + rows[y1] * wy1[:, None]).astype(np.float32)
-
-
-def _reference_resize2x():
-    if not HAVE_REFERENCE:
-        raise RuntimeError("the x2 mask resize needs OpenCV; pass resize2x=")
-    import cv2  # type: ignore
-
-    return lambda m: cv2.resize(m, (m.shape[1] * 2, m.shape[0] * 2), interpolation=cv2.INTER_LINEAR)
-
-
-def _reference_resize():
-    if not HAVE_REFERENCE:
-        raise RuntimeError("pages that need resizing (max side > inpainting_size or not a multiple of 8) need OpenCV; pass resize=")
-    import cv2  # type: ignore
-    from manga_translator.utils import resize_keep_aspect  # type: ignore
-
-    def fn(img, dsize, mode):
-        if mode == "keep_aspect":
-            return resize_keep_aspect(img, max(dsize))
-        return cv2.resize(img, dsize, interpolation=cv2.INTER_LINEAR)
-
-    return fn
 
 
 def _ckpt_path(plugin, name: str) -> str:

@@ -1,6 +1,6 @@
 """Is the two-stream mode of PageEngine (LaMa on the caller's stream, detector + OCR beside it) bit-identical to the one-stream mode?
 
-usage: [MIT_COTENANT_SAFE=0|1] python scripts/dev/overlap_check.py [pages] [repeats]
+usage: python scripts/dev/overlap_check.py [pages] [repeats]
 Prints, per repeat, how many result elements of each stage differ from the one-stream run of the same engine."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
@@ -33,4 +33,4 @@ for i in range(reps):
     extra = ""
     if d["prob"]:
         extra = " max |dprob| %.3g" % float((ref["prob"] - got["prob"]).abs().max())
-    print(f"two-stream run {i} (MIT_COTENANT_SAFE={os.environ.get('MIT_COTENANT_SAFE', '0')}):", d, extra)
+    print(f"two-stream run {i}:", d, extra)

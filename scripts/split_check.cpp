@@ -44,31 +44,25 @@ int main(int argc, char **argv) {
     const int reps = argc > 1 ? atoi(argv[1]) : 10;
     const int f_wide = find_cfg("fast128x128x16w4c"), f_narrow = find_cfg("fast128x64x16w5c");
     const int s6 = find_cfg("split128x128x16p6"), s9 = find_cfg("split128x128x16p9"), s3 = find_cfg("split128x128x16p3");
-    const int n6 = find_cfg("split128x64x16p6"), n9 = find_cfg("split128x64x16p9"), s6k32 = find_cfg("split128x128x32p6");
-    const int s6s = find_cfg("split128x128x16p6s"), s9s = find_cfg("split128x128x16p9s"), n6s = find_cfg("split128x64x16p6s"), s6k32s = find_cfg("split128x128x32p6s");
-    const int s6m = find_cfg("split128x128x16p6m"), s9m = find_cfg("split128x128x16p9m"), n6m = find_cfg("split128x64x16p6m"), s6k32m = find_cfg("split128x128x32p6m");
+    const int n6 = find_cfg("split128x64x16p6"), n9 = find_cfg("split128x64x16p9"), s9m = find_cfg("split128x128x16p9m");
     const int s6o = find_cfg("split128x128x16p6o"), n6o = find_cfg("split128x64x16p6o");
-    if (s6o < 0 || n6o < 0) return 2;  // (names of removed experiment tiles come back as -1 and are skipped below)
-    const int s64 = find_cfg("split64x64x16p6o"), s32 = find_cfg("split128x32x16p6o"), f32t = find_cfg("fast128x32x16w4c");  // small / narrow tiles (-1: skipped)
-    const int w6o = find_cfg("split64x256x16p6o");
-    const int t192 = find_cfg("split128x192x16p6o"), t256 = find_cfg("split256x64x16p6o");
-    const int t160 = find_cfg("split128x160x16p6o"), t96 = find_cfg("split128x96x16p6o");  // exact-N tiles for N = 160 k / N = 80  // wide-N tile (-1 in builds without it: skipped)
-    const int pp = find_cfg("split256x128x16p6pp"), pq = find_cfg("split128x256x16p6pp");
+    if (s6o < 0 || n6o < 0) return 2;
+    const int s64 = find_cfg("split64x64x16p6o"), s32 = find_cfg("split128x32x16p6o"), f32t = find_cfg("fast128x32x16w4c");  // small / narrow tiles
+    const int t160 = find_cfg("split128x160x16p6o"), t96 = find_cfg("split128x96x16p6o"), t192 = find_cfg("split128x192x16p6o");  // exact-N tiles
     const int bd = find_cfg("split128x128x16p6u");  // round 6: operand loads through buffer instructions
-    const int bv = find_cfg("split128x128x16p6v");  // ... + two K-tiles per loop trip with constant LDS buffer parity  // round 6: the eight-wave ping-pong tiles
     const int gen32 = find_cfg("128x32x16"), f64 = find_cfg("fast64x64x16w8c"), s64k = find_cfg("split64x64x32p6o");
     if (f_wide < 0 || f_narrow < 0 || s6 < 0 || s9 < 0 || s3 < 0 || n6 < 0 || n9 < 0 || s9m < 0) {
         fprintf(stderr, "tile names not found\n");
         return 2;
     }
     std::vector<Case> cases = {
-        {"probe: A[m][k] = (k == m % 16), W[k][n] = 1000 k + n", 1, 1, 256, 16, 128, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6, s9, s3, n6, s6s, n6s, s6m, n6m, s6o, n6o, s64}},
-        {"1x1 320->1280 (ConvNeXt pw1), M=65536, gelu", 1, 256, 256, 320, 1280, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6, s9, s3, s6s, s6m, s9m, s6k32m, s6o, w6o, s6o, w6o, s6o}},
-        {"3x3 reflect 128->128, 2x96x160, relu", 2, 96, 160, 128, 128, 3, 1, MIT_PAD_REFLECT, 1, MIT_ACT_RELU, f_wide, {s6, s9, s6s, s6m, s9m, s6k32m, s6o, s6m, s6o, s6m, s6o}},
-        {"winograd-like Z=36, T=8192, 128->384", 1, 1, 8192, 128, 384, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6, s9, s6m, s9m, s6o, n6o, w6o, s6o, n6o, w6o}},
-        {"1x1 192->384 (spectral conv2), M=131072, relu", 1, 256, 512, 192, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, n6o, w6o, s6o, n6o, w6o}},
-        {"1x1 160->640 (ConvNeXt stage 2 pw1), M=131072, gelu", 1, 256, 512, 160, 640, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6o, n6o, w6o, s6o, n6o, w6o}},
-        {"1x1 80->320 (ConvNeXt stage 1 pw1), M=262144, gelu", 1, 512, 512, 80, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6o, n6o, w6o, s6o, n6o, w6o}},
+        {"probe: A[m][k] = (k == m % 16), W[k][n] = 1000 k + n", 1, 1, 256, 16, 128, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6, s9, s3, n6, s6o, n6o, s64}},
+        {"1x1 320->1280 (ConvNeXt pw1), M=65536, gelu", 1, 256, 256, 320, 1280, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6, s9, s3, s9m, s6o, s6o, s6o}},
+        {"3x3 reflect 128->128, 2x96x160, relu", 2, 96, 160, 128, 128, 3, 1, MIT_PAD_REFLECT, 1, MIT_ACT_RELU, f_wide, {s6, s9, s9m, s6o, s6o, s6o}},
+        {"winograd-like Z=36, T=8192, 128->384", 1, 1, 8192, 128, 384, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6, s9, s9m, s6o, n6o, s6o, n6o}},
+        {"1x1 192->384 (spectral conv2), M=131072, relu", 1, 256, 512, 192, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, n6o, s6o, n6o}},
+        {"1x1 160->640 (ConvNeXt stage 2 pw1), M=131072, gelu", 1, 256, 512, 160, 640, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6o, n6o, s6o, n6o}},
+        {"1x1 80->320 (ConvNeXt stage 1 pw1), M=262144, gelu", 1, 512, 512, 80, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6o, n6o, s6o, n6o}},
         {"1x1 640->160 (ConvNeXt stage 2 pw2), M=131072", 1, 256, 512, 640, 160, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6o, n6o, t160, s6o, n6o, t160}},
         {"1x1 320->80 (ConvNeXt stage 1 pw2), M=262144", 1, 512, 512, 320, 80, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6o, n6o, t96, s6o, n6o, t96}},
         {"1x1 1280->320 (pw2), M=131072", 1, 256, 512, 1280, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6o, n6o, t160, n6o, t160}},
@@ -79,17 +73,17 @@ int main(int argc, char **argv) {
         {"1x1 192->384 (spectral conv2), M=262144, relu", 1, 512, 512, 192, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, t192, s6o, t192}},
         {"winograd-like Z=36, T=16384, 128->384", 1, 1, 16384, 128, 384, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6o, t192, s6o, t192}},
         {"1x1 2 taps-like: 768->384, M=131072", 1, 256, 512, 768, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, t192, s6o, t192}},
-        {"1x1 224->64 (stem-like K), M=1048576, relu", 1, 1024, 1024, 224, 64, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_narrow, {n6o, t256, n6o, t256}},
-        {"1x1 256->64 (convT parity-like), M=1048576, relu", 1, 1024, 1024, 256, 64, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_narrow, {n6o, t256, n6o, t256}},
-        {"1x1 512->64, M=1048576, relu", 1, 1024, 1024, 512, 64, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_narrow, {n6o, t256, n6o, t256}},
-        {"3x3 zero 64->64, 2x512x512, leaky", 2, 512, 512, 64, 64, 3, 1, MIT_PAD_ZERO, 1, MIT_ACT_LEAKY, f_narrow, {n6o, t256, n6o, t256}},
-        {"1x1 80->320 (pw1) again, M=524288, gelu", 1, 1024, 512, 80, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {n6o, t256, n6o, t256}},
+        {"1x1 224->64 (stem-like K), M=1048576, relu", 1, 1024, 1024, 224, 64, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_narrow, {n6o, n6o}},
+        {"1x1 256->64 (convT parity-like), M=1048576, relu", 1, 1024, 1024, 256, 64, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_narrow, {n6o, n6o}},
+        {"1x1 512->64, M=1048576, relu", 1, 1024, 1024, 512, 64, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_narrow, {n6o, n6o}},
+        {"3x3 zero 64->64, 2x512x512, leaky", 2, 512, 512, 64, 64, 3, 1, MIT_PAD_ZERO, 1, MIT_ACT_LEAKY, f_narrow, {n6o, n6o}},
+        {"1x1 80->320 (pw1) again, M=524288, gelu", 1, 1024, 512, 80, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {n6o, n6o}},
         {"decoder-like M=10240: 320->960 exact-N", 1, 1, 10240, 320, 960, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {n6o, t160, n6o, t160}},
         {"encoder-like M=60208: 320->960 exact-N", 1, 1, 60208, 320, 960, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {n6o, t160, n6o, t160}},
-        {"3x3 s2 zero 128->256 (LaMa down), 2x128x96", 2, 256, 192, 128, 256, 3, 2, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, w6o, s6o, w6o}},
-        {"1x1 384x2taps-like: 768->384, M=65536", 1, 256, 256, 768, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, w6o, s6o, w6o}},
-        {"3x3 s2 zero 64->64, 4x128x128", 4, 128, 128, 64, 64, 3, 2, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_narrow, {n6, n9, n6s, n6m, n6o, n6m, n6o}},
-        {"1x1 1280->320 (pw2), M=65536", 1, 256, 256, 1280, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6, s9, n6, s6m, n6m, s6k32m, s6o, n6o, s6m, s6o}},
+        {"3x3 s2 zero 128->256 (LaMa down), 2x128x96", 2, 256, 192, 128, 256, 3, 2, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, s6o}},
+        {"1x1 384x2taps-like: 768->384, M=65536", 1, 256, 256, 768, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, s6o}},
+        {"3x3 s2 zero 64->64, 4x128x128", 4, 128, 128, 64, 64, 3, 2, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_narrow, {n6, n9, n6o, n6o}},
+        {"1x1 1280->320 (pw2), M=65536", 1, 256, 256, 1280, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6, s9, n6, s6o, n6o, s6o}},
         {"3x3 zero 128->32 (ESRGAN dense conv3), 2x256x256, leaky", 2, 256, 256, 128, 32, 3, 1, MIT_PAD_ZERO, 1, MIT_ACT_LEAKY, gen32, {f32t, s32, n6o}},
         {"decoder-like M=160: 320->960", 1, 1, 160, 320, 960, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {f64, s6o, n6o, s64, s64k, s64, s64k}},
         {"decoder-like M=160: 320->320", 1, 1, 160, 320, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {f64, s64, s64k, s64, s64k}},
@@ -99,24 +93,23 @@ int main(int argc, char **argv) {
         {"decoder-like M=10240: 320->960", 1, 1, 10240, 320, 960, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6o, n6o, s64, s64k, s64, s64k}},
         {"decoder-like M=10240: 2048->320", 1, 1, 10240, 2048, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s64, s64k, s64, s64k}},
         {"detector-like 3x3 256->256, 1x32x32", 1, 32, 32, 256, 256, 3, 1, MIT_PAD_ZERO, 1, MIT_ACT_LEAKY, f_wide, {s64, s64k, s64, s64k}},
-        {"ragged: M=1000, 48->200 3x3 zero", 1, 25, 40, 48, 200, 3, 1, MIT_PAD_ZERO, 1, MIT_ACT_LEAKY, f_wide, {s6, n6, n9, s6m, n6m, s6o, n6o, pp, pq}},
-        // round 6: the five shapes of the ping-pong experiment, each against the shipped 128 x 128 tile, twice
-        {"pp: long K 1x1 2304->512, M=46592, relu", 1, 182, 256, 2304, 512, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, pp, pq, s6o, pp, pq}},
-        {"pp: 3x3 s2 zero 256->512 (LaMa down3), 4x91x128", 4, 182, 256, 256, 512, 3, 2, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, pp, pq, s6o, pp, pq}},
-        {"pp: winograd Z=36, T=11776, 512->128", 1, 1, 11776, 512, 128, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6o, pp, s6o, pp}},
-        {"pp: winograd Z=36, T=11776, 128->384", 1, 1, 11776, 128, 384, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6o, pp, pq, s6o, pp, pq}},
-        {"pp: spectral 1x1 192->384, M=186368, relu", 1, 364, 512, 192, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, t192, pp, pq, s6o, t192, pp, pq}},
-        {"pp: pw1 1x1 320->1280, M=131072, gelu", 1, 256, 512, 320, 1280, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6o, pp, pq, s6o, pp, pq}},
-        {"pp: pw2 1x1 1280->320, M=131072", 1, 256, 512, 1280, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6o, t160, pp, pq, s6o, t160, pp, pq}},
-        {"pp: 3x3 reflect 128->128, 2x96x160, relu", 2, 96, 160, 128, 128, 3, 1, MIT_PAD_REFLECT, 1, MIT_ACT_RELU, f_wide, {s6o, pp, s6o, pp}},
+        {"ragged: M=1000, 48->200 3x3 zero", 1, 25, 40, 48, 200, 3, 1, MIT_PAD_ZERO, 1, MIT_ACT_LEAKY, f_wide, {s6, n6, n9, s6o, n6o}},
+        // round 6: the shapes of the ping-pong experiment (the tile itself was removed) — the shipped
+        // 128 x 128 tile and its buffer-load twin (below)
+        {"pp: long K 1x1 2304->512, M=46592, relu", 1, 182, 256, 2304, 512, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, s6o}},
+        {"pp: 3x3 s2 zero 256->512 (LaMa down3), 4x91x128", 4, 182, 256, 256, 512, 3, 2, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, s6o}},
+        {"pp: winograd Z=36, T=11776, 512->128", 1, 1, 11776, 512, 128, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6o, s6o}},
+        {"pp: winograd Z=36, T=11776, 128->384", 1, 1, 11776, 128, 384, 1, 1, MIT_PAD_ZERO, 36, MIT_ACT_NONE, f_wide, {s6o, s6o}},
+        {"pp: spectral 1x1 192->384, M=186368, relu", 1, 364, 512, 192, 384, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_RELU, f_wide, {s6o, t192, s6o, t192}},
+        {"pp: pw1 1x1 320->1280, M=131072, gelu", 1, 256, 512, 320, 1280, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_GELU, f_wide, {s6o, s6o}},
+        {"pp: pw2 1x1 1280->320, M=131072", 1, 256, 512, 1280, 320, 1, 1, MIT_PAD_ZERO, 1, MIT_ACT_NONE, f_wide, {s6o, t160, s6o, t160}},
+        {"pp: 3x3 reflect 128->128, 2x96x160, relu", 2, 96, 160, 128, 128, 3, 1, MIT_PAD_REFLECT, 1, MIT_ACT_RELU, f_wide, {s6o, s6o}},
     };
-    for (auto &c : cases)   // the direct-W tile wherever the shipped wide tile is measured
+    for (auto &c : cases)   // the buffer-load twin wherever the shipped wide tile is measured
         if (!strncmp(c.name, "pp:", 3) || !strncmp(c.name, "ragged", 6) || !strncmp(c.name, "probe", 5)) {
             c.cfgs.push_back(bd);
-            c.cfgs.push_back(bv);
             c.cfgs.push_back(s6o);
             c.cfgs.push_back(bd);
-            c.cfgs.push_back(bv);
         }
     if (const char *only = getenv("SC_CASE")) {  // substring filter on the case name
         std::vector<Case> keep;

@@ -5,9 +5,7 @@ split-bf16 GEMM tile; round 4 found the cause in the victims' own instructions: 
 arithmetic into v_pk_mul_f32 / v_pk_add_f32 with op_sel / neg modifiers, and on gfx950 such an instruction now and then returns a wrong
 16-lane pass while another kernel's MFMA waves share the CU (xpos_rotate_kernel: the second product of x.x * c + (-x.y) * s missing in 16
 consecutive lanes).  The library is built with -fno-slp-vectorize since; these tests keep the hazard visible:
-  * the FFT rows kernels must be bit-reproducible while a child process hammers the device with that GEMM tile, in the default launch
-    form and in the co-tenant-safe one (MIT_COTENANT_SAFE: narrow LDS reads + a whole CU's LDS — the mitigation that shipped before
-    the cause was known, kept as a switch);
+  * the FFT rows kernels must be bit-reproducible while a child process hammers the device with that GEMM tile;
   * the page engine with its stages on two streams must give the bytes of the one-stream run.
 (The engine-level two-process form — two ranks running whole page engines on one GPU at the same time — is tests/test_dist_gpu.py.)"""
 import os
@@ -84,7 +82,7 @@ def _count_disturbed(launches=60):
     from manga_image_translator_amd.lama import rfft_row_tables
 
     results = {}
-    for w in (24, 182):     # the size of scripts/cotenant_check (radix 4, 3) and the BASELINE page's W / 8 (radix 7, 13)
+    for w in (24, 182):     # a small row (radix 4, 3) and the BASELINE page's W / 8 (radix 7, 13)
         B, h, C_ = 2, 64, 192
         g = torch.Generator().manual_seed(w)
         x = torch.randn(B, h, w, C_, generator=g).cuda()
@@ -102,34 +100,17 @@ def _count_disturbed(launches=60):
     return bad
 
 
-def test_fft_rows_are_bit_stable_beside_a_looping_split_tile_process_in_safe_mode(cuda):
-    from manga_image_translator_amd import lib
-
-    prev = lib.load().mit_cotenant_safe_set(1)
-    try:
-        bad = _count_disturbed()
-    finally:
-        lib.load().mit_cotenant_safe_set(prev)
-    assert bad == {24: 0, 182: 0}, f"launches that differ from the quiet run, per row length: {bad}"
-
-
 def test_fft_rows_are_bit_stable_beside_a_looping_split_tile_process_default_mode(cuda):
     """The default launches (wide LDS reads, CUs shared with whatever else is resident): 55-58 of 60 launches were disturbed at both row
     lengths while the library was built with the SLP vectoriser; none may be now."""
-    from manga_image_translator_amd import lib
-
-    prev = lib.load().mit_cotenant_safe_set(0)
-    try:
-        bad = _count_disturbed()
-    finally:
-        lib.load().mit_cotenant_safe_set(prev)
+    bad = _count_disturbed()
     assert bad == {24: 0, 182: 0}, f"launches that differ from the quiet run, per row length: {bad}"
 
 
 def test_two_stream_page_engine_gives_the_one_stream_bytes(cuda):
     """PageEngine(overlap=True) — LaMa on the caller's stream, detector + OCR on a second one, kernels of both resident at once —
     against the one-stream engine on the same pages: every result tensor identical, from the first call to the fourth (with the SLP
-    build the OCR results differed from the second call on, and the inpainted pages too without the safe mode)."""
+    build the OCR results differed from the second call on, and the inpainted pages too unless the FFT rows kernels took a whole CU)."""
     import numpy as np
     from manga_image_translator_amd import pipeline, synth
 
