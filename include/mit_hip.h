@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 14
+#define MIT_ABI_VERSION 15
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -791,6 +791,60 @@ int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *args, void 
  * third of the time per Linear at one page.  Needs GEMM mode 6 | 9.  rows < 0 only queries; 0 = never.  Initial value 2560 (16 pages of
  * 32 lines).  Returns the previous value.  Nothing in the reference corresponds to it. */
 int mit_ocr48_decode_rows_max_set(int rows);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * 32px OCR (``--ocr 32px``): reference manga_translator/ocr/model_32px.py.  Backbone and encoder run on the entry points above
+ * (FAN ResNet [3, 6, 7, 5] :143-234, 3 x post-norm nn.TransformerEncoderLayer :474-476); the decoder is the call below. */
+
+/* OCR(dictionary, 768)'s decoder side (:467-489): 2 x nn.TransformerDecoderLayer(320, 4) (post-norm, FFN 2048, ReLU), embedding,
+ * sinusoidal table pe.pe, pred1 (+ ReLU), pred (weight tied to embd), color_pred1 (+ ReLU) and the six 64 -> 1 colour heads packed as
+ * one 64 -> 6 Linear in the order fg_r, fg_g, fg_b, bg_r, bg_g, bg_b (:484-489). */
+typedef struct MitOcr32Decoder {
+    MitOcrDecoderLayer layers[2];
+    const float *embd;     /* [dict][320] */
+    const float *pe;       /* [pe_len][320]: PositionalEncoding.pe (:289-300) */
+    MitLinear pred1;       /* 320 -> 320, ReLU */
+    MitLinear pred;        /* 320 -> dict */
+    MitLinear color1;      /* 320 -> 64, ReLU */
+    MitLinear color_heads; /* 64 -> 6 */
+    int32_t dict_size, pe_len;
+} MitOcr32Decoder;
+
+typedef struct MitOcr32DecodeArgs {
+    int32_t N, L;               /* text lines; padded encoder-memory length */
+    const float *mem_k;         /* [2][N][L][320] cross-attention keys of the memory per decoder layer (multihead_attn's k projection) */
+    const float *mem_v;         /* [2][N][L][320] */
+    const int32_t *mem_len;     /* [N] valid memory length (w + 3) / 4 + 2 (:523); keys beyond it are masked */
+    int32_t max_seq_length;     /* T: iterations of the beam loop after the first step (255 in the reference call, :100) */
+    int32_t start_tok, end_tok; /* 1, 2 (:518) */
+    int32_t max_finished;       /* max_finished_hypos (2, :518); 1 or 2 */
+    void *workspace;            /* device scratch of mit_ocr32_decode_workspace_bytes() */
+    int64_t workspace_bytes;
+    int32_t *res_tok;           /* [N][T+2] tokens incl. the start token, 0 beyond res_len */
+    int32_t *res_len;           /* [N] number of valid tokens in res_tok */
+    float *res_prob;            /* [N] exp(mean(out_logprobs)), the start token's 0.0 included (:398-399) */
+    float *colors;              /* [N][T+1][8]: the six colour heads over the chosen hypothesis's output history (res_len - 1 positions) */
+    int32_t *res_src;           /* optional [N][T+1]: beam row that holds position t of the chosen hypothesis's history, -1 beyond it */
+    float *trace_logits;        /* optional [T+1][N*5][dict] raw logits per step (pred(pred1(decoded)), :533,:546); NULL in production */
+    int32_t *trace_hist;        /* optional [T+1][N*5][T+2] kept hypotheses after each step (rows of done lines are stale) */
+    int32_t steps_run;          /* out: network evaluations executed (first step included) */
+    int32_t form;               /* 0: the few-row form of a step (every Linear on bf16-plane activations, one wave per 32 x 32 block) where
+                                 * the GEMM mode (6 | 9) and the row count allow, else the tiled form; 1: always the tiled form.  Same
+                                 * arithmetic except the FFN output Linear's K cut across four waves (few rows): tokens equal, the
+                                 * probabilities in their last bits (tests/test_ocr32_gpu.py) */
+} MitOcr32DecodeArgs;
+
+/* The whole beam search of OCR.infer_beam_batch (:518-595) after the encoder as one native call: per step embedding + pe[len] ->
+ * 2 post-norm decoder layers (per-layer K / V history that follows the beam's parent links, instead of next_token_batch's
+ * re-projection of the whole history, :444-451) -> pred1 / pred -> log-softmax / top-5 -> Hypothesis bookkeeping (:549-572), the final
+ * pick (:576-585) and the colour heads (:586-593).  Lines keep their five rows in place after they are done.  Synchronises the stream
+ * every four steps to test for the early exit (:573-574). */
+int64_t mit_ocr32_decode_workspace_bytes(int N, int T, int dict_size);
+int mit_ocr32_decode(const MitOcr32Decoder *dec, MitOcr32DecodeArgs *args, void *stream);
+/* The bookkeeping kernels of mit_ocr32_decode alone, fed with given top-5 tables vals_dev / idx_dev [steps][N*5][5] (log-probabilities
+ * descending and their tokens; step 0 reads row 5 n of line n) instead of a network: fills res_tok / res_len / res_prob / res_src and
+ * trace_hist ([steps][N*5][T+2]) of args (N, max_seq_length, start_tok, end_tok, max_finished, workspace as for the decode). */
+int mit_ocr32_beam_replay(const float *vals_dev, const int32_t *idx_dev, int steps, MitOcr32DecodeArgs *args, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@ import ctypes as C
 from pathlib import Path
 
 MIT_MAX_TAPS = 64
-MIT_ABI_VERSION = 14
+MIT_ABI_VERSION = 15
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SILU, ACT_SIGMOID, ACT_GELU = range(6)
 ACT_POST_FIRST = 0x100
@@ -123,6 +123,19 @@ class MitOcr48DecodeArgs(C.Structure):
                 ("res_tok", C.c_void_p), ("res_len", C.c_void_p), ("res_prob", C.c_void_p), ("res_row", C.c_void_p),
                 ("colors", C.c_void_p), ("trace_logits", C.c_void_p), ("trace_hist", C.c_void_p), ("steps_run", C.c_int32),
                 ("graph_mode", C.c_int32)]
+
+
+class MitOcr32Decoder(C.Structure):
+    _fields_ = [("layers", MitOcrDecoderLayer * 2), ("embd", C.c_void_p), ("pe", C.c_void_p), ("pred1", MitLinear), ("pred", MitLinear),
+                ("color1", MitLinear), ("color_heads", MitLinear), ("dict_size", C.c_int32), ("pe_len", C.c_int32)]
+
+
+class MitOcr32DecodeArgs(C.Structure):
+    _fields_ = [("N", C.c_int32), ("L", C.c_int32), ("mem_k", C.c_void_p), ("mem_v", C.c_void_p), ("mem_len", C.c_void_p),
+                ("max_seq_length", C.c_int32), ("start_tok", C.c_int32), ("end_tok", C.c_int32), ("max_finished", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("res_tok", C.c_void_p), ("res_len", C.c_void_p),
+                ("res_prob", C.c_void_p), ("colors", C.c_void_p), ("res_src", C.c_void_p), ("trace_logits", C.c_void_p),
+                ("trace_hist", C.c_void_p), ("steps_run", C.c_int32), ("form", C.c_int32)]
 
 
 class MitProfStat(C.Structure):
@@ -291,6 +304,9 @@ SYMBOLS = {
     "mit_logsoftmax_top5": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mit_ocr48_decode_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mit_ocr48_decode": (C.c_int, [C.POINTER(MitOcr48Decoder), C.POINTER(MitOcr48DecodeArgs), C.c_void_p]),
+    "mit_ocr32_decode_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mit_ocr32_decode": (C.c_int, [C.POINTER(MitOcr32Decoder), C.POINTER(MitOcr32DecodeArgs), C.c_void_p]),
+    "mit_ocr32_beam_replay": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MitOcr32DecodeArgs), C.c_void_p]),
     "mit_resize_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "mit_select_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),

@@ -58,19 +58,20 @@ class _Block:
             self.down = ops.Conv2d((w * s[None, :, None, None]).float(), (w[:, :, 0, 0] @ t).float(), device=device)
 
 
-class OcrCtcEngine:
-    """forward(): u8 line crops of one reference chunk -> (logits [N,T,dict], colours [N,T,6]); decode(): greedy CTC."""
+class FanBackbone:
+    """The FAN pre-activation ResNet (ResNet.forward, model_48px_ctc.py:335-370) on NHWC fp32.  ``layers``: blocks per stage;
+    ``tail_kernel``: 3 = conv4_1 3 x 3 s(2,1) p1 + conv4_2 3 x 3 p0 (48px_ctc, :362-368), 2 = conv4_1 2 x 2 s(2,1) p(0,1) + conv4_2
+    2 x 2 p0 (the 32px model, model_32px.py:177-181).  ``buf(name, *shape)`` hands out workspace slabs."""
 
-    def __init__(self, sd: Dict[str, torch.Tensor], dict_size: int, device="cuda"):
-        self.device = dev = torch.device(device)
-        self.dict_size = dict_size
+    def __init__(self, sd: Dict[str, torch.Tensor], device, layers: Sequence[int] = tuple(LAYERS), tail_kernel: int = 3):
+        dev = device
         p = "backbone.ConvNet"
         self.conv0_1 = ops.Conv2d(sd[p + ".conv0_1.weight"], None, padding=1, bn=_bn(sd, p + ".bn0_1"), act=ACT_RELU, device=dev)
         self.conv0_2 = ops.Conv2d(sd[p + ".conv0_2.weight"], None, padding=1, device=dev)
         self.layers: List[List[_Block]] = []
         self.tails = []
         inpl = 40
-        for li, (planes, n) in enumerate(zip(CHANNELS, LAYERS), start=1):
+        for li, (planes, n) in enumerate(zip(CHANNELS, layers), start=1):
             closing = _bn(sd, f"{p}.bn{li}") if li < 4 else _bn(sd, p + ".bn4_1")
             blocks = []
             for b in range(n):
@@ -79,10 +80,79 @@ class OcrCtcEngine:
             self.layers.append(blocks)
             if li < 4:
                 self.tails.append(ops.Conv2d(sd[f"{p}.conv{li}.weight"], None, padding=1, device=dev))
-        # conv4_1 (s(2,1), p1) carries bn4_2 + relu, conv4_2 (p0) carries bn4_3 (:362-368)
-        self.conv4_1 = ops.Conv2d(sd[p + ".conv4_1.weight"], None, stride=(2, 1), padding=(1, 1), bn=_bn(sd, p + ".bn4_2"),
+        # conv4_1 (s(2,1)) carries bn4_2 + relu, conv4_2 (p0) carries bn4_3 (:362-368)
+        pad41 = (1, 1) if tail_kernel == 3 else (0, 1)
+        self.conv4_1 = ops.Conv2d(sd[p + ".conv4_1.weight"], None, stride=(2, 1), padding=pad41, bn=_bn(sd, p + ".bn4_2"),
                                   act=ACT_RELU, device=dev)
         self.conv4_2 = ops.Conv2d(sd[p + ".conv4_2.weight"], None, padding=0, bn=_bn(sd, p + ".bn4_3"), device=dev)
+
+    def out_width(self, Wp: int) -> int:
+        """Feature columns for a padded crop width Wp (two 2 x 2 pools, then +1 at the third pool, +/- the tail convs)."""
+        w = Wp // 2 // 2 + 1
+        w = self.conv4_1.out_hw(4, w)[1]
+        return self.conv4_2.out_hw(4, w)[1]
+
+    def __call__(self, x: torch.Tensor, buf, post: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [N,H,Wp,4] -> [N,1,T,320]; ``post`` (optional, the output's shape, any strides): added in conv4_2's epilogue."""
+        lib = _lib.load()
+        st = C.c_void_p(ops.current_stream())
+
+        def affine_relu(src, sc_bi, out):
+            B, H, W, Cc = src.shape
+            _lib.check(lib.mit_affine_act_nhwc(src.data_ptr(), src.stride(2), sc_bi[0].data_ptr(), sc_bi[1].data_ptr(), out.data_ptr(),
+                                               out.stride(2), B * H * W, Cc, 1, st), "mit_affine_act_nhwc")
+
+        def pool(src, name, kh, kw, sh, sw, ph, pw):
+            B, H, W, Cc = src.shape
+            Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+            out = buf(name, B, Ho, Wo, Cc)
+            _lib.check(lib.mit_avgpool_nhwc(src.data_ptr(), out.data_ptr(), B, H, W, Cc, kh, kw, sh, sw, ph, pw, st), "mit_avgpool_nhwc")
+            return out
+
+        B = x.shape[0]
+        a = buf("c01", B, x.shape[1], x.shape[2], 40)
+        self.conv0_1(x, out=a)
+        cur = buf("c02", B, x.shape[1], x.shape[2], 40)
+        self.conv0_2(a, out=cur)
+        pools = [(2, 2, 2, 2, 0, 0), (2, 2, 2, 2, 0, 0), (2, 2, 2, 1, 0, 1), None]
+        for li, blocks in enumerate(self.layers):
+            if pools[li] is not None:
+                cur = pool(cur, f"pool{li}", *pools[li])
+            _, H, W, _ = cur.shape
+            for bi, blk in enumerate(blocks):
+                cin, planes = cur.shape[3], CHANNELS[li]
+                pre = buf(f"pre{li}", B, H, W, cin)
+                affine_relu(cur, blk.pre, pre)
+                mid = buf(f"mid{li}", B, H, W, planes)
+                blk.conv1(pre, out=mid)
+                res = cur
+                if blk.down is not None:
+                    res = buf(f"res{li}", B, H, W, planes)
+                    blk.down(cur, out=res)
+                nxt = buf(f"x{li}_{bi & 1}", B, H, W, planes)
+                if blk.closing:
+                    blk.conv2(mid, out=nxt, pre=res)    # relu(bn(conv2 + residual)): input of the layer's trailing conv
+                else:
+                    blk.conv2(mid, out=nxt, post=res)   # conv2 + residual
+                cur = nxt
+            if li < 3:
+                t = buf(f"tail{li}", B, H, W, CHANNELS[li])
+                self.tails[li](cur, out=t)
+                cur = t
+        a = buf("c41", B, *self.conv4_1.out_hw(cur.shape[1], cur.shape[2]), 320)
+        self.conv4_1(cur, out=a)
+        f = buf("c42", B, *self.conv4_2.out_hw(a.shape[1], a.shape[2]), 320)
+        self.conv4_2(a, out=f, post=post)
+        return f
+
+
+class OcrCtcEngine:
+    """forward(): u8 line crops of one reference chunk -> (logits [N,T,dict], colours [N,T,6]); decode(): greedy CTC."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], dict_size: int, device="cuda"):
+        self.device = dev = torch.device(device)
+        self.dict_size = dict_size
+        self.backbone = FanBackbone(sd, dev, LAYERS, 3)
         self.enc = []
         s = HEAD_DIM ** -0.5
         for i in range(3):
@@ -117,56 +187,9 @@ class OcrCtcEngine:
     def release_workspace(self):
         self._ws.clear()
 
-    def _affine_relu(self, x, sc_bi, out):
-        B, H, W, Cc = x.shape
-        _lib.check(_lib.load().mit_affine_act_nhwc(x.data_ptr(), x.stride(2), sc_bi[0].data_ptr(), sc_bi[1].data_ptr(), out.data_ptr(),
-                                                   out.stride(2), B * H * W, Cc, 1, C.c_void_p(ops.current_stream())), "mit_affine_act_nhwc")
-
-    def _pool(self, x, name, kh, kw, sh, sw, ph, pw):
-        B, H, W, Cc = x.shape
-        Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
-        out = self._buf(name, B, Ho, Wo, Cc)
-        _lib.check(_lib.load().mit_avgpool_nhwc(x.data_ptr(), out.data_ptr(), B, H, W, Cc, kh, kw, sh, sw, ph, pw,
-                                                C.c_void_p(ops.current_stream())), "mit_avgpool_nhwc")
-        return out
-
     def _backbone(self, x: torch.Tensor) -> torch.Tensor:
         """ResNet.forward (:335-370). x [N,48,Wp,4] -> [N,1,T,320]."""
-        B = x.shape[0]
-        a = self._buf("c01", B, x.shape[1], x.shape[2], 40)
-        self.conv0_1(x, out=a)
-        cur = self._buf("c02", B, x.shape[1], x.shape[2], 40)
-        self.conv0_2(a, out=cur)
-        pools = [(2, 2, 2, 2, 0, 0), (2, 2, 2, 2, 0, 0), (2, 2, 2, 1, 0, 1), None]
-        for li, blocks in enumerate(self.layers):
-            if pools[li] is not None:
-                cur = self._pool(cur, f"pool{li}", *pools[li])
-            _, H, W, _ = cur.shape
-            for bi, blk in enumerate(blocks):
-                cin, planes = cur.shape[3], CHANNELS[li]
-                pre = self._buf(f"pre{li}", B, H, W, cin)
-                self._affine_relu(cur, blk.pre, pre)
-                mid = self._buf(f"mid{li}", B, H, W, planes)
-                blk.conv1(pre, out=mid)
-                res = cur
-                if blk.down is not None:
-                    res = self._buf(f"res{li}", B, H, W, planes)
-                    blk.down(cur, out=res)
-                nxt = self._buf(f"x{li}_{bi & 1}", B, H, W, planes)
-                if blk.closing:
-                    blk.conv2(mid, out=nxt, pre=res)    # relu(bn(conv2 + residual)): input of the layer's trailing conv
-                else:
-                    blk.conv2(mid, out=nxt, post=res)   # conv2 + residual
-                cur = nxt
-            if li < 3:
-                t = self._buf(f"tail{li}", B, H, W, CHANNELS[li])
-                self.tails[li](cur, out=t)
-                cur = t
-        a = self._buf("c41", B, *self.conv4_1.out_hw(cur.shape[1], cur.shape[2]), 320)
-        self.conv4_1(cur, out=a)
-        f = self._buf("c42", B, *self.conv4_2.out_hw(a.shape[1], a.shape[2]), 320)
-        self.conv4_2(a, out=f)
-        return f
+        return self.backbone(x, self._buf)
 
     @torch.no_grad()
     def forward(self, region_u8: torch.Tensor, taps: Optional[dict] = None):

@@ -17,12 +17,16 @@ CHANNELS = [80, 160, 320, 320]
 LAYERS = [4, 6, 8, 6]
 
 
-def resnet_schema(prefix: str = "backbone.ConvNet") -> Schema:
+def resnet_schema(prefix: str = "backbone.ConvNet", layers=None, tail_kernel: int = 3) -> Schema:
+    """``layers`` / ``tail_kernel``: block counts and the kernel size of conv4_1 / conv4_2 (the 32px model's backbone is this ResNet with
+    [3, 6, 7, 5] and 2 x 2 tails, ocr/model_32px.py:177-181,284)."""
     p = prefix
+    layers = LAYERS if layers is None else layers
+    tk = tail_kernel
     s: Schema = [(f"{p}.conv0_1.weight", (40, 3, 3, 3), "conv")] + bn_entries(f"{p}.bn0_1", 40)
     s += [(f"{p}.conv0_2.weight", (40, 40, 3, 3), "conv")]
     inpl = 40
-    for li, (planes, n) in enumerate(zip(CHANNELS, LAYERS), start=1):
+    for li, (planes, n) in enumerate(zip(CHANNELS, layers), start=1):
         for b in range(n):
             q = f"{p}.layer{li}.{b}"
             # residual branches would grow ~1.4x per block with unit BN gains: damp the second BN so 24 blocks stay O(1)
@@ -33,8 +37,8 @@ def resnet_schema(prefix: str = "backbone.ConvNet") -> Schema:
             inpl = planes
         if li < 4:
             s += bn_entries(f"{p}.bn{li}", planes) + [(f"{p}.conv{li}.weight", (planes, planes, 3, 3), "conv")]
-    s += bn_entries(f"{p}.bn4_1", 320) + [(f"{p}.conv4_1.weight", (320, 320, 3, 3), "conv")]
-    s += bn_entries(f"{p}.bn4_2", 320) + [(f"{p}.conv4_2.weight", (320, 320, 3, 3), "conv")]
+    s += bn_entries(f"{p}.bn4_1", 320) + [(f"{p}.conv4_1.weight", (320, 320, tk, tk), "conv")]
+    s += bn_entries(f"{p}.bn4_2", 320) + [(f"{p}.conv4_2.weight", (320, 320, tk, tk), "conv")]
     s += bn_entries(f"{p}.bn4_3", 320)
     return s
 

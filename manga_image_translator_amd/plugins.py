@@ -6,6 +6,7 @@ Each class honours the contract of its reference counterpart:
   HipDefaultDetector     <- DefaultDetector     (detection/default.py:27-103)
   HipModel48pxOCR        <- Model48pxOCR        (ocr/model_48px.py:25-180)
   HipModel48pxCTCOCR     <- Model48pxCTCOCR     (ocr/model_48px_ctc.py:30-160)
+  HipModel32pxOCR        <- Model32pxOCR        (ocr/model_32px.py:19-140)
   HipLamaMPEInpainter    <- LamaMPEInpainter    (inpainting/inpainting_lama_mpe.py:26-118)
   HipLamaLargeInpainter  <- LamaLargeInpainter  (inpainting/inpainting_lama_mpe.py:121-136)
   HipAotInpainter        <- AotInpainter        (inpainting/inpainting_aot.py:11-33), the reference's ``Inpainter.default``
@@ -484,6 +485,83 @@ class HipModel48pxCTCOCR(HipModel48pxOCR):
         return out
 
 
+class HipModel32pxOCR(HipModel48pxOCR):
+    """``--ocr 32px`` on the HIP engine (ocr/model_32px.py:19-140)."""
+    _KEY = _key = "32px_hip"
+    _MODEL_MAPPING: Dict = {  # ocr/model_32px.py:20-29
+        "model": {
+            "url": "https://github.com/zyddnys/manga-image-translator/releases/download/beta-0.3/ocr.zip",
+            "hash": "47405638b96fa2540a5ee841a4cd792f25062c09d9458a973362d40785f95d7a",
+            "archive": {
+                "ocr.ckpt": ".",
+                "alphabet-all-v5.txt": ".",
+            },
+        },
+    }
+
+    async def _load(self, device: str):
+        from . import ocr32
+
+        dev = _gpu_device(device)
+        if self._weights is None or self.dictionary is None:
+            self._weights, self.dictionary = _load_ocr32_checkpoint(self)
+        self.engine = ocr32.Ocr32Engine(self._weights, len(self.dictionary), device=dev)
+        self.device = device
+
+    @torch.no_grad()
+    async def _infer(self, image: np.ndarray, textlines: List, config=None, verbose: bool = False, max_seq_length: int = 255):
+        """Same contract as the 48px plugin with the 32px model's rules (:58-140): text height 32, chunks padded to max_w + 7, the line
+        probability exp(mean log-prob) against a 0.7 default threshold (:62), each colour the mean of the clipped head over ALL positions of
+        the chosen hypothesis's history (:104-109).  ``config.ignore_bubble`` in 1..50: a rejected line's rows of the chunk stay zero and it
+        is decoded as such (:84-86).  Returns the accepted lines in processing order."""
+        from . import textline as TL
+
+        threshold = 0.7 if config is None or getattr(config, "prob", None) is None else config.prob
+        ignore_bubble = int(getattr(config, "ignore_bubble", 0) or 0) if config is not None else 0
+        pairs = self._directions(textlines)
+        if not pairs:
+            return []
+        quads = [q for q, _ in pairs]
+        dirs = [d for _, d in pairs]
+        page = torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device)[None]
+        own = [_own_quad(q) for q in quads]
+        reject = (lambda crop: TL.is_ignore(crop, ignore_bubble)) if 1 <= ignore_bubble <= 50 else None
+        r = self.engine.recognize_lines(page, own, dirs, max_seq_length=max_seq_length, reject=reject)
+        toks, lens = r["tokens"].cpu().numpy(), r["length"].cpu().numpy()
+        probs, cols = r["prob"].cpu().numpy(), r["colors"].cpu().numpy()
+        out = []
+        for row, i in enumerate(r["order"]):
+            q, prob = quads[i], float(probs[row])
+            q.assigned_direction = dirs[i]
+            if prob < threshold:
+                continue
+            n = int(lens[row])
+            txt, fgc, bgc = decode_32px_line(toks[row, :n], cols[row, :n - 1], self.dictionary)
+            q.text, q.prob = txt, prob
+            q.fg_r, q.fg_g, q.fg_b = fgc
+            q.bg_r, q.bg_g, q.bg_b = bgc
+            out.append(q)
+        return out
+
+
+def decode_32px_line(tokens, colour_history, dictionary: Sequence[str]) -> Tuple[str, Tuple[int, int, int], Tuple[int, int, int]]:
+    """Tokens (start symbol included) + the six colour heads over the hypothesis's output history [len, 6] -> (text, fg rgb, bg rgb):
+    model_32px.py:104-120.  Each colour is ``(clip(head, 0, 1).mean() * 255)`` truncated, in float32 like the reference, over every
+    position — the one that predicted ``</S>`` too; the text skips ``<S>``, stops at ``</S>`` and maps ``<SP>`` to a blank."""
+    col = np.clip(np.asarray(colour_history, dtype=np.float32).reshape(-1, 6), np.float32(0), np.float32(1))
+    mean = col.mean(axis=0, dtype=np.float32) * np.float32(255)
+    c = [int(v) for v in mean]   # .long(): truncation
+    seq: List[str] = []
+    for t in tokens:
+        ch = dictionary[int(t)]
+        if ch == "<S>":
+            continue
+        if ch == "</S>":
+            break
+        seq.append(" " if ch == "<SP>" else ch)
+    return "".join(seq), (c[0], c[1], c[2]), (c[3], c[4], c[5])
+
+
 def decode_ctc_line(line, dictionary: Sequence[str]):
     """[(char id, log-prob, fr, fg, fb, br, bg, bb)] -> (text, prob, fg rgb, bg rgb) or None for an empty line:
     model_48px_ctc.py:105-134 (AvgMeter means; colours only over non-space characters; prob = exp(mean log-prob))."""
@@ -878,6 +956,16 @@ def _load_ocr_ctc_checkpoint(plugin):
     return synth.check_state_dict(sd, ocr_ctc_schema.ocr_ctc_schema(len(dictionary)), "ocr-ctc.ckpt"), dictionary
 
 
+def _load_ocr32_checkpoint(plugin):
+    """ocr.ckpt ({'model': state_dict} or bare, ``pe.pe`` included) + alphabet-all-v5.txt (model_32px.py:39-45)."""
+    from . import ocr32_schema, synth
+
+    dictionary = _read_dictionary(_ckpt_path(plugin, "alphabet-all-v5.txt"))
+    sd = torch.load(_ckpt_path(plugin, "ocr.ckpt"), map_location="cpu")
+    sd = sd["model"] if "model" in sd else sd
+    return synth.check_state_dict(sd, ocr32_schema.ocr32_schema(len(dictionary)), "ocr.ckpt"), dictionary
+
+
 def _load_lama_checkpoint(plugin):
     """{'gen_state_dict', 'str_state_dict'?} (inpainting_lama_mpe.py:818-825)."""
     from . import lama_schema, synth
@@ -946,6 +1034,7 @@ def register() -> None:
 
     for reg, enum_name, cls in ((DETECTORS, "Detector", HipComicTextDetector), (DETECTORS, "Detector", HipDefaultDetector),
                                 (OCRS, "Ocr", HipModel48pxOCR), (OCRS, "Ocr", HipModel48pxCTCOCR),
+                                (OCRS, "Ocr", HipModel32pxOCR),
                                 (INPAINTERS, "Inpainter", HipLamaMPEInpainter), (INPAINTERS, "Inpainter", HipLamaLargeInpainter),
                                 (INPAINTERS, "Inpainter", HipAotInpainter),
                                 (UPSCALERS, "Upscaler", HipESRGANUpscaler), (COLORIZERS, "Colorizer", HipMangaColorizer)):

@@ -88,6 +88,9 @@ def synth_state_dict(schema: Schema, seed: int = 0, gain: float = 1.0) -> Dict[s
             pe[:, 0::2] = torch.sin(position * div_term)
             pe[:, 1::2] = torch.cos(position * div_term)
             t = pe.unsqueeze(0)
+        elif kind == "sinus_pe_t":  # the same table as a [max_len, 1, d_model] buffer (ocr/model_32px.py:289-300)
+            max_len, _, d_model = shape
+            t = synth_state_dict([("pe", (1, max_len, d_model), "sinus_pe")])["pe"].transpose(0, 1).contiguous()
         elif kind.startswith("tie:"):  # shares storage with an earlier entry (pred.weight = embd.weight, model_48px.py:536)
             t = sd[kind.split(":", 1)[1]]
         else:
