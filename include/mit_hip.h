@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 15
+#define MIT_ABI_VERSION 16
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -620,6 +620,21 @@ int mit_mask_assign_lines(uint8_t *mask, int H, int W, const int32_t *boxes_xywh
  * reads out of its page-sized per-line images (text_mask_utils.py:145,173). */
 int mit_mask_line_crops(const MitMaskRun *runs, int64_t n_runs, const int32_t *assign, const int32_t *jobs, int n_jobs, uint8_t *out,
                         const int64_t *offsets);
+/* Mask refinement, the same half on the DEVICE (csrc/mask_assign.hip) for a working-scale mask that already lives there; V must be 4.
+ * mask_dev: u8 [H,W], outlined in place like the host routine's.  boxes_xywh_dev / polys_dev / font_size_dev: the host routine's
+ * arrays in device memory.  ws_dev: mit_mask_assign_workspace_bytes(H, W) bytes (int32 planes of H*W entries: root label per pixel,
+ * area / rectangle / line per root — no cap on the number of components); it holds the labelling for mit_mask_line_crops_dev until
+ * the next call.  line_rects_dev: i32 [4*M + 4]: the host routine's line_rects, then a status word {components assigned, components
+ * of more than 9 pixels, components, 0}.  Decisions are the host routine's (same double / fp32 expressions, no contraction): equal
+ * rectangles, not close ones.  Asynchronous on the stream; no allocation, no synchronisation. */
+int64_t mit_mask_assign_workspace_bytes(int H, int W);
+int mit_mask_assign_lines_dev(uint8_t *mask_dev, int H, int W, const int32_t *boxes_xywh_dev, const double *polys_dev,
+                              const double *font_size_dev, int M, int V, double keep_threshold, void *ws_dev, int64_t ws_bytes,
+                              int32_t *line_rects_dev, void *stream);
+/* mit_mask_line_crops from the workspace mit_mask_assign_lines_dev left: jobs_dev i32 [n_jobs,5] (line, x, y, w, h), offsets_dev
+ * i64 [n_jobs] ascending, total = bytes of all crops; out_dev is the packed crop buffer mit_densecrf_refine reads as mask_dev. */
+int mit_mask_line_crops_dev(const void *ws_dev, int64_t ws_bytes, int H, int W, const int32_t *jobs_dev, const int64_t *offsets_dev,
+                            int n_jobs, int64_t total, uint8_t *out_dev, void *stream);
 /* merge_mask_list of the ctd detector's refine_mask (detection/ctd_utils/textmask.py:74-132; filter_with_lines False), HOST
  * pointers: n_cands candidate masks [n_cands][h*w] (0 / 255) with their xor scores, the network's mask window pred_mask [h*w];
  * merged [h*w] receives the result.  Candidates in ascending score, their 8-connected components in raster order of the first

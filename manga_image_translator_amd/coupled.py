@@ -44,6 +44,7 @@ class CoupledResult:
     mask: torch.Tensor                         # u8 [B,H,W] final inpainting mask (device)
     inpainted: torch.Tensor                    # u8 [B,H,W,3] (device)
     seconds: Dict[str, float] = field(default_factory=dict)   # host wall time per phase (the GPU runs asynchronously underneath)
+    mask_raw: Optional[torch.Tensor] = None   # u8 [B,H,W] the mask the refinement started from (the detector's, or the request's)
 
 
 def synthetic_head_outputs(page: np.ndarray, quads: np.ndarray, map_hw, shrink_ratio: float = 0.4, unclip_ratio: float = 1.5):
@@ -87,6 +88,21 @@ class CoupledPageEngine:
         self.ctd = ctd.CtdEngine(weights["ctd.yolo"], weights["ctd.seg"], weights["ctd.det"], device=self.device)
         self.ocr = ocr48.Ocr48Engine(weights["ocr48"], len(self.dictionary), device=self.device)
         self.lama = lama.LamaEngine(weights["lama.gen"], weights.get("lama.mpe"), n_blocks=lama_blocks, device=self.device)
+        self._init_host(ctd_mb, lama_mb, host_workers, mask_workers, side_stream)
+
+    @classmethod
+    def from_engines(cls, ctd_engine, ocr_engine, lama_engine, dictionary: Sequence[str], ctd_mb: int = 16, lama_mb: int = 16,
+                     host_workers: int = 16, mask_workers: int = 4, side_stream: Optional[bool] = None) -> "CoupledPageEngine":
+        """On the engines loaded plugins already own (``plugin.engine``): no second copy of any weight.  The engine objects are kept,
+        not their methods, so whatever a caller hangs on ``engine.forward`` afterwards is what a run calls."""
+        self = cls.__new__(cls)
+        self.device = torch.device(ctd_engine.device)
+        self.dictionary = list(dictionary)
+        self.ctd, self.ocr, self.lama = ctd_engine, ocr_engine, lama_engine
+        self._init_host(ctd_mb, lama_mb, host_workers, mask_workers, side_stream)
+        return self
+
+    def _init_host(self, ctd_mb, lama_mb, host_workers, mask_workers, side_stream):
         self.ctd_mb, self.lama_mb = ctd_mb, lama_mb
         self.pool = cf.ThreadPoolExecutor(max_workers=host_workers, thread_name_prefix="mit-host")
         # mask refinement: a few pages in flight at once — each worker thread owns a backend (its DenseCRF workspace); their launches
@@ -180,8 +196,11 @@ class CoupledPageEngine:
         return out
 
     # ---- stages 3 + 4: text-line merge, mask refinement -------------------------------------------------------------------
-    def merge_and_refine(self, pages_u8: torch.Tensor, textlines: List[List[Quadrilateral]], mask_raw: torch.Tensor):
+    def merge_and_refine(self, pages_u8: torch.Tensor, textlines: List[List[Quadrilateral]], mask_raw: torch.Tensor,
+                         given: Optional[Sequence] = None, dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE):
+        """``given``: per page None or the request's final mask (u8 [H,W], host or device): that page skips merge + refinement."""
         B, H, W, _ = pages_u8.shape
+        given = list(given) if given is not None else [None] * B
         main = torch.cuda.current_stream()
         # Mask refinement alternates short kernels with host arithmetic (labelling -> assignment -> CRF -> dilation): on the caller's
         # stream each of its read-backs waits for whatever the other stages queued ahead (a LaMa group: a quarter of a second), and the
@@ -198,15 +217,21 @@ class CoupledPageEngine:
                 side.wait_event(ready)
                 mask_raw.record_stream(side)
             final = torch.zeros(B, H, W, dtype=torch.uint8, device=self.device)   # (from the side stream's own pool of blocks)
-        regions = list(self.pool.map(lambda ls: TM.dispatch_sync(ls, W, H) if ls else [], textlines))
+        regions = list(self.pool.map(lambda b: TM.dispatch_sync(textlines[b], W, H) if textlines[b] and given[b] is None else [], range(B)))
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
 
         def refine(b):
+            if given[b] is not None:
+                torch.cuda.set_device(dev_index)
+                with torch.cuda.stream(side):
+                    g = given[b]
+                    final[b] = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g, dtype=np.uint8)).to(self.device)
+                return True
             if not regions[b]:
                 return None      # no text: the orchestrator returns the page as it is (manga_translator.py:500-504)
             torch.cuda.set_device(dev_index)
             with torch.no_grad(), torch.cuda.stream(side):
-                m = MR.dispatch_device(regions[b], pages_u8[b], mask_raw[b], dilation_offset=MASK_DILATION_OFFSET, kernel_size=KERNEL_SIZE,
+                m = MR.dispatch_device(regions[b], pages_u8[b], mask_raw[b], dilation_offset=dilation_offset, kernel_size=kernel_size,
                                        backend=self._mask_backend())
                 final[b] = m
                 return True
@@ -230,45 +255,82 @@ class CoupledPageEngine:
     # ---- the whole path -----------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def run(self, pages_u8: torch.Tensor, max_seq_length: int = 255, suppress_eos: bool = False, prob_threshold: float = 0.2,
-            inject=None, group: Optional[int] = 16) -> CoupledResult:
+            inject=None, group: Optional[int] = 16, textlines: Optional[Sequence] = None, mask_raw: Optional[Sequence] = None,
+            mask: Optional[Sequence] = None, mask_dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE,
+            inpainting_size: Optional[int] = None) -> CoupledResult:
         """``group``: pages per pipeline slot.  A batch larger than one group flows through three stage threads (detector + boxes +
         refine_mask | OCR | merge + mask refinement + LaMa), each working on a different group at a time, so the host phases of one
         group run while the kernels of its neighbours execute; every stage sees the groups in order and owns its engines, and each
-        page's result is what the unpipelined call (``group=None``) gives."""
+        page's result is what the unpipelined call (``group=None``) gives.
+
+        What a request may carry, per page (each a sequence of B entries, None where the page brings nothing): ``textlines`` — quads
+        [n,4,2] that replace the detector's (the detector still runs, as in ``serve.DenseStages.translate``); ``mask_raw`` — u8 [H,W]
+        that replaces the detector's refined mask ahead of merge + refinement; ``mask`` — the final mask, which skips merge +
+        refinement.  ``inpainting_size``: the inpainter plugin's resize rule (``plugins.inpaint_pages``); None = the pages go to the
+        network as they are (H, W multiples of 8).  The defaults are the constants the benchmark path has always used."""
         if pages_u8.dtype != torch.uint8 or pages_u8.dim() != 4 or pages_u8.shape[-1] != 3 or not pages_u8.is_cuda:
             raise ValueError(f"CoupledPageEngine.run expects a uint8 device tensor [B,H,W,3], got {pages_u8.dtype} {tuple(pages_u8.shape)}")
         B = pages_u8.shape[0]
+        for name, v in (("textlines", textlines), ("mask_raw", mask_raw), ("mask", mask)):
+            if v is not None and len(v) != B:
+                raise ValueError(f"CoupledPageEngine.run: {name} must have one entry per page ({len(v)} for {B} pages)")
+        req = {"textlines": textlines, "mask_raw": mask_raw, "mask": mask, "offset": int(mask_dilation_offset), "kernel": int(kernel_size),
+               "inpainting_size": inpainting_size}
         if group is not None and B > group:
-            return self._run_pipelined(pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, int(group))
+            return self._run_pipelined(pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, int(group), req)
         sec = {}
         t = time.perf_counter()
-        textlines, mask_raw = self.detect(pages_u8, inject)
+        tl, mraw = self._requested(*self.detect(pages_u8, inject), req, 0, B)
         sec["detect+boxes+refine_mask"] = time.perf_counter() - t
         t = time.perf_counter()
-        textlines = self.recognize(pages_u8, textlines, max_seq_length, suppress_eos, prob_threshold)
+        tl = self.recognize(pages_u8, tl, max_seq_length, suppress_eos, prob_threshold)
         sec["ocr"] = time.perf_counter() - t
         t = time.perf_counter()
-        regions, mask = self.merge_and_refine(pages_u8, textlines, mask_raw)
+        regions, final = self.merge_and_refine(pages_u8, tl, mraw, mask, req["offset"], req["kernel"])
         sec["textline_merge+mask_refinement"] = time.perf_counter() - t
         t = time.perf_counter()
         inpainted = torch.empty_like(pages_u8)
-        for i in range(0, B, self.lama_mb):
-            j = min(B, i + self.lama_mb)
-            inpainted[i:j].copy_(self.lama.forward(pages_u8[i:j], mask[i:j]))
+        self._inpaint(pages_u8, final, inpainted, inpainting_size)
         sec["inpaint (enqueue)"] = time.perf_counter() - t
-        return CoupledResult(textlines, regions, mask, inpainted, sec)
+        return CoupledResult(tl, regions, final, inpainted, sec, mraw)
 
-    def _inpaint(self, pages_u8: torch.Tensor, mask: torch.Tensor, out: torch.Tensor):
+    def _requested(self, textlines, mask_raw, req, a, b):
+        """The detector's lines / refined masks of pages a..b with what the request brings for them laid over."""
+        tin, min_ = req["textlines"], req["mask_raw"]
+        if tin is not None:
+            for k in range(a, b):
+                if tin[k] is not None:
+                    textlines[k - a] = [Quadrilateral(np.asarray(p, dtype=np.int64), "", 1.0) for p in tin[k]]
+        if min_ is not None and any(min_[k] is not None for k in range(a, b)):
+            ready = getattr(mask_raw, "mit_ready_event", None)
+            for k in range(a, b):
+                if min_[k] is not None:
+                    m = min_[k]
+                    m = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint8))
+                    if tuple(m.shape) != tuple(mask_raw.shape[1:]):
+                        raise ValueError(f"mask_raw of page {k} must be {tuple(mask_raw.shape[1:])} (got {tuple(m.shape)})")
+                    mask_raw[k - a] = m.to(self.device)
+            if ready is not None:
+                mask_raw.mit_ready_event = torch.cuda.current_stream().record_event()
+        return textlines, mask_raw
+
+    def _inpaint(self, pages_u8: torch.Tensor, mask: torch.Tensor, out: torch.Tensor, inpainting_size: Optional[int] = None):
+        if inpainting_size is not None:   # the plugin's resize / composite legs around the network, for the whole group
+            from . import plugins as P
+
+            out.copy_(P.inpaint_pages(self.lama, pages_u8, mask, int(inpainting_size), None, self.lama_mb))
+            return
         for i in range(0, pages_u8.shape[0], self.lama_mb):
             j = min(pages_u8.shape[0], i + self.lama_mb)
             out[i:j].copy_(self.lama.forward(pages_u8[i:j], mask[i:j]))
 
-    def _run_pipelined(self, pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, group) -> CoupledResult:
+    def _run_pipelined(self, pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, group, req) -> CoupledResult:
         B, H, W, _ = pages_u8.shape
         spans = [(i, min(B, i + group)) for i in range(0, B, group)]
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         sec = {"detect+boxes+refine_mask": 0.0, "ocr": 0.0, "textline_merge+mask_refinement": 0.0, "inpaint (enqueue)": 0.0}
         mask = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        mask_raw_all = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
         inpainted = torch.empty_like(pages_u8)
         caller = torch.cuda.current_stream()
         # One stream per stage thread (``stage_streams``, MIT_COUPLED_STAGE_STREAMS=1): a stage's read-backs wait for ITS kernels only, and
@@ -294,7 +356,7 @@ class CoupledPageEngine:
 
         def st_detect(a, b):
             inj = None if inject is None else {k: v[a:b] for k, v in inject.items()}
-            return timed("detect+boxes+refine_mask", self.detect, pages_u8[a:b], inj)
+            return timed("detect+boxes+refine_mask", lambda: self._requested(*self.detect(pages_u8[a:b], inj), req, a, b))
 
         def st_ocr(a, b, f_det):
             tl, mraw = f_det.result()
@@ -302,10 +364,12 @@ class CoupledPageEngine:
 
         def st_tail(a, b, f_ocr):
             tl, mraw = f_ocr.result()
-            regions, m = timed("textline_merge+mask_refinement", self.merge_and_refine, pages_u8[a:b], tl, mraw)
+            given = None if req["mask"] is None else req["mask"][a:b]
+            regions, m = timed("textline_merge+mask_refinement", self.merge_and_refine, pages_u8[a:b], tl, mraw, given, req["offset"], req["kernel"])
             with torch.cuda.stream(st["tail"]):
                 mask[a:b] = m
-            timed("inpaint (enqueue)", self._inpaint, pages_u8[a:b], mask[a:b], inpainted[a:b])
+                mask_raw_all[a:b] = mraw
+            timed("inpaint (enqueue)", self._inpaint, pages_u8[a:b], mask[a:b], inpainted[a:b], req["inpainting_size"])
             return tl, regions
 
         with cf.ThreadPoolExecutor(1, "mit-st-det") as e1, cf.ThreadPoolExecutor(1, "mit-st-ocr") as e2, cf.ThreadPoolExecutor(1, "mit-st-tail") as e3:
@@ -318,4 +382,4 @@ class CoupledPageEngine:
                 caller.wait_stream(x)
         textlines = [t for tl, _ in done for t in tl]
         regions = [r for _, rg in done for r in rg]
-        return CoupledResult(textlines, regions, mask, inpainted, sec)
+        return CoupledResult(textlines, regions, mask, inpainted, sec, mask_raw_all)

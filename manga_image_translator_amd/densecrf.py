@@ -46,10 +46,16 @@ class DenseCrfRefiner:
                return_q: bool = False, iterations: int = ITERATIONS, packed: bool = False):
         """page_dev u8 [H,W,3] (device), rects (x, y, w, h) per crop, masks u8 [h, w] per crop (host) -> list of u8 [h, w] masks in
         {0, 255} (and the final marginals [h, w, 2] per crop when ``return_q``).  ``packed``: the refined crops stay on the device —
-        returns (u8 device tensor with the crops back to back, row-major, [offset of each crop])."""
+        returns (u8 device tensor with the crops back to back, row-major, [offset of each crop]).  ``masks`` may itself be such a
+        packed u8 device tensor (``GpuMaskBackend.assign_lines_device`` paints it): no host copy of the crops at all then."""
         if page_dev.dtype != torch.uint8 or page_dev.dim() != 3 or page_dev.shape[2] != 3 or not page_dev.is_cuda:
             raise ValueError(f"DenseCrfRefiner.refine expects a uint8 device page [H,W,3], got {page_dev.dtype} {tuple(page_dev.shape)}")
-        if len(rects) != len(masks):
+        masks_dev = masks if isinstance(masks, torch.Tensor) else None
+        if masks_dev is not None:
+            if masks_dev.dtype != torch.uint8 or not masks_dev.is_cuda or not masks_dev.is_contiguous() or \
+                    masks_dev.numel() != sum(int(w) * int(h) for _, _, w, h in rects):
+                raise ValueError("DenseCrfRefiner.refine: packed masks must be one contiguous uint8 device tensor of sum(w * h) bytes")
+        elif len(rects) != len(masks):
             raise ValueError("one mask per crop rectangle")
         if not rects:
             if packed:
@@ -59,12 +65,13 @@ class DenseCrfRefiner:
         H, W, _ = page_dev.shape
         crops = (_lib.MitCrfCrop * len(rects))()
         flat = []
-        for i, ((x, y, w, h), m) in enumerate(zip(rects, masks)):
-            m = np.ascontiguousarray(m, dtype=np.uint8)
-            if m.shape != (h, w):
-                raise ValueError(f"crop {i}: mask {m.shape} does not match its rectangle {(h, w)}")
+        for i, (x, y, w, h) in enumerate(rects):
             crops[i].x, crops[i].y, crops[i].w, crops[i].h = int(x), int(y), int(w), int(h)
-            flat.append(m.reshape(-1))
+            if masks_dev is None:
+                m = np.ascontiguousarray(masks[i], dtype=np.uint8)
+                if m.shape != (h, w):
+                    raise ValueError(f"crop {i}: mask {m.shape} does not match its rectangle {(h, w)}")
+                flat.append(m.reshape(-1))
         L = _lib.load()
         need = L.mit_densecrf_workspace_bytes(C.byref(crops), len(rects))
         if need < 0:
@@ -72,7 +79,7 @@ class DenseCrfRefiner:
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
-        mask_dev = torch.from_numpy(np.concatenate(flat)).to(self.device)
+        mask_dev = masks_dev.reshape(-1) if masks_dev is not None else torch.from_numpy(np.concatenate(flat)).to(self.device)
         out_dev = torch.empty_like(mask_dev)
         q_dev = torch.empty(mask_dev.numel(), 2, dtype=torch.float32, device=self.device) if return_q else None
         _lib.check(L.mit_densecrf_refine(page_dev.data_ptr(), H, W, C.byref(crops), len(rects), mask_dev.data_ptr(), out_dev.data_ptr(),

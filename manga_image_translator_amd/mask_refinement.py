@@ -8,7 +8,9 @@ component labelling and statistics, the component -> text-line assignment (overl
 dilation-size arithmetic, elliptical dilation, the final merge.  On the GPU (default backend ``GpuMaskBackend``): the
 ``cv2.bilateralFilter(img, 17, 80, 80)`` of the page (``mit_bilateral_u8c3``) and the per-line DenseCRF
 (``text_mask_utils.refine_mask`` -> pydensecrf), all lines of the page in ONE batched call (``mit_densecrf_refine``) on the
-filtered page that never leaves the device.  There is no CPU substitute: without the HIP library / a GPU the default backend
+filtered page that never leaves the device — and, when the raw mask is a device tensor (``dispatch_device``, the serving path), the
+component labelling, the line assignment and the crops as well (``GpuMaskBackend.assign_lines_device``, csrc/mask_assign.hip: the same
+decisions as the host code, only the line rectangles come back).  There is no CPU substitute: without the HIP library / a GPU the default backend
 raises.  ``refine=`` / ``bilateral=`` still inject per-crop / per-page callables (the reference's own, or the stubs the pin uses).
 Pinned against the reference's Python, run with stand-ins for cv2 / shapely and the same two callables stubbed on both sides
 (tests/golden/mask_refinement.npz, oracle/make_golden.py); the GPU steps are checked against oracle/densecrf.py and
@@ -51,14 +53,21 @@ class CallableMaskBackend:
 class GpuMaskBackend:
     """Default backend: bilateral filter + batched DenseCRF on the device (imgproc.bilateral_filter_u8, densecrf.DenseCrfRefiner)."""
 
-    def __init__(self, device=None, gpu_tail: bool = True):
+    def __init__(self, device=None, gpu_tail: bool = True, gpu_assign: bool = True):
         """``gpu_tail``: the per-line dilations, their union and the closing dilation run on the device too (``refine_dilate_union``);
-        False keeps them on the host (scipy) — bit-identical, for A/B runs and tests."""
+        False keeps them on the host (scipy) — bit-identical, for A/B runs and tests.
+        ``gpu_assign``: a mask that is a device tensor is outlined, labelled and assigned to the text lines on the device
+        (``assign_lines_device``: ``mit_mask_assign_lines_dev``); False downloads it for the host routine — same rectangles, crops
+        and masks, for A/B runs and tests.  ``device_assigns`` counts the calls the device form served."""
         import torch
 
         from . import densecrf, lib
 
         self.gpu_tail = gpu_tail
+        self.gpu_assign = gpu_assign
+        self.device_assigns = 0
+        self._assign_ws = None
+        self._rects_pinned = None
         lib.load()  # fails loudly without the HIP library
         if device is None:
             if not torch.cuda.is_available():
@@ -115,7 +124,7 @@ class GpuMaskBackend:
         from . import lib as _lib, ops
 
         L = _lib.load()
-        out_dev, offs = self._crf.refine(page, [r for r, _, _ in jobs], masks, packed=True)
+        out_dev, offs = self._crf.refine(page, [r for r, _, _ in jobs], masks, packed=True)   # masks: host crops or one packed device tensor
         n = len(jobs)
         final = torch.zeros(2, H, W, dtype=torch.uint8, device=self.device)
         scratch = torch.empty((n + 1) * C.sizeof(_lib.MitDilateJob), dtype=torch.uint8, device=self.device)
@@ -134,8 +143,82 @@ class GpuMaskBackend:
                                           scratch.data_ptr() + n * C.sizeof(_lib.MitDilateJob), stream), "mit_mask_dilate_jobs")
         return final[1]
 
+    def assign_lines_device(self, mask_dev, textlines, keep_threshold: float):
+        """The component labelling and line assignment of complete_mask on the device (csrc/mask_assign.hip) for a u8 [H, W] device
+        mask, outlined in place.  Only the lines' rectangles (and a status word) come back: one asynchronous copy into pinned memory
+        and one stream wait.  Returns what ``_assign_components_native`` returns — (rects per line or None, crop(i, x, y, w, h),
+        crops(jobs)) with host arrays — and a fourth entry, packed(jobs) -> u8 device tensor with the crops back to back, the form
+        ``DenseCrfRefiner.refine`` takes as it is."""
+        import ctypes as C
+
+        import torch
+
+        from . import lib as _lib, ops
+
+        L = _lib.load()
+        if mask_dev.dtype != torch.uint8 or mask_dev.dim() != 2 or not mask_dev.is_cuda or not mask_dev.is_contiguous():
+            raise ValueError("assign_lines_device: a contiguous uint8 device mask [H, W] is required")
+        H, W = mask_dev.shape
+        M = len(textlines)
+        # one upload for the lines: polygons and font sizes (f64), then the boxes (i32)
+        par = np.empty(M * 9 * 8 + M * 16, dtype=np.uint8)
+        par[:M * 64].view(np.float64)[:] = np.asarray([np.asarray(t.pts, dtype=np.float64) for t in textlines], dtype=np.float64).reshape(-1)
+        par[M * 64:M * 72].view(np.float64)[:] = [float(t.font_size) for t in textlines]
+        par[M * 72:].view(np.int32)[:] = np.asarray([_xywh(t) for t in textlines], dtype=np.int32).reshape(-1)
+        par_dev = torch.from_numpy(par).to(self.device) if M else None
+        base = par_dev.data_ptr() if M else None
+        need = int(L.mit_mask_assign_workspace_bytes(H, W))
+        if need < 0:
+            raise ValueError(f"assign_lines_device: bad mask shape {H}x{W}")
+        if self._assign_ws is None or self._assign_ws.numel() < need:
+            self._assign_ws = None
+            self._assign_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._assign_ws
+        rects_dev = torch.empty(4 * M + 4, dtype=torch.int32, device=self.device)
+        stream = C.c_void_p(ops.current_stream())
+        _lib.check(L.mit_mask_assign_lines_dev(mask_dev.data_ptr(), H, W, base + M * 72 if M else None, base, base + M * 64 if M else None, M, 4,
+                                               float(keep_threshold), ws.data_ptr(), ws.numel(), rects_dev.data_ptr(), stream),
+                   "mit_mask_assign_lines_dev")
+        if self._rects_pinned is None or self._rects_pinned.numel() < rects_dev.numel():
+            self._rects_pinned = torch.empty(max(rects_dev.numel(), 1024), dtype=torch.int32).pin_memory()
+        host = self._rects_pinned[:rects_dev.numel()]
+        host.copy_(rects_dev, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        rects = host.numpy().copy()
+        self.device_assigns += 1
+        self.last_assign_status = [int(v) for v in rects[4 * M:]]   # components assigned, of more than 9 pixels, in all, 0
+
+        def packed(jobs):  # jobs: (line, x, y, w, h)
+            ja = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 5)
+            n = len(ja)
+            offs = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(ja[:, 3].astype(np.int64) * ja[:, 4], out=offs[1:])
+            if n and (ja[:, 3:] < 0).any():
+                raise ValueError("assign_lines_device: a crop job has a negative size")
+            total = int(offs[-1])
+            out = torch.empty(total, dtype=torch.uint8, device=self.device)
+            if total:
+                jb = np.empty(n * 8 + n * 20, dtype=np.uint8)   # offsets (i64) first: both stay aligned
+                jb[:n * 8].view(np.int64)[:] = offs[:n]
+                jb[n * 8:].view(np.int32)[:] = ja.reshape(-1)
+                jd = torch.from_numpy(jb).to(self.device)
+                _lib.check(L.mit_mask_line_crops_dev(ws.data_ptr(), ws.numel(), H, W, jd.data_ptr() + n * 8, jd.data_ptr(), n, total,
+                                                     out.data_ptr(), C.c_void_p(ops.current_stream())), "mit_mask_line_crops_dev")
+            return out, offs
+
+        def crops(jobs):
+            if not jobs:
+                return []
+            out, offs = packed(jobs)
+            flat = out.cpu().numpy()
+            return [flat[offs[j]:offs[j + 1]].reshape(int(jobs[j][4]), int(jobs[j][3])) for j in range(len(jobs))]
+
+        line_rects = [None if rects[4 * i] < 0 else [int(v) for v in rects[4 * i:4 * i + 4]] for i in range(M)]
+        return line_rects, (lambda i, x, y, w, h: crops([(i, x, y, w, h)])[0]), crops, packed
+
     def release_workspace(self):
         self._crf.release_workspace()
+        self._assign_ws = None
 
 
 _DEFAULT_BACKEND = None
@@ -309,14 +392,22 @@ def complete_mask(img: np.ndarray, mask: np.ndarray, textlines: Sequence[Quadril
     H, W = mask.shape
     if native is None:
         native = all(np.asarray(t.pts).shape == (4, 2) for t in textlines)
+    on_device = not isinstance(mask, np.ndarray)   # a device tensor (the GPU backend's resize_binarize made it)
+    if on_device and not (native and getattr(be, "gpu_assign", False)):
+        mask = mask.cpu().numpy()   # polygons other than quadrilaterals, or the host form asked for: the host routines
+        on_device = False
     if native:
-        # a device backend starts the page's bilateral filter now: it runs while the host labels and assigns the components
+        # a device backend starts the page's bilateral filter now: it runs while the components are labelled and assigned
         page = be.filter_page(img) if getattr(be, "gpu_tail", None) is not None else None
-        rects, _line_crop, _line_crops = _assign_components_native(mask, textlines, keep_threshold)
+        packed = None
+        if on_device:
+            rects, _line_crop, _line_crops, packed = be.assign_lines_device(mask, textlines, keep_threshold)
+        else:
+            rects, _line_crop, _line_crops = _assign_components_native(mask, textlines, keep_threshold)
         if not any(r is not None for r in rects):
             return None
         return _complete_mask_tail(be, img, mask, textlines, rects, _line_crop, _line_crops, dilation_offset, kernel_size, device_result,
-                                   page=page)
+                                   page=page, packed_crops=packed)
     boxes = [_xywh(t) for t in textlines]
     polys = [np.asarray(t.pts, dtype=np.float64) for t in textlines]
     areas2 = [HG_area(p) for p in polys]
@@ -382,11 +473,13 @@ def complete_mask(img: np.ndarray, mask: np.ndarray, textlines: Sequence[Quadril
                                kernel_size, device_result)
 
 
-def _complete_mask_tail(be, img, mask, textlines, rects, _line_crop, _line_crops, dilation_offset, kernel_size, device_result, page=None):
-    """complete_mask from the per-line rectangles on (:172-195): crop, DenseCRF, per-line dilation, union, closing dilation."""
+def _complete_mask_tail(be, img, mask, textlines, rects, _line_crop, _line_crops, dilation_offset, kernel_size, device_result, page=None,
+                        packed_crops=None):
+    """complete_mask from the per-line rectangles on (:172-195): crop, DenseCRF, per-line dilation, union, closing dilation.
+    ``packed_crops(jobs)``: the crops as one packed device tensor (device assignment); they then reach the DenseCRF without a host copy."""
     H, W = mask.shape
     M = len(textlines)
-    final = np.zeros_like(mask)
+    final = np.zeros((H, W), dtype=np.uint8)
     if page is None:
         page = be.filter_page(img)
     jobs = []  # (line index, crop rectangle, dilation size)
@@ -400,9 +493,11 @@ def _complete_mask_tail(be, img, mask, textlines, rects, _line_crop, _line_crops
         if w1 <= 0 or h1 <= 0 or x1 >= W or y1 >= H:   # an empty slice
             continue
         jobs.append((i, (x1, y1, w1, h1), dilate_size))
-    crops = _line_crops([(i, x, y, w, h) for i, (x, y, w, h), _ in jobs])
+    device_tail = getattr(be, "gpu_tail", False) and kernel_size % 2 == 1 and kernel_size <= 255 and all(k <= 255 for _, _, k in jobs)
+    crop_jobs = [(i, x, y, w, h) for i, (x, y, w, h), _ in jobs]
+    crops = packed_crops(crop_jobs)[0] if device_tail and packed_crops is not None else _line_crops(crop_jobs)
     # (the device dilation takes ellipse sizes up to 255 — a text size of ~830 px at the scaled page; anything larger stays on the host form)
-    if getattr(be, "gpu_tail", False) and kernel_size % 2 == 1 and kernel_size <= 255 and all(k <= 255 for _, _, k in jobs):
+    if device_tail:
         # device tail: the windows are the host form's own rectangles; inside a window every non-zero pixel of the line's component
         # image lies in its crop rectangle (the crop is the components' bounding box, extended), so the refined crop is all the
         # dilation has to read
@@ -473,8 +568,8 @@ def dispatch_sync(text_regions, raw_image: np.ndarray, raw_mask: np.ndarray, met
     size = (int(w * scale), int(h * scale))
     be = _backend_for(refine, bilateral, backend)
     img_small = be.resize_image(raw_image, size)  # a device tensor with the GPU backend: it never comes back to the host
-    if hasattr(be, "resize_binarize"):  # device backend: resize and "> 0 -> 255" there, one download
-        mask_small = be.resize_binarize(be._dev(raw_mask), size).cpu().numpy()
+    if hasattr(be, "resize_binarize"):  # device backend: resize and "> 0 -> 255" there; complete_mask labels it where it is
+        mask_small = be.resize_binarize(be._dev(raw_mask), size)
     else:
         mask_small = be.resize_mask(raw_mask, size).copy()
         mask_small[mask_small > 0] = 255
@@ -507,6 +602,6 @@ async def dispatch(text_regions, raw_image: np.ndarray, raw_mask: np.ndarray, me
 
 def dispatch_device(text_regions, page_dev, mask_dev, dilation_offset: int = 0, kernel_size: int = 3, backend=None):
     """``dispatch`` for a device-resident page (u8 [H,W,3]) and raw mask (u8 [H,W]); returns the refined mask on the device.  Only the
-    down-scaled raw mask (for the component labelling) and the per-line component crops cross PCIe."""
+    line rectangles cross PCIe (the components are labelled, assigned and cropped on the device: ``GpuMaskBackend.assign_lines_device``)."""
     return dispatch_sync(text_regions, page_dev, mask_dev, "fit_text", dilation_offset, 0, False, kernel_size, backend=backend or default_backend(),
                          device_result=True)

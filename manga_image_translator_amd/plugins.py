@@ -694,36 +694,50 @@ class HipLamaMPEInpainter(_InpBase):
             raise ValueError(f"bad shapes: image {image.shape}, mask {mask.shape}")
         if image.dtype != np.uint8 or mask.dtype != np.uint8:
             raise ValueError(f"expected uint8 page and mask, got {image.dtype} / {mask.dtype}")
-        from . import imgproc
-
-        height, width = image.shape[:2]
         dev = self.engine.device
         img0 = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]     # the page crosses PCIe once, as bytes
         msk0 = torch.from_numpy(np.ascontiguousarray(mask)).to(dev)[None]
-        img, msk = img0, msk0
-        rs = self._resize  # optional injected callable (img, (w, h), "keep_aspect" | "linear") -> ndarray: e.g. the real OpenCV
-        if max(height, width) > inpainting_size:                                # resize_keep_aspect = INTER_LINEAR_EXACT (:64-66)
-            dsize = imgproc.keep_aspect_size(height, width, inpainting_size)
-            img, msk = self._resized(img, dsize, "keep_aspect", rs), self._resized(msk, dsize, "keep_aspect", rs)
-        h, w = img.shape[1:3]
-        new_h, new_w = (h + 7) // 8 * 8, (w + 7) // 8 * 8                      # pad_size 8, by RESIZING (INTER_LINEAR, :67-79)
-        if (new_h, new_w) != (h, w):
-            img, msk = self._resized(img, (new_w, new_h), "linear", rs), self._resized(msk, (new_w, new_h), "linear", rs)
-        resized = (new_h, new_w) != (height, width)
-        out = self.engine.forward(img, msk, composite=not resized)  # resized: img_inpainted of :111, every pixel from the network
-        if resized:                                                             # back to the page size (:112-113)
-            out = self._resized(out, (width, height), "linear", rs)
-        # img_inpainted * mask_original + img_original * (1 - mask_original), mask_original = mask >= 127 (:57-61,116)
-        return imgproc.select_u8(msk0, 127, out, img0)[0].cpu().numpy()
+        # optional injected callable (img, (w, h), "keep_aspect" | "linear") -> ndarray: e.g. the real OpenCV
+        return inpaint_pages(self.engine, img0, msk0, inpainting_size, self._resize)[0].cpu().numpy()
 
     @staticmethod
     def _resized(t: torch.Tensor, dsize, mode: str, injected: Optional[Callable]) -> torch.Tensor:
-        """[1,H,W(,C)] u8 device tensor -> (w, h) = dsize: ``mit_resize_u8`` on the GPU, or the injected host callable."""
+        """[B,H,W(,C)] u8 device tensor -> (w, h) = dsize: ``mit_resize_u8`` on the GPU, or the injected host callable page by page."""
         from . import imgproc
 
         if injected is None:
             return imgproc.resize_u8(t, dsize, exact=(mode == "keep_aspect"))
-        return torch.from_numpy(np.ascontiguousarray(injected(t[0].cpu().numpy(), dsize, mode))).to(t.device)[None]
+        return torch.from_numpy(np.ascontiguousarray(np.stack([injected(x.cpu().numpy(), dsize, mode) for x in t]))).to(t.device)
+
+
+@torch.no_grad()
+def inpaint_pages(engine, img0: torch.Tensor, msk0: torch.Tensor, inpainting_size: int, resize: Optional[Callable] = None,
+                  micro_batch: int = 16) -> torch.Tensor:
+    """The resize / composite legs of LamaMPEInpainter._infer (inpainting_lama_mpe.py:56-118) around ``engine.forward`` for device
+    pages u8 [B,H,W,3] and masks u8 [B,H,W] of one size: what the plugin runs for its one page and the coupled batch engine for a
+    group — the same kernels in the same order, so a page's bytes do not depend on how many pages travel with it."""
+    from . import imgproc
+
+    B, height, width, _ = img0.shape
+    rs = HipLamaMPEInpainter._resized
+    out_all = torch.empty_like(img0)
+    for a in range(0, B, micro_batch):
+        i0, m0 = img0[a:a + micro_batch], msk0[a:a + micro_batch]
+        img, msk = i0, m0
+        if max(height, width) > inpainting_size:                                # resize_keep_aspect = INTER_LINEAR_EXACT (:64-66)
+            dsize = imgproc.keep_aspect_size(height, width, inpainting_size)
+            img, msk = rs(img, dsize, "keep_aspect", resize), rs(msk, dsize, "keep_aspect", resize)
+        h, w = img.shape[1:3]
+        new_h, new_w = (h + 7) // 8 * 8, (w + 7) // 8 * 8                      # pad_size 8, by RESIZING (INTER_LINEAR, :67-79)
+        if (new_h, new_w) != (h, w):
+            img, msk = rs(img, (new_w, new_h), "linear", resize), rs(msk, (new_w, new_h), "linear", resize)
+        resized = (new_h, new_w) != (height, width)
+        out = engine.forward(img, msk, composite=not resized)  # resized: img_inpainted of :111, every pixel from the network
+        if resized:                                                             # back to the page size (:112-113)
+            out = rs(out, (width, height), "linear", resize)
+        # img_inpainted * mask_original + img_original * (1 - mask_original), mask_original = mask >= 127 (:57-61,116)
+        out_all[a:a + micro_batch] = imgproc.select_u8(m0, 127, out, i0)
+    return out_all
 
 
 class HipLamaLargeInpainter(HipLamaMPEInpainter):

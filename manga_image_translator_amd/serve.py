@@ -92,6 +92,11 @@ class DenseStages:
     def __init__(self, params: Optional[dict] = None):
         self.params = dict(params or {})
         self._loaded = False
+        self._coupled = None
+        self.pages_batched = 0     # pages of translate_batch requests that went through one CoupledPageEngine.run with others
+        self.pages_looped = 0      # pages of translate_batch requests that took the page loop (translate); last_batch_plan says why
+        self.last_batch_plan: List[Tuple[List[int], str]] = []
+        self.last_coupled_seconds: List[Dict[str, float]] = []
 
     async def _load(self):
         if self._loaded:
@@ -132,6 +137,11 @@ class DenseStages:
         det = cfg.get("detector", {})
         tls, mask_raw, _ = await self.det.infer(page, int(det.get("detection_size", 1024)), float(det.get("text_threshold", 0.5)),
                                                 float(det.get("box_threshold", 0.7)), float(det.get("unclip_ratio", 2.3)))
+        raw_in = cfg.get("mask_raw")        # a request may bring the raw text mask ([H, W] uint8) instead of the detector's: unlike "mask"
+        if raw_in is not None:              # it goes through text-line merge + mask refinement
+            mask_raw = np.ascontiguousarray(np.asarray(raw_in, dtype=np.uint8))
+            if mask_raw.shape != (H, W):
+                raise ValueError(f"mask_raw must be {H}x{W} (got {mask_raw.shape})")
         lines_in = cfg.get("textlines")     # a request may bring its own text lines (quads [n,4,2]) instead of the detector's
         if lines_in is not None:
             from .textline import Quadrilateral
@@ -163,18 +173,123 @@ class DenseStages:
                 "mask_raw": np.asarray(mask_raw), "mask": np.asarray(mask), "inpainted": np.asarray(out), "device": self.device_name,
                 "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES")}
 
+    PER_PAGE_KEYS = ("textlines", "mask", "mask_raw")
+
+    @classmethod
+    def page_configs(cls, config, n: int) -> List[dict]:
+        """The config of each page of a batch request: the shared config with ``config["per_page"][i]`` (a dict of ``textlines`` /
+        ``mask`` / ``mask_raw``) laid over it."""
+        cfg = dict(_as_dict(config))
+        per_page = cfg.pop("per_page", None)
+        if per_page is None:
+            return [cfg] * n
+        if len(per_page) != n:
+            raise ValueError(f"per_page must have one entry per image ({len(per_page)} for {n} images)")
+        out = []
+        for i, pp in enumerate(per_page):
+            pp = dict(pp or {})
+            bad = sorted(set(pp) - set(cls.PER_PAGE_KEYS))
+            if bad:
+                raise ValueError(f"per_page[{i}]: only {', '.join(cls.PER_PAGE_KEYS)} may differ between the pages of a batch (got {', '.join(bad)})")
+            out.append({**cfg, **pp})
+        return out
+
+    @staticmethod
+    def plan_batches(shapes: Sequence[Tuple[int, int]], loop_reason: Sequence[Optional[str]], batch_size: int) -> List[Tuple[List[int], str]]:
+        """How a batch request is served: [(page indices, "" for one coupled run | the reason for the page loop)].  Pages of equal
+        (H, W) form a size group in request order, cut into runs of up to ``batch_size``; a run of one page, a page with a
+        ``loop_reason`` of its own and everything when ``batch_size <= 1`` take the loop."""
+        if batch_size <= 1:
+            return [([i], "batch_size <= 1") for i in range(len(shapes))]
+        plan, groups = [], {}
+        for i, (hw, why) in enumerate(zip(shapes, loop_reason)):
+            if why:
+                plan.append(([i], why))
+            else:
+                groups.setdefault(tuple(hw), []).append(i)
+        for idx in groups.values():
+            for a in range(0, len(idx), batch_size):
+                run = idx[a:a + batch_size]
+                plan.append((run, "" if len(run) > 1 else "alone in its size group"))
+        return sorted(plan, key=lambda e: e[0][0])
+
+    def _loop_reason(self, page: np.ndarray, cfg: dict) -> Optional[str]:
+        """Why a page cannot join a coupled run (None: it can)."""
+        from . import rearrange
+
+        if page.ndim != 3 or page.shape[2] != 3:
+            return "not HxWx3"
+        if rearrange.plan(page.shape[0], page.shape[1], 1024) is not None:
+            return "webtoon strip (rearranged detection)"
+        if int(_as_dict(cfg.get("ocr", {})).get("ignore_bubble", 0)):
+            return "ocr.ignore_bubble is not implemented by the coupled engine"
+        return None
+
+    def _coupled_engine(self):
+        from . import coupled
+
+        engines = (self.det.engine, self.ocr.engine, self.inp.engine)
+        if self._coupled is None or self._coupled[0] != tuple(id(e) for e in engines):
+            if self._coupled is not None:
+                self._coupled[1].close()
+            self._coupled = (tuple(id(e) for e in engines), coupled.CoupledPageEngine.from_engines(*engines, self.ocr.dictionary))
+        return self._coupled[1]
+
     async def translate_batch(self, images, config=None, batch_size: int = 1):
-        """``/simple_execute/translate_batch`` (server/instance.py:22-26 sends ``{"images", "config", "batch_size"}``): the pages of a
-        request one after the other through ``translate`` — the plugins are the reference's page-at-a-time interface; the batched engines
-        (pipeline.PageEngine, coupled.CoupledPageEngine) are what a batch job calls directly."""
-        return [await self.translate(im, config) for im in images]
+        """``/simple_execute/translate_batch`` (server/instance.py:22-26 sends ``{"images", "config", "batch_size"}``).  With
+        ``batch_size`` > 1 the pages of equal size are grouped, up to ``batch_size`` per group; each group is uploaded once and goes
+        through ONE ``CoupledPageEngine.run`` on the engines the loaded plugins own.  Results come back in request order, each the
+        dict ``translate`` returns for that page with ``config`` and its ``config["per_page"][i]`` overlay.  A page alone in its size
+        group, a webtoon strip and a request option the coupled engine does not implement take the page loop (``translate``), as
+        every page does with ``batch_size <= 1``; ``last_batch_plan`` and the ``pages_batched`` / ``pages_looped`` counters of
+        ``device_info`` say which way the pages went."""
+        import torch
+
+        await self._load()
+        images = list(images)
+        cfgs = self.page_configs(config, len(images))
+        pages = [np.ascontiguousarray(np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.uint8)) for im in images]
+        plan = self.plan_batches([p.shape[:2] for p in pages], [self._loop_reason(p, c) for p, c in zip(pages, cfgs)], int(batch_size))
+        self.last_batch_plan = plan
+        self.last_coupled_seconds = []      # CoupledResult.seconds of each coupled run of this request
+        results: List[Optional[dict]] = [None] * len(images)
+        for idx, why in plan:
+            if why:
+                for i in idx:
+                    results[i] = await self.translate(pages[i], cfgs[i])
+                self.pages_looped += len(idx)
+                continue
+            cfg = cfgs[idx[0]]      # everything but textlines / mask / mask_raw is shared by the pages of a request
+            ocr, inp = _as_dict(cfg.get("ocr", {})), _as_dict(cfg.get("inpainter", {}))
+            H, W = pages[idx[0]].shape[:2]
+            for i in idx:
+                m = cfgs[i].get("mask")
+                if m is not None and np.asarray(m).shape != (H, W):
+                    raise ValueError(f"mask must be {H}x{W} (got {np.asarray(m).shape})")
+            eng = self._coupled_engine()
+            pages_dev = torch.from_numpy(np.stack([pages[i] for i in idx])).to(eng.device)      # one upload per group
+            r = eng.run(pages_dev, max_seq_length=int(ocr.get("max_seq_length", 255)), suppress_eos=bool(ocr.get("suppress_eos", False)),
+                        prob_threshold=0.2 if ocr.get("prob") is None else float(ocr["prob"]),
+                        textlines=[cfgs[i].get("textlines") for i in idx], mask_raw=[cfgs[i].get("mask_raw") for i in idx],
+                        mask=[cfgs[i].get("mask") for i in idx], mask_dilation_offset=int(cfg.get("mask_dilation_offset", 20)),
+                        kernel_size=int(cfg.get("kernel_size", 3)), inpainting_size=int(inp.get("inpainting_size", 2048)))
+            self.last_coupled_seconds.append(dict(r.seconds))
+            mask_raw, mask, out = r.mask_raw.cpu().numpy(), r.mask.cpu().numpy(), r.inpainted.cpu().numpy()
+            for k, i in enumerate(idx):
+                results[i] = {"textlines": [{"pts": np.asarray(l.pts).tolist(), "text": l.text, "prob": float(l.prob),
+                                             "fg": [int(l.fg_r), int(l.fg_g), int(l.fg_b)], "bg": [int(l.bg_r), int(l.bg_g), int(l.bg_b)]}
+                                            for l in r.textlines[k]],
+                              "mask_raw": mask_raw[k], "mask": mask[k], "inpainted": out[k], "device": self.device_name,
+                              "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES")}
+            self.pages_batched += len(idx)
+        return results
 
     async def device_info(self, image=None, config=None):   # (the executor's send calls always carry both attributes)
         await self._load()
         import torch
 
         return {"device": self.device_name, "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES"), "n_visible": torch.cuda.device_count(),
-                "pid": os.getpid()}
+                "pid": os.getpid(), "pages_batched": self.pages_batched, "pages_looped": self.pages_looped}
 
 
 def _as_dict(config) -> dict:
