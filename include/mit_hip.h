@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 16
+#define MIT_ABI_VERSION 17
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -121,6 +121,18 @@ typedef struct MitConvGemm {
     const int32_t *lut_rows;
     const float *lut1, *lut2;
     int64_t lut_ld;
+    /* precision of THIS launch.  0: follow the GEMM mode (mit_gemm_mode_set) — fp32 results on the split-bf16 or fp32 MFMA tiles.
+     * 1: the one-product tiles ("p1"): both operands rounded to bf16 (round to nearest even, the rounding of tensor.to(torch.bfloat16))
+     * while they are staged, ONE bf16 MFMA product per 16-wide k-step, fp32 accumulation (k ascending) and the fp32 epilogue — what
+     * a convolution computes under torch.autocast(dtype=torch.bfloat16), the reference's GPU path of LaMa
+     * (inpainting_lama_mpe.py:106), WITHOUT the rounding of the layer output to bf16.  W is plane 0 of w_split.  Taken whatever the
+     * GEMM mode is and whatever the launch size (mit_gemm_split_min_tiles is ignored), identical bits on every p1 tile.  A launch
+     * that carries no w_split or misses the split tiles' preconditions (Cin % 16 == 0, <= 16 taps, 32-bit offsets) is refused: the
+     * caller asked for a precision, there is no silent fp32 fallback.  Any other value is refused.  (An explicit p1 tile index through
+     * mit_conv_gemm_cfg runs with nprod = 0 as well, like the test-only 3-pair tile: the tile decides; nprod = 1 with a tile that
+     * is not a p1 tile is refused.) */
+    int32_t nprod;
+    int32_t _pad1;
 } MitConvGemm;
 
 const char *mit_last_error(void);

@@ -257,7 +257,7 @@ class CoupledPageEngine:
     def run(self, pages_u8: torch.Tensor, max_seq_length: int = 255, suppress_eos: bool = False, prob_threshold: float = 0.2,
             inject=None, group: Optional[int] = 16, textlines: Optional[Sequence] = None, mask_raw: Optional[Sequence] = None,
             mask: Optional[Sequence] = None, mask_dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE,
-            inpainting_size: Optional[int] = None) -> CoupledResult:
+            inpainting_size: Optional[int] = None, precision: str = "fp32") -> CoupledResult:
         """``group``: pages per pipeline slot.  A batch larger than one group flows through three stage threads (detector + boxes +
         refine_mask | OCR | merge + mask refinement + LaMa), each working on a different group at a time, so the host phases of one
         group run while the kernels of its neighbours execute; every stage sees the groups in order and owns its engines, and each
@@ -267,7 +267,10 @@ class CoupledPageEngine:
         [n,4,2] that replace the detector's (the detector still runs, as in ``serve.DenseStages.translate``); ``mask_raw`` — u8 [H,W]
         that replaces the detector's refined mask ahead of merge + refinement; ``mask`` — the final mask, which skips merge +
         refinement.  ``inpainting_size``: the inpainter plugin's resize rule (``plugins.inpaint_pages``); None = the pages go to the
-        network as they are (H, W multiples of 8).  The defaults are the constants the benchmark path has always used."""
+        network as they are (H, W multiples of 8).  ``precision``: the inpainter's, "fp32" | "bf16" (``LamaEngine.forward``) —
+        a server passes its plugin's ``precision_for(config)``.  The defaults are the constants the benchmark path has always used."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"CoupledPageEngine.run: precision must be 'fp32' or 'bf16' (got {precision!r})")
         if pages_u8.dtype != torch.uint8 or pages_u8.dim() != 4 or pages_u8.shape[-1] != 3 or not pages_u8.is_cuda:
             raise ValueError(f"CoupledPageEngine.run expects a uint8 device tensor [B,H,W,3], got {pages_u8.dtype} {tuple(pages_u8.shape)}")
         B = pages_u8.shape[0]
@@ -275,7 +278,7 @@ class CoupledPageEngine:
             if v is not None and len(v) != B:
                 raise ValueError(f"CoupledPageEngine.run: {name} must have one entry per page ({len(v)} for {B} pages)")
         req = {"textlines": textlines, "mask_raw": mask_raw, "mask": mask, "offset": int(mask_dilation_offset), "kernel": int(kernel_size),
-               "inpainting_size": inpainting_size}
+               "inpainting_size": inpainting_size, "precision": precision}
         if group is not None and B > group:
             return self._run_pipelined(pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, int(group), req)
         sec = {}
@@ -290,7 +293,7 @@ class CoupledPageEngine:
         sec["textline_merge+mask_refinement"] = time.perf_counter() - t
         t = time.perf_counter()
         inpainted = torch.empty_like(pages_u8)
-        self._inpaint(pages_u8, final, inpainted, inpainting_size)
+        self._inpaint(pages_u8, final, inpainted, inpainting_size, precision)
         sec["inpaint (enqueue)"] = time.perf_counter() - t
         return CoupledResult(tl, regions, final, inpainted, sec, mraw)
 
@@ -314,15 +317,17 @@ class CoupledPageEngine:
                 mask_raw.mit_ready_event = torch.cuda.current_stream().record_event()
         return textlines, mask_raw
 
-    def _inpaint(self, pages_u8: torch.Tensor, mask: torch.Tensor, out: torch.Tensor, inpainting_size: Optional[int] = None):
+    def _inpaint(self, pages_u8: torch.Tensor, mask: torch.Tensor, out: torch.Tensor, inpainting_size: Optional[int] = None,
+                 precision: str = "fp32"):
         if inpainting_size is not None:   # the plugin's resize / composite legs around the network, for the whole group
             from . import plugins as P
 
-            out.copy_(P.inpaint_pages(self.lama, pages_u8, mask, int(inpainting_size), None, self.lama_mb))
+            out.copy_(P.inpaint_pages(self.lama, pages_u8, mask, int(inpainting_size), None, self.lama_mb, precision=precision))
             return
+        kw = {} if precision == "fp32" else {"precision": precision}
         for i in range(0, pages_u8.shape[0], self.lama_mb):
             j = min(pages_u8.shape[0], i + self.lama_mb)
-            out[i:j].copy_(self.lama.forward(pages_u8[i:j], mask[i:j]))
+            out[i:j].copy_(self.lama.forward(pages_u8[i:j], mask[i:j], **kw))
 
     def _run_pipelined(self, pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, group, req) -> CoupledResult:
         B, H, W, _ = pages_u8.shape
@@ -369,7 +374,7 @@ class CoupledPageEngine:
             with torch.cuda.stream(st["tail"]):
                 mask[a:b] = m
                 mask_raw_all[a:b] = mraw
-            timed("inpaint (enqueue)", self._inpaint, pages_u8[a:b], mask[a:b], inpainted[a:b], req["inpainting_size"])
+            timed("inpaint (enqueue)", self._inpaint, pages_u8[a:b], mask[a:b], inpainted[a:b], req["inpainting_size"], req["precision"])
             return tl, regions
 
         with cf.ThreadPoolExecutor(1, "mit-st-det") as e1, cf.ThreadPoolExecutor(1, "mit-st-ocr") as e2, cf.ThreadPoolExecutor(1, "mit-st-tail") as e3:

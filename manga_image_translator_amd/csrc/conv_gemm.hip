@@ -66,14 +66,14 @@ bool buf_eligible(const MitConvGemm &p) {
     if (maxoff * 4 >= 0x80000000LL) return false;
     return (int64_t)3 * (p.Kw >> 3) * p.ldw * 16 < 0x80000000LL;
 }
-// the buffer-load twin of a shipped p6 tile ("...p6o" -> "...p6u"), or the tile itself
+// the buffer-load twin of a shipped p6 / p1 tile ("...p6o" -> "...p6u"), or the tile itself
 int buf_twin(int c) {
     static const std::vector<int> twin = [] {
         std::vector<int> t(kNumCfgs);
         for (int i = 0; i < kNumCfgs; ++i) {
             t[i] = i;
             const std::string n = kCfgs[i].name;
-            if (n.size() > 3 && n.compare(n.size() - 3, 3, "p6o") == 0) {
+            if (n.size() > 3 && (n.compare(n.size() - 3, 3, "p6o") == 0 || n.compare(n.size() - 3, 3, "p1o") == 0)) {
                 const int u = cfg_by_name((n.substr(0, n.size() - 1) + "u").c_str());
                 if (u >= 0) t[i] = u;
             }
@@ -110,7 +110,28 @@ int gemm_mode_now() {
 std::atomic<long long> g_split_min{0};
 int64_t split_min_now() { return g_split_min.load(std::memory_order_relaxed); }
 
+// MitConvGemm.nprod == 1: the one-product tiles, whatever the GEMM mode and the launch size (the caller checked split_eligible(p, 16)).
+// The choice follows the p6 one — narrow / 192-column / wide by N, 64 x 64 for under-filled launches — and every p1 tile gives the same
+// bits, so a result depends neither on it nor on how many pages share the launch.  Measured on LaMa's shapes only (N = 128 / 256 / 512
+// wide, 64 narrow, 192 / 384 on the 192-column tile: profiles/r17a_lama_precision.json); outside them the choice is UNMEASURED — the
+// 192-column tile for every N % 192 == 0, and no N <= 32 form (such a launch runs the 64-column tile with half its columns padded).
+int pick_cfg_p1(const MitConvGemm &p, int64_t M) {
+    static const int wide = cfg_by_name("split128x128x32p1o"), narrow = cfg_by_name("split128x64x32p1o"), t192 = cfg_by_name("split128x192x32p1o");
+    static const int small = cfg_by_name("split64x64x32p1o"), k16 = cfg_by_name("split64x64x16p1o");
+    int c;
+    if (!split_eligible(p, 32)) {
+        c = k16;  // Cin % 32 != 0
+    } else {
+        const int r = p.N % 128;
+        c = (p.N <= 64 || (r != 0 && r <= 64)) ? narrow : wide;
+        if (p.N % 192 == 0) c = t192;
+        if (p.Z == 1 && ((M + 127) / 128) * ((p.N + 63) / 64) < 768) c = small;
+    }
+    return buf_eligible(p) ? buf_twin(c) : c;
+}
+
 int pick_cfg(const MitConvGemm &p, int64_t M) {
+    if (p.nprod == 1) return pick_cfg_p1(p, M);
     // measured on MI355X (scripts/bench_conv.py)
     static const int wide = cfg_by_name("fast128x128x16w4c"), narrow = cfg_by_name("fast128x64x16w5c"), m192 = cfg_by_name("fast192x64x16w4c");
     static const int kCfgGemv16 = cfg_by_name("gemv16"), kCfgGemv4 = cfg_by_name("gemv4"), kCfgGemv16N1 = cfg_by_name("gemv16n1"), kCfgGemv4N1 = cfg_by_name("gemv4n1");
@@ -309,12 +330,14 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
         if (p.lut_ld > 0x7fff) return mit_set_error("mit_conv_gemm: lut_ld too large (row offsets are 16-bit row x lut_ld in 32 bits)");
     }
     if (p.Z > 65535) return mit_set_error("mit_conv_gemm: Z too large");
+    if (p.nprod != 0 && p.nprod != 1) return mit_set_error("mit_conv_gemm: nprod must be 0 (the GEMM mode) or 1 (one bf16 product) (got %d)", p.nprod);
+    if (p.nprod == 1 && !p.w_split) return mit_set_error("mit_conv_gemm: nprod = 1 needs w_split (mit_gemm_split_pack): there is no fp32 fallback for a requested precision");
     // The fast kernels index A with 32-bit element offsets.  A batch whose activations exceed 2^31 elements (16 pages of
     // 2048 x 1456 x 64: LaMa's first stride-2 conv) is cut into runs of whole images that fit, instead of falling to the generic kernel.
     // Round 6: in the split mode the runs are cut to what the buffer-load tiles address (2^31 BYTES per run: buf_eligible) when one
     // image fits that — every run is still thousands of workgroups, and each takes the "u" tile instead of its "o" twin.
     bool want_buf = false;
-    if (cfg < 0 && p.Z == 1 && p.NB > 1 && gemm_mode_now() == 6 && p.w_split != nullptr && split_eligible(p, 16)) {
+    if (cfg < 0 && p.Z == 1 && p.NB > 1 && (gemm_mode_now() == 6 || p.nprod == 1) && p.w_split != nullptr && split_eligible(p, 16)) {
         MitConvGemm one = p;
         one.NB = 1;
         want_buf = buf_eligible(one);
@@ -344,6 +367,11 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
             }
             return 0;
         }
+    }
+    if (p.nprod == 1) {  // (after the cut into runs above: a batch past 2^31 elements is eligible run by run)
+        if (!split_eligible(p, 16))
+            return mit_set_error("mit_conv_gemm: nprod = 1 needs the split tiles' preconditions (Cin %% 16 == 0, <= %d taps, 32-bit element offsets, 16-byte aligned w_split with w_zs1 == 0 and Kw %% 8 == 0): there is no fp32 fallback for a requested precision", FAST_MAX_TAPS);
+        if (cfg >= 0 && cfg < kNumCfgs && !strstr(kCfgs[cfg].name, "p1")) return mit_set_error("mit_conv_gemm: nprod = 1 with tile %s, which is not a one-product tile", kCfgs[cfg].name);
     }
     if (cfg < 0) cfg = pick_cfg(p, M64);
     if (cfg >= kNumCfgs) return mit_set_error("mit_conv_gemm: bad cfg %d", cfg);

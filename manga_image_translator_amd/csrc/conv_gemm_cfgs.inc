@@ -55,3 +55,15 @@ X(3, "split128x128x16p6", 4, 128, 128, 16, launch_split, 2, 2, 2, 6, 0)
 X(3, "split128x128x16p9", 4, 128, 128, 16, launch_split, 2, 2, 2, 9, 0)
 X(3, "split128x128x16p3", 4, 128, 128, 16, launch_split, 2, 2, 2, 3, 0)     // 16-bit-significand products (tests only)
 X(3, "split128x64x16p6", 4, 128, 64, 16, launch_split, 2, 2, 2, 6, 0)
+// ---- "p1" (MitConvGemm.nprod = 1, conv_gemm_split.h): ONE product of the bf16 roundings of both operands, fp32 accumulation — the opt-in
+// bf16 precision (LaMa's precision="bf16"), never a GEMM mode.  K-tile 32; "o" / "u" as above.  All of them give the same bits.
+X(6, "split128x128x32p1o", 4, 128, 128, 32, launch_split, 2, 2, 3, 1, 385)   // wide
+X(6, "split128x128x32p1u", 4, 128, 128, 32, launch_split, 2, 2, 3, 1, 2433)
+X(6, "split128x64x32p1o", 4, 128, 64, 32, launch_split, 2, 2, 3, 1, 385)     // narrow (N <= 64 or N % 128 <= 64)
+X(6, "split128x64x32p1u", 4, 128, 64, 32, launch_split, 2, 2, 3, 1, 2433)
+X(6, "split128x192x32p1o", 4, 128, 192, 32, launch_split, 4, 1, 2, 1, 385)   // N = 192 / 384 (LaMa spectral convs): wave tile 32 x 192
+X(6, "split128x192x32p1u", 4, 128, 192, 32, launch_split, 4, 1, 2, 1, 2433)
+X(6, "split64x64x32p1o", 4, 64, 64, 32, launch_split, 2, 2, 4, 1, 385)       // under-filled launches
+X(6, "split64x64x32p1u", 4, 64, 64, 32, launch_split, 2, 2, 4, 1, 2433)
+X(6, "split64x64x16p1o", 4, 64, 64, 16, launch_split, 2, 2, 4, 1, 385)       // Cin % 32 != 0 (a K-tile must lie inside one tap)
+X(6, "split64x64x16p1u", 4, 64, 64, 16, launch_split, 2, 2, 4, 1, 2433)

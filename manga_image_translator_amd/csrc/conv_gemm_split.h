@@ -1,7 +1,7 @@
 // conv_gemm_split.h — the split-bf16 tiles of mit_conv_gemm (GEMM mode 6, the default, and 9: mit_gemm_mode_set / MIT_GEMM_SPLIT): kernel,
 // weight packer and launcher.  No kernel here may spill to scratch memory (check .amdhsa_private_segment_fixed_size after changes).
 // Included at the end of conv_gemm_kernels.h (it shares that header's epilogue, RowOff and launch conventions); instantiated by
-// conv_gemm_inst2 .. 5.hip through conv_gemm_cfgs.inc.
+// conv_gemm_inst2 .. 6.hip through conv_gemm_cfgs.inc.
 #pragma once
 #include "bf16_split.h"
 
@@ -22,6 +22,13 @@ namespace mitcg {
 // the residual x - Inf is -Inf / NaN, so such an operand yields NaN here where the fp32 MFMA yields Inf or a finite value.  Activations
 // and weights of the networks on this path are many orders of magnitude inside the range.
 // (plane pairs kSplitPA / kSplitPB, smallest products first; NPROD takes the last NPROD entries: bf16_split.h)
+//
+// NPROD = 1 ("p1", MitConvGemm.nprod = 1): the one product hi(a) * hi(w), i.e. both operands rounded to bf16 (round to nearest even, what
+// tensor.to(torch.bfloat16) does) and accumulated in fp32 — a bf16 autocast convolution without the rounding of its output.  Not a parity
+// mode: a precision the caller asks for per launch.  One plane per operand: A is converted with pack_bf16 only (no residuals), W is plane 0
+// of the same w_split cells, LDS holds a third of a p6 tile.  Its tiles take a K-tile of 32 (two MFMA steps per barrier: with one product
+// a 16-wide K-tile would leave 4 MFMAs between two barriers); the 16-wide form exists for layers whose Cin is not a multiple of 32.
+// Every p1 tile issues, per output element, one MFMA per 16-wide k-step with k ascending: a result does not depend on the tile.
 
 // A cells are row-swizzled per k slab (row ^ kh * 64 / BK) instead of padded.  ds_write_b64 is served in groups of 16 consecutive lanes
 // over 32 four-byte banks (MI355X_MICROARCH.md, LDS table): a group's 16 eight-byte halves — 16 / KQ rows x all KH slabs x 2 halves —
@@ -43,7 +50,8 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     constexpr int TN = WN / 32;
     static_assert(WAVES_M * WAVES_N == 4 && TM >= 1 && TN >= 1, "wave tile");
     static_assert(BK == 16 || BK == 32, "K-tile of one or two bf16 MFMA steps");
-    static_assert(NPROD == 3 || NPROD == 6 || NPROD == 9, "plane pairs");
+    static_assert(NPROD == 1 || NPROD == 3 || NPROD == 6 || NPROD == 9, "plane pairs");
+    constexpr int NPL = NPROD == 1 ? 1 : 3;  // planes per operand held in LDS
     constexpr int KH = BK / 8;   // 16-byte cells along k
     constexpr int KS = BK / 16;  // MFMA steps per K-tile
     constexpr int KQ = BK / 4;   // float4 chunks along k of the fp32 A tile
@@ -63,14 +71,14 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     constexpr bool BUF = (VAR & 2048) != 0;
     static_assert((VAR & ~(1 | 128 | 256 | 2048)) == 0, "VAR bits");
     constexpr int SA = BM, SB = BN;
-    constexpr int A_TILE = 3 * KH * SA, B_TILE = 3 * KH * SB;  // cells per buffer
+    constexpr int A_TILE = NPL * KH * SA, B_TILE = NPL * KH * SB;  // cells per buffer
     constexpr int B_CPP = KH * BN;                             // W cells per plane per K-tile
-    constexpr int B_CELLS = 3 * B_CPP;
+    constexpr int B_CELLS = NPL * B_CPP;
     constexpr int B_ITERS = (B_CELLS + 255) / 256;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    u32x4 *As = reinterpret_cast<u32x4 *>(smem);  // [2][3][KH][SA]
-    u32x4 *Bs = As + 2 * A_TILE;                  // [2][3][KH][SB]
+    u32x4 *As = reinterpret_cast<u32x4 *>(smem);  // [2][NPL][KH][SA]
+    u32x4 *Bs = As + 2 * A_TILE;                  // [2][NPL][KH][SB]
     int *rowtab = reinterpret_cast<int *>(Bs + 2 * B_TILE);  // [ntaps][BM]
 
     const int tid = threadIdx.x;
@@ -189,7 +197,12 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             const int ml = (am + i * A_MSTEP) ^ split_swz<BK>(kh);
             u32x2 h, m, l;
             const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            split3(!BUF && a_off[i] < 0 ? zero : a_reg[i], h, m, l);
+            const f32x4 v = !BUF && a_off[i] < 0 ? zero : a_reg[i];
+            if (NPL == 1) {
+                as2[(kh * SA + ml) * 2 + half] = u32x2{pack_bf16(v.x, v.y), pack_bf16(v.z, v.w)};
+                continue;
+            }
+            split3(v, h, m, l);
             as2[((0 * KH + kh) * SA + ml) * 2 + half] = h;
             as2[((1 * KH + kh) * SA + ml) * 2 + half] = m;
             as2[((2 * KH + kh) * SA + ml) * 2 + half] = l;
@@ -207,15 +220,15 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
 
     // The staging of one tile as a sequence of small steps (PIPE): per A chunk three (pack a plane, write it, form the residual), one
     // per W cell write, then the loads of the following tile (row offsets, A chunks, W cells).
-    constexpr int STAGE_WRITE_STEPS = 3 * A_ITERS + B_ITERS, STAGE_STEPS = STAGE_WRITE_STEPS + 1 + A_ITERS + B_ITERS;
+    constexpr int STAGE_WRITE_STEPS = NPL * A_ITERS + B_ITERS, STAGE_STEPS = STAGE_WRITE_STEPS + 1 + A_ITERS + B_ITERS;
     auto stage_step = [&](const int st, const int buf, const bool with_loads) {
-        if (ORD && st == 3 * (A_ITERS - 1) + 1 && with_loads) {  // the last use of the current offsets (the zero mask of the last chunk) is behind:
+        if (ORD && st == NPL * (A_ITERS - 1) + 1 && with_loads) {  // the last use of the current offsets (the zero mask of the last chunk) is behind:
             const int *rt = rowtab + ld_tap * BM + am;            // the next tile's take their registers, ahead of most of this tile's LDS writes
 #pragma unroll
             for (int i = 0; i < A_ITERS; ++i) a_off[i] = rt[i * A_MSTEP];
         }
-        if (st < 3 * A_ITERS) {
-            const int i = st / 3, ph = st % 3;
+        if (st < NPL * A_ITERS) {
+            const int i = st / NPL, ph = st % NPL;
             const int kh = aq >> 1, half = aq & 1;
             // one index register for every chunk and plane: the swizzle only touches row bits below A_MSTEP, so chunk i sits
             // i * A_MSTEP rows (an immediate) behind chunk 0
@@ -231,14 +244,14 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             }
             const u32x2 pk = {pack_bf16(r.x, r.y), pack_bf16(r.z, r.w)};
             reinterpret_cast<u32x2 *>(As + buf * A_TILE)[((ph * KH + kh) * SA + ml) * 2 + half] = pk;
-            if (ph < 2) {
+            if (ph < NPL - 1) {
                 r.x = r.x - bf16_lo(pk.x);
                 r.y = r.y - bf16_hi(pk.x);
                 r.z = r.z - bf16_lo(pk.y);
                 r.w = r.w - bf16_hi(pk.y);
             }
         } else if (st < STAGE_WRITE_STEPS) {
-            const int j = st - 3 * A_ITERS;
+            const int j = st - NPL * A_ITERS;
             if ((j + 1) * 256 <= B_CELLS || tid + j * 256 < B_CELLS) (Bs + buf * B_TILE)[bdst(j)] = b_reg[j];
         } else if (st == STAGE_WRITE_STEPS) {
             if (!ORD) {
@@ -264,7 +277,7 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
         }
     };
 
-    bf16x8 af[KS][3][TM], bf[KS][3][TN];
+    bf16x8 af[KS][NPL][TM], bf[KS][NPL][TN];
     // One K-tile: fragment reads, then (PIPE) the staging of tile kt + 1 and the loads of tile kt + 2 placed among the MFMAs, or (plain)
     // the MFMAs and then the staging of tile kt + 1, loaded at the top of the iteration.
     auto tile = [&](const int kt, auto do_store, auto do_load) {
@@ -276,9 +289,9 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-            for (int o = 0; o < 3; ++o) {
-                const int pa = ORD ? (o == 0 ? 0 : 3 - o) : o;  // consumption order of the pairs: A planes 0, 2, 1 with W planes 2, 0, 1
-                const int pb = ORD ? (o == 0 ? 2 : o - 1) : o;
+            for (int o = 0; o < NPL; ++o) {
+                const int pa = ORD && NPL == 3 ? (o == 0 ? 0 : 3 - o) : o;  // consumption order of the pairs: A planes 0, 2, 1 with W planes 2, 0, 1
+                const int pb = ORD && NPL == 3 ? (o == 0 ? 2 : o - 1) : o;
 #pragma unroll
                 for (int mi = 0; mi < TM; ++mi)
                     af[ks][pa][mi] = __builtin_bit_cast(bf16x8, as[(pa * KH + 2 * ks + lh) * SA + ((wm0 + mi * 32 + li) ^ split_swz<BK>(2 * ks + lh))]);
@@ -380,7 +393,8 @@ template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD,
 void launch_split(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {
     constexpr int KH = BK / 8;
     constexpr int SA = BM, SB = BN;
-    size_t staging = (size_t)(2 * 3 * KH * SA + 2 * 3 * KH * SB) * 16 + (size_t)p.ntaps * BM * sizeof(int);
+    constexpr int NPL = NPROD == 1 ? 1 : 3;
+    size_t staging = (size_t)(2 * NPL * KH * SA + 2 * NPL * KH * SB) * 16 + (size_t)p.ntaps * BM * sizeof(int);
     size_t rows = ((size_t)BM * sizeof(RowOff) + 15) / 16 * 16 + (size_t)4 * 32 * EPI_PITCH * sizeof(float) + (size_t)BM * sizeof(LutOff);
     size_t smem = staging > rows ? staging : rows;
     auto kern = conv_gemm_split_kernel<BM, BN, BK, WAVES_M, WAVES_N, MINW, NPROD, VAR>;

@@ -185,6 +185,11 @@ class _FFC:
     def __init__(self, sd, p, device, winograd=True):
         w_l = torch.cat([sd[p + ".ffc.convl2l.weight"], sd[p + ".ffc.convg2l.weight"]], dim=1)  # [128, 512, 3, 3]
         self.winograd = winograd
+        self._direct = None
+        # what direct() needs and nothing else of the state dict: the three 3x3 weights and bn_l, as the checkpoint's own tensors (no
+        # copy; the rest of the checkpoint can be freed by its owner).  Dropped once direct() has packed them.
+        self._direct_src = (sd[p + ".ffc.convl2l.weight"], sd[p + ".ffc.convg2l.weight"], sd[p + ".ffc.convl2g.weight"],
+                            _bn(sd, p + ".bn_l"), device) if winograd else None
         if winograd:  # F(4x4, 3x3): both convs read the same transformed input (convl2g its first 128 channels)
             self.to_l = ops.WinogradConv3x3(w_l, None, pad_mode=PAD_REFLECT, bn=_bn(sd, p + ".bn_l"), act=ACT_RELU, device=device)
             self.l2g = ops.WinogradConv3x3(sd[p + ".ffc.convl2g.weight"], None, pad_mode=PAD_REFLECT, device=device)
@@ -204,6 +209,20 @@ class _FFC:
         self.fu_scale, self.fu_bias = sc.to(device), bi.to(device)
         # conv2 (192->384) carries the global branch's BN + ReLU (+ pre = convl2g(x_l), + residual)
         self.st_out = ops.Conv2d(sd[st + ".conv2.weight"], None, bn=_bn(sd, p + ".bn_g"), act=ACT_RELU, device=device)
+
+    def direct(self):
+        """(to_l, l2g) in the direct 9-tap form.  Built on the first call of a Winograd engine's bf16 precision (F(4x4, 3x3) with bf16
+        operands has 9x the rms error of the direct form with bf16 operands), so an fp32-only user never packs them; until
+        then a block keeps references to its three 3x3 checkpoint weights on the host (3.4 MB a block)."""
+        if not self.winograd:
+            return self.to_l, self.l2g
+        if self._direct is None:
+            w_l2l, w_g2l, w_l2g, bn_l, device = self._direct_src
+            self._direct = (ops.Conv2d(torch.cat([w_l2l, w_g2l], dim=1), None, padding=1, pad_mode=PAD_REFLECT, bn=bn_l, act=ACT_RELU,
+                                       device=device),
+                            ops.Conv2d(w_l2g, None, padding=1, pad_mode=PAD_REFLECT, device=device))
+            self._direct_src = None
+        return self._direct
 
 
 class LamaEngine:
@@ -315,8 +334,11 @@ class LamaEngine:
         if self._dbg is not None and name not in self._dbg:
             self._dbg[name] = t.clone()
 
-    def _fourier_unit(self, ffc: _FFC, t1: torch.Tensor, t2: torch.Tensor):
-        """t2 = t1 + irfft2(relu(bn(conv1x1(rfft2(t1)))))   (x + fu(x), :305)."""
+    def _fourier_unit(self, ffc: _FFC, t1: torch.Tensor, t2: torch.Tensor, nprod: int = 0):
+        """t2 = t1 + irfft2(relu(bn(conv1x1(rfft2(t1)))))   (x + fu(x), :305).  ``nprod`` = 1: the spectral 1x1 convolution on the
+        one-product bf16 tiles; the transforms stay fp32 (the reference casts to fp32 around rfftn / irfftn under autocast, :225-226)."""
+        if nprod:
+            ops.ensure_split(ffc.fu_w)
         B, h, w, Cc = t1.shape
         wk = w // 2 + 1
         plane = h * wk * Cc
@@ -369,7 +391,7 @@ class LamaEngine:
         launch_conv_gemm(conv_gemm_desc(
             a=Zf, NB=B, Hi=h, Wi=wk, Cin=Cc, a_strides=(2 * plane, wk * Cc, Cc), Ho=h, Wo=wk, sy=1, sx=1,
             taps=[(0, 0, 0), (0, 0, plane)], pad_mode=PAD_ZERO, w=ffc.fu_w, ldw=ffc.fu_Np, Kw=ffc.fu_Kp, Nw=ffc.fu_Np,
-            N=2 * Cc, c=cm, scale=ffc.fu_scale, bias=ffc.fu_bias, act=ACT_RELU))
+            N=2 * Cc, c=cm, scale=ffc.fu_scale, bias=ffc.fu_bias, act=ACT_RELU, nprod=nprod))
         self._dbg_put("fu3_spectral_conv", Z2)
         # S3: inverse complex DFT along H.  U[b,h,t] rows (t,h) = G2i @ Z2[b]
         if use_fft:
@@ -399,14 +421,19 @@ class LamaEngine:
             pad_mode=PAD_ZERO, w=U, ldw=Cc, Kw=2 * wk, Nw=Cc, N=Cc, c=cm, post=pm, Z=B * h, zdiv=1 << 30,
             w_zs=(0, 2 * wk * Cc)))
 
-    def _ffc(self, ffc: _FFC, x: torch.Tensor, out: torch.Tensor, residual: Optional[torch.Tensor]):
-        """FFC_BN_ACT.forward (:395-399 over :349-369) on the fused [B,h,w,512] state."""
+    def _ffc(self, ffc: _FFC, x: torch.Tensor, out: torch.Tensor, residual: Optional[torch.Tensor], nprod: int = 0):
+        """FFC_BN_ACT.forward (:395-399 over :349-369) on the fused [B,h,w,512] state.  ``nprod`` = 1 (precision "bf16"): every
+        convolution on the one-product bf16 tiles, the 3x3s in the direct 9-tap form."""
         B, h, w, _ = x.shape
         x_l, x_g = x[..., :LOCAL_C], x[..., LOCAL_C:]
         res_l = None if residual is None else residual[..., :LOCAL_C]
         res_g = None if residual is None else residual[..., LOCAL_C:]
         P = self._buf("ffc_P", B, h, w, GLOBAL_C)
-        if ffc.winograd:
+        if nprod:
+            to_l, l2g = ffc.direct()
+            to_l(x, out=out[..., :LOCAL_C], post=res_l, nprod=nprod)
+            l2g(x_l, out=P, nprod=nprod)
+        elif ffc.winograd:
             T = ops.WinogradConv3x3.tiles(B, h, w)
             V = self._buf("wino_v", 36, T, LOCAL_C + GLOBAL_C)
             ffc.to_l.transform_input(x, V)
@@ -422,20 +449,31 @@ class LamaEngine:
             ffc.l2g(x_l, out=P)  # convl2g(x_l), raw
         t1 = self._buf("ffc_t1", B, h, w, SPEC_C)
         t2 = self._buf("ffc_t2", B, h, w, SPEC_C)
-        ffc.st_in(x_g, out=t1)  # SpectralTransform.conv1 (:272-277)
+        ffc.st_in(x_g, out=t1, nprod=nprod)  # SpectralTransform.conv1 (:272-277)
         self._dbg_put("s1_st_in", t1)
-        self._fourier_unit(ffc, t1, t2)
+        self._fourier_unit(ffc, t1, t2, nprod)
         self._dbg_put("fu5_irfft_rows_plus_t1", t2)
-        ffc.st_out(t2, out=out[..., LOCAL_C:], pre=P, post=res_g)
+        ffc.st_out(t2, out=out[..., LOCAL_C:], pre=P, post=res_g, nprod=nprod)
         self._dbg_put("s2_out_global", out[..., LOCAL_C:])  # conv2(x + fu(x)) + convl2g -> bn_g -> relu (+ id_g)
 
     # -- full generator ------------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, taps: Optional[dict] = None, composite: bool = True) -> torch.Tensor:
+    def forward(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, taps: Optional[dict] = None, composite: bool = True,
+                precision: str = "fp32") -> torch.Tensor:
         """LamaFourier.__call__ (:713-726) + the tensor pre/post of _infer (:82-117) for pages whose
         H, W are multiples of 8.  img_u8 [B,H,W,3] u8, mask_u8 [B,H,W] u8 (device) -> u8 [B,H,W,3].
         ``composite=False`` returns ``img_inpainted`` of :111 (the network's bytes everywhere) instead of the final composite
-        of :117 — the plugin resizes that back to the page size first when the page was resized (:112-117)."""
+        of :117 — the plugin resizes that back to the page size first when the page was resized (:112-117).
+
+        ``precision``: "fp32" (default; the reference's CPU path, :93-95) or "bf16" — the reference's GPU path, which runs the model
+        under torch.autocast(dtype=bfloat16) (:97-107).  In "bf16" the stride-2 convolutions, the FFC blocks' 3x3 (direct form) and
+        1x1 convolutions, the spectral convolution and the three up-convolutions round both operands to bf16 and accumulate in fp32
+        (MitConvGemm.nprod = 1).  Activations stay fp32 between layers (no rounding of layer outputs, which autocast adds), the FFTs
+        stay fp32 as in the reference (:225-226, 247-248), and so do the 7x7 stem and the 7x7 output convolution.  Per call: an
+        fp32 call after a bf16 one gives the bytes it gave before."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"LamaEngine.forward: precision must be 'fp32' or 'bf16' (got {precision!r})")
+        nprod = 1 if precision == "bf16" else 0
         if img_u8.dtype != torch.uint8 or mask_u8.dtype != torch.uint8:
             raise TypeError("LamaEngine.forward expects uint8 page and mask tensors")
         if img_u8.dim() != 4 or img_u8.shape[-1] != 3 or tuple(mask_u8.shape) != tuple(img_u8.shape[:3]):
@@ -483,34 +521,34 @@ class LamaEngine:
         if taps is not None:
             taps["stem"] = s64.clone()
         d1 = self._buf("d1", B, H // 2, W // 2, 128)
-        self.down1(s64, out=d1)
+        self.down1(s64, out=d1, nprod=nprod)
         d2 = self._buf("d2", B, H // 4, W // 4, 256)
-        self.down2(d1, out=d2)
+        self.down2(d1, out=d2, nprod=nprod)
         h, w = H // 8, W // 8
         X = self._buf("X", B, h, w, 512)
         T = self._buf("Xtmp", B, h, w, 512)
-        self.down3(d2, out=X)
+        self.down3(d2, out=X, nprod=nprod)
         if taps is not None:
             taps["down"] = X.clone()
         for i, (c1, c2) in enumerate(self.blocks):  # FFCResnetBlock.forward :421-436
-            self._ffc(c1, X, T, None)
-            self._ffc(c2, T, X, X)  # in place: each element reads its own residual before it is overwritten
+            self._ffc(c1, X, T, None, nprod)
+            self._ffc(c2, T, X, X, nprod)  # in place: each element reads its own residual before it is overwritten
             if taps is not None:
                 taps[f"block{i}"] = X.clone()
         u1 = self._buf("d2", B, H // 4, W // 4, 256)
-        self.ups[0](X, out=u1)
+        self.ups[0](X, out=u1, nprod=nprod)
         u2 = self._buf("d1", B, H // 2, W // 2, 128)
-        self.ups[1](u1, out=u2)
+        self.ups[1](u1, out=u2, nprod=nprod)
         pred = self._buf("pred", B, H, W, 3)
         if self.planar_tail:   # the last up-convolution writes 64 / P planes of P channels, the 7x7 output convolution reads them slice by slice
             P = self.planar_tail
             pm = P == 4 and H % 2 == 0 and W % 2 == 0   # 4-channel planes as four dense parity sub-images: both sides move consecutive pixels
             u3 = self._buf("full64", 64 // P, B, H, W, P)
-            self.ups[2](u2, out=u3, planes=64 // P, parity_major=pm)
+            self.ups[2](u2, out=u3, planes=64 // P, parity_major=pm, nprod=nprod)
             self.out_conv(u3, out=pred, parity_major=pm)
         else:                  # planar_tail = 0: NHWC between the two (tests) — same values, other addresses
             u3 = self._buf("full64", B, H, W, 64)
-            self.ups[2](u2, out=u3)
+            self.ups[2](u2, out=u3, nprod=nprod)
             self.out_conv(u3, out=pred)
         if taps is not None:
             taps["pred"] = pred.clone()

@@ -9,7 +9,7 @@ import ctypes as C
 from pathlib import Path
 
 MIT_MAX_TAPS = 64
-MIT_ABI_VERSION = 16
+MIT_ABI_VERSION = 17
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SILU, ACT_SIGMOID, ACT_GELU = range(6)
 ACT_POST_FIRST = 0x100
@@ -76,6 +76,8 @@ class MitConvGemm(C.Structure):
         ("lut1", C.c_void_p),
         ("lut2", C.c_void_p),
         ("lut_ld", C.c_int64),
+        ("nprod", C.c_int32),   # 0 = follow the GEMM mode; 1 = the one-product bf16 tiles (include/mit_hip.h)
+        ("_pad1", C.c_int32),
     ]
 
 

@@ -24,7 +24,7 @@ from .lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_S
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "ACT_LEAKY", "ACT_SILU", "ACT_SIGMOID", "ACT_GELU", "ACT_POST_FIRST", "PAD_ZERO", "PAD_REFLECT",
-    "Conv2d", "ConvSmallCout", "split_mode", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "current_stream",
+    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "current_stream",
 ]
 
 
@@ -120,8 +120,9 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
                    pre: Optional[MitTensorMap] = None, post: Optional[MitTensorMap] = None,
                    scale: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
                    alpha: float = 0.0, Z: int = 1, zdiv: int = 1, a_zs: Tuple[int, int] = (0, 0),
-                   w_zs: Tuple[int, int] = (0, 0)) -> MitConvGemm:
-    """Fill a ``MitConvGemm`` descriptor. Pure host logic (usable without a GPU)."""
+                   w_zs: Tuple[int, int] = (0, 0), nprod: int = 0) -> MitConvGemm:
+    """Fill a ``MitConvGemm`` descriptor. Pure host logic (usable without a GPU).  ``nprod`` = 1: the one-product bf16 tiles for this
+    launch (MitConvGemm.nprod; the weight must carry planes: ``ensure_split``)."""
     if len(taps) == 0 or len(taps) > MIT_MAX_TAPS:
         raise ValueError(f"ntaps {len(taps)} out of range")
     d = MitConvGemm()
@@ -137,7 +138,7 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
     d.w_zs1, d.w_zs0 = w_zs
     d.ldw, d.Kw, d.Nw = ldw, Kw, Nw
     if _SPLITS:
-        planes, zs = _split_for(w, ldw, Kw, w_zs)
+        planes, zs = _split_for(w, ldw, Kw, w_zs, nprod)
         if planes is not None:
             d.w_split, d.ws_zs0 = planes.data_ptr(), zs
     d.N, d.Z, d.zdiv = N, Z, zdiv
@@ -147,6 +148,7 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
     d.scale = _ptr(scale)
     d.bias = _ptr(bias)
     d.act, d.act_alpha = act, alpha
+    d.nprod = int(nprod)
     return d
 
 
@@ -207,7 +209,8 @@ class gemm_mode:
         return False
 
 
-_SPLITS: Dict[int, Tuple["weakref.ref", torch.Tensor, int, int, int]] = {}   # data_ptr -> (weight, planes, nz, Kp, Np)
+# data_ptr -> (weight, planes, nz, Kp, Np[, p1_only]); p1_only (absent = False): planes attached for one-product launches only (ensure_split)
+_SPLITS: Dict[int, tuple] = {}
 
 
 def split_weight(w: torch.Tensor) -> torch.Tensor:
@@ -225,7 +228,7 @@ def split_weight(w: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def register_split(w: torch.Tensor, force: bool = False) -> Optional[torch.Tensor]:
+def register_split(w: torch.Tensor, force: bool = False, p1_only: bool = False) -> Optional[torch.Tensor]:
     """Attach split planes to a packed weight (no-op unless ``split_mode()`` or ``force``): ``conv_gemm_desc`` finds them by the
     tensor's identity, so every layer built on ``pack_weight_kn`` / ``WinogradConv3x3`` gets the split tiles without further plumbing."""
     if w.device.type != "cuda" or not (force or split_mode()):
@@ -233,13 +236,24 @@ def register_split(w: torch.Tensor, force: bool = False) -> Optional[torch.Tenso
     planes = split_weight(w)
     nz = 1 if w.dim() == 2 else w.shape[0]
     key = w.data_ptr()
-    _SPLITS[key] = (weakref.ref(w, lambda _r, k=key: _SPLITS.pop(k, None)), planes, nz, w.shape[-2], w.shape[-1])
+    _SPLITS[key] = (weakref.ref(w, lambda _r, k=key: _SPLITS.pop(k, None)), planes, nz, w.shape[-2], w.shape[-1], bool(p1_only))
     return planes
 
 
-def _split_for(w: torch.Tensor, ldw: int, Kw: int, w_zs: Tuple[int, int]):
+def ensure_split(w: torch.Tensor) -> None:
+    """Planes for a weight that is about to run with ``nprod = 1``, whatever the GEMM mode was when it was packed.  A weight packed in
+    mode 0 carries none and stays on the fp32 tiles in every mode (``set_split_mode``): the planes attached here are therefore handed
+    to one-product launches only, so an fp32 launch of the same layer keeps the tile — and the bytes — it had before."""
+    e = _SPLITS.get(w.data_ptr())
+    if e is None or e[0]() is not w:
+        register_split(w, force=True, p1_only=True)
+
+
+def _split_for(w: torch.Tensor, ldw: int, Kw: int, w_zs: Tuple[int, int], nprod: int = 0):
     e = _SPLITS.get(w.data_ptr())
     if e is None or e[0]() is not w or (e[3], e[4]) != (Kw, ldw) or w_zs[0] != 0 or (e[2] > 1 and w_zs[1] != Kw * ldw):
+        return None, 0
+    if nprod != 1 and e[5:] == (True,):
         return None, 0
     return e[1], (3 * Kw * ldw if e[2] > 1 else 0)
 
@@ -390,8 +404,11 @@ class Conv2d:
         return ((H + 2 * self.py - d * (self.kh - 1) - 1) // self.sy + 1, (W + 2 * self.px - d * (self.kw - 1) - 1) // self.sx + 1)
 
     def desc(self, x: torch.Tensor, out: torch.Tensor, pre: Optional[torch.Tensor] = None,
-             post: Optional[torch.Tensor] = None) -> MitConvGemm:
+             post: Optional[torch.Tensor] = None, nprod: int = 0) -> MitConvGemm:
+        """``nprod`` = 1: this launch on the one-product bf16 tiles (MitConvGemm.nprod)."""
         _check_nhwc(x, "Conv2d input")
+        if nprod:
+            ensure_split(self.w)
         _check_nhwc(out, "Conv2d output")
         B, H, W, Cx = x.shape
         if Cx != self.Cin:
@@ -406,14 +423,14 @@ class Conv2d:
             a=x, NB=B, Hi=H, Wi=W, Cin=self.Cin, a_strides=(x.stride(0), x.stride(1), x.stride(2)), Ho=Ho, Wo=Wo,
             sy=self.sy, sx=self.sx, taps=self.taps, pad_mode=self.pad_mode, w=self.w, ldw=self.Np, Kw=self.Kp,
             Nw=self.Np, N=self.Cout, c=tensor_map(out), pre=tensor_map(pre), post=tensor_map(post),
-            scale=self.scale, bias=self.bias, act=self.act, alpha=self.alpha)
+            scale=self.scale, bias=self.bias, act=self.act, alpha=self.alpha, nprod=nprod)
 
     def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None,
-                 post: Optional[torch.Tensor] = None, cfg: int = -1) -> torch.Tensor:
+                 post: Optional[torch.Tensor] = None, cfg: int = -1, nprod: int = 0) -> torch.Tensor:
         if out is None:
             Ho, Wo = self.out_hw(x.shape[1], x.shape[2])
             out = torch.empty(x.shape[0], Ho, Wo, self.Cout, dtype=torch.float32, device=x.device)
-        launch_conv_gemm(self.desc(x, out, pre, post), cfg)
+        launch_conv_gemm(self.desc(x, out, pre, post, nprod), cfg)
         return out
 
 
@@ -653,7 +670,7 @@ class ConvTranspose2d:
     def out_hw(self, H: int, W: int) -> Tuple[int, int]:
         return ((H - 1) * self.s - 2 * self.p + self.k[0] + self.op, (W - 1) * self.s - 2 * self.p + self.k[1] + self.op)
 
-    def descs(self, x: torch.Tensor, out: torch.Tensor, planes: int = 0, parity_major: bool = False) -> List[MitConvGemm]:
+    def descs(self, x: torch.Tensor, out: torch.Tensor, planes: int = 0, parity_major: bool = False, nprod: int = 0) -> List[MitConvGemm]:
         """``planes`` = P > 0: ``out`` is [P, B, Ho, Wo, Cout / P] (contiguous) and every launch writes through a column-split map
         (MitTensorMap.nsplit = Cout / P): channel group g of a pixel goes to plane g.  The consumer that reads channel groups (the 7x7
         output convolution) then finds each group in whole lines."""
@@ -678,6 +695,8 @@ class ConvTranspose2d:
             ov = out[:, py::self.s, px::self.s]
             if ov.shape[1] == 0 or ov.shape[2] == 0:
                 continue
+            if nprod:
+                ensure_split(pk.w)
             if parity_major:   # every plane holds the image as four dense sub-images, one per output parity class: [2 (py)][2 (px)][Ho / 2][Wo / 2][P]
                 pc, h2, w2 = self.Cout // planes, Ho // 2, Wo // 2   # — a class's launch then writes consecutive pixels (an interleaved
                 ov = out.as_strided((B, h2, w2, self.Cout), (Ho * Wo * pc, w2 * pc, pc, 1),      # image would put them 2 P floats apart)
@@ -686,14 +705,15 @@ class ConvTranspose2d:
                 a=x, NB=B, Hi=H, Wi=W, Cin=self.Cin, a_strides=(x.stride(0), x.stride(1), x.stride(2)),
                 Ho=ov.shape[1], Wo=ov.shape[2], sy=1, sx=1, taps=pk.taps, pad_mode=PAD_ZERO, w=pk.w, ldw=pk.Np,
                 Kw=pk.Kp, Nw=pk.Np, N=self.Cout, c=tensor_map(ov, nsplit=split, nhi=nhi), scale=self.scale, bias=self.bias, act=self.act,
-                alpha=self.alpha))
+                alpha=self.alpha, nprod=nprod))
         return ds
 
-    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, cfg: int = -1, planes: int = 0, parity_major: bool = False) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, cfg: int = -1, planes: int = 0, parity_major: bool = False,
+                 nprod: int = 0) -> torch.Tensor:
         if out is None:
             Ho, Wo = self.out_hw(x.shape[1], x.shape[2])
             out = (torch.empty(planes, x.shape[0], Ho, Wo, self.Cout // planes, dtype=torch.float32, device=x.device) if planes else
                    torch.empty(x.shape[0], Ho, Wo, self.Cout, dtype=torch.float32, device=x.device))
-        for d in self.descs(x, out, planes, parity_major):
+        for d in self.descs(x, out, planes, parity_major, nprod):
             launch_conv_gemm(d, cfg)
         return out

@@ -651,8 +651,40 @@ def decode_lines(tokens: np.ndarray, lengths: np.ndarray, colors: np.ndarray, di
     return out
 
 
+LAMA_PRECISIONS = ("fp32", "bf16", "config")
+
+
+def lama_precision_default() -> str:
+    """The ``precision`` of a LaMa plugin created without one (``register()``, ``serve.py``): ``MIT_LAMA_PRECISION`` in the
+    environment ("fp32" | "bf16" | "config"), else "fp32"."""
+    v = os.environ.get("MIT_LAMA_PRECISION", "").strip().lower() or "fp32"
+    if v not in LAMA_PRECISIONS:
+        raise ValueError(f"MIT_LAMA_PRECISION must be one of {LAMA_PRECISIONS} (got {v!r})")
+    return v
+
+
+def resolve_lama_precision(setting: str, config=None) -> str:
+    """A plugin's ``precision`` setting and the ``config`` of a call -> the engine's precision, "fp32" or "bf16".  "config" follows
+    ``config.inpainting_precision`` the way the reference's GPU path does (inpainting_lama_mpe.py:97-107: ``bf16`` -> bf16, ``fp16``
+    -> bf16 as well, :102-104; ``fp32`` -> fp32); without a config it is fp32."""
+    if setting not in LAMA_PRECISIONS:
+        raise ValueError(f"LaMa precision must be one of {LAMA_PRECISIONS} (got {setting!r})")
+    if setting != "config":
+        return setting
+    if config is None:
+        return "fp32"
+    v = getattr(config, "inpainting_precision", None)
+    v = str(getattr(v, "value", v)).lower()      # the reference's InpaintPrecision is a str enum
+    if v in ("bf16", "fp16"):
+        return "bf16"
+    if v == "fp32":
+        return "fp32"
+    raise ValueError(f"config.inpainting_precision must be fp32, fp16 or bf16 (got {v!r})")
+
+
 class HipLamaMPEInpainter(_InpBase):
-    """``--inpainter lama_mpe`` on the HIP engine."""
+    """``--inpainter lama_mpe`` on the HIP engine.  ``precision``: "fp32" (default), "bf16", or "config" = what the call's
+    ``config.inpainting_precision`` says, as in the reference (``resolve_lama_precision``); None = ``lama_precision_default()``."""
     _KEY = _key = "lama_mpe_hip"
     _MODEL_MAPPING: Dict = {  # inpainting/inpainting_lama_mpe.py:32-38
         "model": {
@@ -664,11 +696,17 @@ class HipLamaMPEInpainter(_InpBase):
     N_BLOCKS, USE_MPE, CKPT = 9, True, "inpainting_lama_mpe.ckpt"
 
     def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None,
-                 resize: Optional[Callable] = None, **kwargs):
+                 resize: Optional[Callable] = None, precision: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
         self._weights, self._resize = weights, resize
+        self.precision = lama_precision_default() if precision is None else precision
+        resolve_lama_precision(self.precision)      # a bad value raises here, not at the first page
         self.engine = None
         _weights_handed_over(self, weights)
+
+    def precision_for(self, config=None) -> str:
+        """The engine precision of a call with this ``config``: "fp32" or "bf16"."""
+        return resolve_lama_precision(self.precision, config)
 
     async def _load(self, device: str):
         from . import lama
@@ -688,8 +726,10 @@ class HipLamaMPEInpainter(_InpBase):
     async def _infer(self, image: np.ndarray, mask: np.ndarray, config=None, inpainting_size: int = 1024,
                      verbose: bool = False) -> np.ndarray:
         """image u8 [H,W,3], mask u8 [H,W] -> inpainted [H,W,3] (inpainting_lama_mpe.py:56-118), any page size: the
-        resize_keep_aspect / multiple-of-8 / back-to-page resizes and the final composite run on the GPU (imgproc.py).  Always
-        fp32: the reference's CPU path never autocasts (:93-95) and that is the parity target."""
+        resize_keep_aspect / multiple-of-8 / back-to-page resizes and the final composite run on the GPU (imgproc.py).  The
+        network runs in ``self.precision_for(config)``: fp32 by default (the reference's CPU path never autocasts, :93-95, and that
+        is the parity target), bf16 when the plugin was created with ``precision="bf16"`` or with ``"config"`` and the config asks
+        for bf16 / fp16 — the reference's GPU path (:97-107); see ``LamaEngine.forward``."""
         if image.ndim != 3 or image.shape[2] != 3 or mask.shape != image.shape[:2]:
             raise ValueError(f"bad shapes: image {image.shape}, mask {mask.shape}")
         if image.dtype != np.uint8 or mask.dtype != np.uint8:
@@ -698,7 +738,7 @@ class HipLamaMPEInpainter(_InpBase):
         img0 = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]     # the page crosses PCIe once, as bytes
         msk0 = torch.from_numpy(np.ascontiguousarray(mask)).to(dev)[None]
         # optional injected callable (img, (w, h), "keep_aspect" | "linear") -> ndarray: e.g. the real OpenCV
-        return inpaint_pages(self.engine, img0, msk0, inpainting_size, self._resize)[0].cpu().numpy()
+        return inpaint_pages(self.engine, img0, msk0, inpainting_size, self._resize, precision=self.precision_for(config))[0].cpu().numpy()
 
     @staticmethod
     def _resized(t: torch.Tensor, dsize, mode: str, injected: Optional[Callable]) -> torch.Tensor:
@@ -712,10 +752,14 @@ class HipLamaMPEInpainter(_InpBase):
 
 @torch.no_grad()
 def inpaint_pages(engine, img0: torch.Tensor, msk0: torch.Tensor, inpainting_size: int, resize: Optional[Callable] = None,
-                  micro_batch: int = 16) -> torch.Tensor:
+                  micro_batch: int = 16, precision: str = "fp32") -> torch.Tensor:
     """The resize / composite legs of LamaMPEInpainter._infer (inpainting_lama_mpe.py:56-118) around ``engine.forward`` for device
     pages u8 [B,H,W,3] and masks u8 [B,H,W] of one size: what the plugin runs for its one page and the coupled batch engine for a
-    group — the same kernels in the same order, so a page's bytes do not depend on how many pages travel with it."""
+    group — the same kernels in the same order, so a page's bytes do not depend on how many pages travel with it.
+    ``precision`` ("fp32" | "bf16") goes to ``engine.forward``; an engine is handed the argument only when it is not "fp32"."""
+    if precision not in ("fp32", "bf16"):
+        raise ValueError(f"inpaint_pages: precision must be 'fp32' or 'bf16' (got {precision!r})")
+    fwd_kw = {} if precision == "fp32" else {"precision": precision}
     from . import imgproc
 
     B, height, width, _ = img0.shape
@@ -732,7 +776,7 @@ def inpaint_pages(engine, img0: torch.Tensor, msk0: torch.Tensor, inpainting_siz
         if (new_h, new_w) != (h, w):
             img, msk = rs(img, (new_w, new_h), "linear", resize), rs(msk, (new_w, new_h), "linear", resize)
         resized = (new_h, new_w) != (height, width)
-        out = engine.forward(img, msk, composite=not resized)  # resized: img_inpainted of :111, every pixel from the network
+        out = engine.forward(img, msk, composite=not resized, **fwd_kw)  # resized: img_inpainted of :111, every pixel from the network
         if resized:                                                             # back to the page size (:112-113)
             out = rs(out, (width, height), "linear", resize)
         # img_inpainted * mask_original + img_original * (1 - mask_original), mask_original = mask >= 127 (:57-61,116)
@@ -756,7 +800,8 @@ class HipLamaLargeInpainter(HipLamaMPEInpainter):
 class HipAotInpainter(HipLamaMPEInpainter):
     """``--inpainter default``: the AOT generator (inpainting_aot.py:11-33).  Like the reference's AotInpainter it subclasses the
     LaMa-MPE plugin and reuses its ``_infer`` unchanged (input / 127.5 - 1, output (x + 1) * 127.5 truncated: the model is not a
-    LamaFourier, inpainting_lama_mpe.py:84,114); only the model and its checkpoint differ.  ``weights``: {"aot": state_dict}."""
+    LamaFourier, inpainting_lama_mpe.py:84,114); only the model and its checkpoint differ.  ``weights``: {"aot": state_dict}.
+    The ``precision`` option is accepted, and the AOT engine runs in fp32 whatever it says: its bf16 form is not built."""
     _KEY = _key = "default_hip"
     _MODEL_MAPPING: Dict = {  # inpainting/inpainting_aot.py:12-18
         "model": {
@@ -767,6 +812,10 @@ class HipAotInpainter(HipLamaMPEInpainter):
     }
     CKPT = "inpainting.ckpt"
     MB = 4   # pages per micro-batch of the engine: 16 full 2048 x 1456 pages run as four of them within one workspace
+
+    def precision_for(self, config=None) -> str:
+        resolve_lama_precision(self.precision, config)   # the option is validated like the parent's
+        return "fp32"
 
     async def _load(self, device: str):
         from . import aot

@@ -225,6 +225,12 @@ class DenseStages:
             return "ocr.ignore_bubble is not implemented by the coupled engine"
         return None
 
+    def _inpaint_precision(self) -> str:
+        """What the page loop's ``self.inp.infer(page, mask, None, ...)`` runs in (the plugin's ``precision`` option, ``MIT_LAMA_PRECISION``
+        by default): a batch follows it.  An inpainter without the option is fp32."""
+        fn = getattr(getattr(self, "inp", None), "precision_for", None)
+        return fn(None) if fn is not None else "fp32"
+
     def _coupled_engine(self):
         from . import coupled
 
@@ -272,7 +278,8 @@ class DenseStages:
                         prob_threshold=0.2 if ocr.get("prob") is None else float(ocr["prob"]),
                         textlines=[cfgs[i].get("textlines") for i in idx], mask_raw=[cfgs[i].get("mask_raw") for i in idx],
                         mask=[cfgs[i].get("mask") for i in idx], mask_dilation_offset=int(cfg.get("mask_dilation_offset", 20)),
-                        kernel_size=int(cfg.get("kernel_size", 3)), inpainting_size=int(inp.get("inpainting_size", 2048)))
+                        kernel_size=int(cfg.get("kernel_size", 3)), inpainting_size=int(inp.get("inpainting_size", 2048)),
+                        precision=self._inpaint_precision())
             self.last_coupled_seconds.append(dict(r.seconds))
             mask_raw, mask, out = r.mask_raw.cpu().numpy(), r.mask.cpu().numpy(), r.inpainted.cpu().numpy()
             for k, i in enumerate(idx):
