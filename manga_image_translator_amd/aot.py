@@ -63,7 +63,7 @@ class _Gated:
                 self.conv = ops.Conv2d(wc, b, stride=stride, padding=(k - 1) // 2, pad_mode=PAD_REFLECT, device=device)
 
 
-class AotEngine:
+class AotEngine(ops.Engine):
     """Batched AOT generator. ``forward(img_u8[B,H,W,3], mask_u8[B,H,W]) -> u8 [B,H,W,3]`` (device tensors), pages run in
     micro-batches of ``mb``."""
 
@@ -73,7 +73,7 @@ class AotEngine:
         from block to block, and Winograd's larger rounding there doubled the distance to a float64 oracle after ten blocks
         (1.5e-4 -> 2.5e-4 at 256 x 184 in the split mode)."""
         synth.check_state_dict(sd, aot_schema.aot_generator_schema(), "AOT generator")
-        self.device = torch.device(device)
+        super().__init__(device)
         self.mb = int(mb)
         if self.mb < 1:
             raise ValueError("AotEngine: mb must be >= 1")
@@ -97,13 +97,6 @@ class AotEngine:
         self.tail = [_Gated(sd, "tail.0", 3, 1, False, winograd, dev), _Gated(sd, "tail.2", 3, 1, False, winograd, dev),
                      _Gated(sd, "tail.4", 4, 2, True, winograd, dev), _Gated(sd, "tail.6", 4, 2, True, winograd, dev),
                      _Gated(sd, "tail.8", 3, 1, False, winograd, dev)]
-        self._ws = ops.Workspace(self.device)
-
-    def _buf(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        return self._ws.buf(name, *shape, dtype=dtype)
-
-    def release_workspace(self):
-        self._ws.release()
 
     # -- pieces ------------------------------------------------------------------------------------------------------------------
     def _conv(self, layer, x: torch.Tensor, out: torch.Tensor):

@@ -21,9 +21,12 @@
 #include "common.h"
 #include "ocr_kernels.h"
 #include "pgemm_rows.h"
+#include "ocr_linear.h"
 #include "bf16_split.h"
 
 namespace {
+
+using namespace ocrlin;
 
 constexpr int E = 320;
 constexpr int FF = 2048;
@@ -41,8 +44,6 @@ struct Ws {
     uint16_t *x_p, *att_p, *ffh_p, *p1_p;
     int64_t Rp;
 };
-
-inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
 int64_t carve(Ws *w, char *base, int N, int T, int D) {
     const int64_t R = (int64_t)N * BEAMS;
@@ -87,51 +88,6 @@ int64_t carve(Ws *w, char *base, int N, int T, int D) {
     if (w) *w = o;
     return off;
 }
-
-// C[M x N] = act((A[M x K] @ W) * scale + bias) + post, rows of A / C / post strided (the tiled GEMM, either GEMM mode).
-int gemm(const MitLinear &lin, const float *A, int64_t lda, float *Cp, int64_t ldc, int M, int act, const float *post, int64_t ldpost,
-         hipStream_t s, int nsplit = 0, int64_t nhi = 0) {
-    MitConvGemm d;
-    memset(&d, 0, sizeof(d));
-    d.a = A;
-    d.a_xs = lda;
-    d.NB = 1; d.Hi = 1; d.Wi = M; d.Ho = 1; d.Wo = M; d.sy = 1; d.sx = 1;
-    d.ntaps = 1; d.pad_mode = MIT_PAD_ZERO;
-    d.w = lin.w; d.ldw = lin.ldw; d.Nw = lin.Np;
-    d.N = lin.N;
-    d.Cin = lin.K; d.Kw = lin.Kp;
-    d.Z = 1; d.zdiv = 1;
-    d.w_split = lin.w_split;
-    d.c.base = Cp; d.c.xs = ldc; d.c.nsplit = nsplit; d.c.nhi = nhi;
-    if (post) {
-        d.post.base = const_cast<float *>(post);
-        d.post.xs = ldpost;
-    }
-    d.scale = lin.scale; d.bias = lin.bias; d.act = act;
-    return mit_conv_gemm(&d, s);
-}
-
-// The same Linear on planar activations (pgemm_rows.h), one wave per 32 x 32 output block: C fp32 (optional, with the column split of
-// gemm()) and / or planes.  splitk: the K = 2048 Linear with K cut across four waves.
-int pgemm(const MitLinear &lin, const uint16_t *a_planes, int64_t lda, int M, float *Cp, int64_t ldc, int act, const float *post, int64_t ldpost,
-          uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0, int splitk = 0) {
-    MitPGemm d;
-    memset(&d, 0, sizeof(d));
-    d.a_planes = a_planes; d.lda = lda;
-    d.w_planes = lin.w_split; d.ldw = lin.ldw;
-    d.M = M; d.N = lin.N; d.K = lin.K; d.Z = 1;
-    d.c = Cp; d.ldc = ldc;
-    d.post = post; d.ld_post = ldpost;
-    d.scale = lin.scale; d.bias = lin.bias; d.act = act;
-    d.nprod = 0;  // the GEMM mode of the moment
-    PgRowsExt x;
-    memset(&x, 0, sizeof(x));
-    x.nsplit = nsplit; x.nhi = nhi; x.splitk = splitk;
-    if (Cp) x.also_planes = c_planes, x.also_ld = ld_cp;
-    else d.c_planes = c_planes, d.ld_cp = ld_cp;
-    return mit_pgemm_rows(d, x, s);
-}
-inline bool rows_ok(const MitLinear &l) { return l.w_split && l.Kp == l.K && (l.K % 16) == 0 && (l.N % 8) == 0; }
 
 // eight consecutive fp32 values -> their cell in each of the three planes (the split a GEMM tile applies to the value itself)
 __device__ __forceinline__ void store_cells(const OcrPlanes &o, const int k8, const int64_t row, const float *v8) {
@@ -658,7 +614,7 @@ extern "C" int mit_ocr32_decode(const MitOcr32Decoder *dec, MitOcr32DecodeArgs *
                 if (layernorm(w.y, ly.ln2_w, ly.ln2_b, w.x, E, R, x_pl, s)) return 1;
                 // feed forward (:457-460): the hidden activations exist as planes only
                 if (pgemm(ly.ff1, w.x_p, Rp, R, nullptr, 0, MIT_ACT_RELU, nullptr, 0, w.ffh_p, Rp, s)) return 1;
-                if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.y, E, MIT_ACT_NONE, w.x, E, nullptr, 0, s, 0, 0, ff2_splitk)) return 1;
+                if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.y, E, MIT_ACT_NONE, w.x, E, nullptr, 0, s, 0, 0, nullptr, 0, ff2_splitk)) return 1;
                 if (layernorm(w.y, ly.ln3_w, ly.ln3_b, out3, out3_rs, R, x_pl, s)) return 1;
             } else {
                 if (gemm(ly.qkv, w.x, E, qc + so, PE_, R, MIT_ACT_NONE, nullptr, 0, s, E, (int64_t)R * PE_)) return 1;

@@ -19,8 +19,11 @@
 #include "common.h"
 #include "ocr_kernels.h"
 #include "pgemm_rows.h"
+#include "ocr_linear.h"
 
 namespace {
+
+using namespace ocrlin;
 
 constexpr int E = 320;
 constexpr int FF = 2048;
@@ -34,8 +37,6 @@ struct Ws {
     uint16_t *nrm_p, *att_p, *ffh_p, *dec_p, *p1_p;
     int64_t Rp;
 };
-
-inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 int64_t carve(Ws *w, char *base, int N, int T, int D) {
     const int64_t R = (int64_t)N * 5;
@@ -74,71 +75,6 @@ int64_t carve(Ws *w, char *base, int N, int T, int D) {
     return off;
 }
 
-// C[M x N] = act((A[M x K] @ W) * scale + bias) + post, rows of A / C / post strided.
-// dyn / a_dyn / c_dyn: device-resident step counter and the per-step strides of A and C (MitConvGemm.dyn), for the graph-replayed steps.
-int gemm(const MitLinear &lin, const float *A, int64_t lda, float *Cp, int64_t ldc, int M, int act, const float *post,
-         int64_t ldpost, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr,
-         int64_t a_dyn = 0, int64_t c_dyn = 0) {
-    MitConvGemm d;
-    memset(&d, 0, sizeof(d));
-    d.dyn = dyn; d.a_dyn = a_dyn; d.c_dyn = c_dyn;
-    d.a = A;
-    d.a_xs = lda;
-    d.NB = 1; d.Hi = 1; d.Wi = M; d.Ho = 1; d.Wo = M; d.sy = 1; d.sx = 1;
-    d.ntaps = 1; d.pad_mode = MIT_PAD_ZERO;
-    d.w = lin.w; d.ldw = lin.ldw; d.Nw = lin.Np;
-    d.N = lin.N;
-    d.Cin = lin.K; d.Kw = lin.Kp;
-    d.Z = 1; d.zdiv = 1;
-    d.w_split = lin.w_split;  // planes attached by the packer in a split GEMM mode (NULL otherwise); the launcher decides by the mode of the moment
-    d.c.base = Cp; d.c.xs = ldc; d.c.nsplit = nsplit; d.c.nhi = nhi;
-    if (post) {
-        d.post.base = const_cast<float *>(post);
-        d.post.xs = ldpost;
-    }
-    d.scale = lin.scale; d.bias = lin.bias; d.act = act;
-    return mit_conv_gemm(&d, s);
-}
-
-// The same Linear on planar activations (pgemm_rows.h): C fp32 (optional, with the column split / step offset of gemm()) and / or planes.
-int pgemm(const MitLinear &lin, const uint16_t *a_planes, int64_t lda, int M, float *Cp, int64_t ldc, int act, const float *post,
-          int64_t ldpost, uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr,
-          int64_t c_dyn = 0, int splitk = 0) {
-    MitPGemm d;
-    memset(&d, 0, sizeof(d));
-    d.a_planes = a_planes; d.lda = lda;
-    d.w_planes = lin.w_split; d.ldw = lin.ldw;
-    d.M = M; d.N = lin.N; d.K = lin.K; d.Z = 1;
-    d.c = Cp; d.ldc = ldc;
-    d.post = post; d.ld_post = ldpost;
-    d.scale = lin.scale; d.bias = lin.bias; d.act = act;
-    d.nprod = 0;  // the GEMM mode of the moment
-    PgRowsExt x;
-    memset(&x, 0, sizeof(x));
-    x.nsplit = nsplit; x.nhi = nhi; x.dyn = dyn; x.c_dyn = c_dyn; x.splitk = splitk;
-    if (Cp) x.also_planes = c_planes, x.also_ld = ld_cp;
-    else d.c_planes = c_planes, d.ld_cp = ld_cp;
-    return mit_pgemm_rows(d, x, s);
-}
-// The same with A = LayerNorm(x) computed by the GEMM's own waves (pgemm_rows_ln.hip; K == 320): bit for bit ocrk_layernorm + pgemm.
-int pgemm_ln(const MitLinear &lin, const float *xin, int64_t ldx, const float *ln_w, const float *ln_b, int M, float *Cp, int64_t ldc, int act,
-             uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr, int64_t c_dyn = 0) {
-    MitPGemm d;
-    memset(&d, 0, sizeof(d));
-    d.w_planes = lin.w_split; d.ldw = lin.ldw;
-    d.M = M; d.N = lin.N; d.K = lin.K; d.Z = 1;
-    d.c = Cp; d.ldc = ldc;
-    d.scale = lin.scale; d.bias = lin.bias; d.act = act;
-    d.nprod = 0;
-    PgRowsExt x;
-    memset(&x, 0, sizeof(x));
-    x.nsplit = nsplit; x.nhi = nhi; x.dyn = dyn; x.c_dyn = c_dyn;
-    if (Cp) x.also_planes = c_planes, x.also_ld = ld_cp;
-    else d.c_planes = c_planes, d.ld_cp = ld_cp;
-    const PgRowsLn ln{xin, ldx, ln_w, ln_b, 1e-5f};
-    return mit_pgemm_rows_ln(d, x, ln, s);
-}
-inline bool rows_ok(const MitLinear &l) { return l.w_split && l.Kp == l.K && (l.K % 16) == 0 && (l.N % 8) == 0; }
 
 __global__ void fill_int_kernel(int *p, int64_t n, int v) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

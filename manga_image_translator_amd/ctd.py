@@ -22,13 +22,9 @@ import torch
 
 from . import lib as _lib
 from . import ops
-from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU
+from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, bn_params
 
 INPUT_SIZE = 1024  # ctd.py:84
-
-
-def _bn(sd, p, eps=1e-5):
-    return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"], eps)
 
 
 def _fused_yolo_conv(sd, p, k, s, device):
@@ -45,7 +41,7 @@ def _fused_yolo_conv(sd, p, k, s, device):
 
 def _head_conv(sd, p, k, device):
     """heads' Conv (common.py:30-46): conv (no bias) -> BN -> LeakyReLU(0.1)."""
-    return ops.Conv2d(sd[p + ".conv.weight"], None, padding=k // 2, bn=_bn(sd, p + ".bn"), act=ACT_LEAKY, alpha=0.1,
+    return ops.Conv2d(sd[p + ".conv.weight"], None, padding=k // 2, bn=bn_params(sd, p + ".bn"), act=ACT_LEAKY, alpha=0.1,
                       device=device)
 
 
@@ -72,12 +68,13 @@ class _C3:
         return self.cv3(cat, out=out)
 
 
-class CtdEngine:
+class CtdEngine(ops.Engine):
     """Batched text-detection network: u8 pages -> (mask u8, lines fp32) on the device."""
 
     def __init__(self, yolo_sd: Dict[str, torch.Tensor], seg_sd: Dict[str, torch.Tensor], det_sd: Dict[str, torch.Tensor],
                  device="cuda"):
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         ymk = lambda k_s: (lambda p, k: _fused_yolo_conv(yolo_sd, p, k, k_s, dev))
         y1 = lambda p, k: _fused_yolo_conv(yolo_sd, p, k, 1, dev)
         self.y0 = _fused_yolo_conv(yolo_sd, "model.0", 6, 2, dev)
@@ -95,7 +92,7 @@ class CtdEngine:
         def up_c3(sd, p, cin, mid, cout):
             hk = lambda q, k: _head_conv(sd, q, k, dev)
             c3 = _C3(sd, p + ".conv.0", cin, mid, 1, hk)
-            up = ops.ConvTranspose2d(sd[p + ".conv.1.weight"], None, stride=2, padding=1, bn=_bn(sd, p + ".conv.2"),
+            up = ops.ConvTranspose2d(sd[p + ".conv.1.weight"], None, stride=2, padding=1, bn=bn_params(sd, p + ".conv.2"),
                                      act=ACT_RELU, device=dev)
             return c3, up
 
@@ -110,27 +107,19 @@ class CtdEngine:
         d = det_sd
         self.d_up3 = up_c3(d, "upconv3", 512, 512, 256)
         self.d_up4 = up_c3(d, "upconv4", 384, 256, 128)
-        self.d_conv = ops.Conv2d(d["conv.0.weight"], d["conv.0.bias"], bn=_bn(d, "conv.1"), act=ACT_RELU, device=dev)
+        self.d_conv = ops.Conv2d(d["conv.0.weight"], d["conv.0.bias"], bn=bn_params(d, "conv.1"), act=ACT_RELU, device=dev)
 
         def branch(p, first_bias):
-            c0 = ops.Conv2d(d[p + ".0.weight"], d[p + ".0.bias"] if first_bias else None, padding=1, bn=_bn(d, p + ".1"),
+            c0 = ops.Conv2d(d[p + ".0.weight"], d[p + ".0.bias"] if first_bias else None, padding=1, bn=bn_params(d, p + ".1"),
                             act=ACT_RELU, device=dev)
-            t1 = ops.ConvTranspose2d(d[p + ".3.weight"], d[p + ".3.bias"], stride=2, bn=_bn(d, p + ".4"), act=ACT_RELU,
+            t1 = ops.ConvTranspose2d(d[p + ".3.weight"], d[p + ".3.bias"], stride=2, bn=bn_params(d, p + ".4"), act=ACT_RELU,
                                      device=dev)
             t2 = ops.ConvTranspose2d(d[p + ".6.weight"], d[p + ".6.bias"], stride=2, act=ACT_SIGMOID, device=dev)
             return c0, t1, t2
 
         self.br_binarize = branch("binarize", True)
         self.br_thresh = branch("thresh", False)
-        self._ws = ops.Workspace(self.device)
         self._prep_tabs: Dict[Tuple, dict] = {}
-
-    def _buf(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        """Named workspace slab, grown to the largest request (ops.Workspace): memory is bounded by the largest page seen."""
-        return self._ws.buf(name, *shape, dtype=dtype)
-
-    def release_workspace(self):
-        self._ws.release()
 
     # -- letterbox geometry (imgproc_utils.py:69-100) ------------------------------------------
     @staticmethod

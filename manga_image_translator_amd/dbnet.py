@@ -18,41 +18,38 @@ import torch
 from . import lib as _lib
 from . import ops
 from .dbnet_schema import RESNET34_LAYERS
-from .ops import ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_SIGMOID
-
-
-def _bn(sd, p, eps=1e-5):
-    return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"], eps)
+from .ops import ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_SIGMOID, bn_params
 
 
 class _Basic:
     def __init__(self, sd, q, stride, dev):
-        self.conv1 = ops.Conv2d(sd[q + ".conv1.weight"], None, stride=stride, padding=1, bn=_bn(sd, q + ".bn1"), act=ACT_RELU, device=dev)
-        self.conv2 = ops.Conv2d(sd[q + ".conv2.weight"], None, padding=1, bn=_bn(sd, q + ".bn2"), act=ACT_RELU | ACT_POST_FIRST, device=dev)
+        self.conv1 = ops.Conv2d(sd[q + ".conv1.weight"], None, stride=stride, padding=1, bn=bn_params(sd, q + ".bn1"), act=ACT_RELU, device=dev)
+        self.conv2 = ops.Conv2d(sd[q + ".conv2.weight"], None, padding=1, bn=bn_params(sd, q + ".bn2"), act=ACT_RELU | ACT_POST_FIRST, device=dev)
         self.down = None
         if (q + ".downsample.0.weight") in sd:
-            self.down = ops.Conv2d(sd[q + ".downsample.0.weight"], None, stride=stride, bn=_bn(sd, q + ".downsample.1"), device=dev)
+            self.down = ops.Conv2d(sd[q + ".downsample.0.weight"], None, stride=stride, bn=bn_params(sd, q + ".downsample.1"), device=dev)
 
 
 class _Triple:
     """conv-bn-relu x 2 then (conv | convT)-bn-relu: double_conv (:22-52) / double_conv_up (:54-75)."""
 
     def __init__(self, sd, p, up, dev):
-        cbr = lambda i: ops.Conv2d(sd[f"{p}.conv.{i}.weight"], None, padding=1, bn=_bn(sd, f"{p}.conv.{i + 1}"), act=ACT_RELU, device=dev)
+        cbr = lambda i: ops.Conv2d(sd[f"{p}.conv.{i}.weight"], None, padding=1, bn=bn_params(sd, f"{p}.conv.{i + 1}"), act=ACT_RELU, device=dev)
         self.a, self.b = cbr(0), cbr(3)
         if up:
-            self.c = ops.ConvTranspose2d(sd[f"{p}.conv.6.weight"], None, stride=2, padding=1, bn=_bn(sd, f"{p}.conv.7"), act=ACT_RELU, device=dev)
+            self.c = ops.ConvTranspose2d(sd[f"{p}.conv.6.weight"], None, stride=2, padding=1, bn=bn_params(sd, f"{p}.conv.7"), act=ACT_RELU, device=dev)
         else:
             self.c = cbr(6)
 
 
-class DbnetEngine:
+class DbnetEngine(ops.Engine):
     """Batched default-detector network: u8 pages (H, W multiples of 64) -> (db [B,2,H,W] after sigmoid, mask [B,H/2,W/2])."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], device="cuda"):
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         p = "backbone"
-        self.stem = ops.Conv2d(sd[p + ".conv1.weight"], None, stride=2, padding=3, bn=_bn(sd, p + ".bn1"), act=ACT_RELU, device=dev)
+        self.stem = ops.Conv2d(sd[p + ".conv1.weight"], None, stride=2, padding=3, bn=bn_params(sd, p + ".bn1"), act=ACT_RELU, device=dev)
         self.layers = []
         for li, (planes, n, stride) in enumerate(RESNET34_LAYERS, start=1):
             self.layers.append([_Basic(sd, f"{p}.layer{li}.{b}", stride if b == 0 else 1, dev) for b in range(n)])
@@ -60,8 +57,8 @@ class DbnetEngine:
         self.ups = [_Triple(sd, f"upconv{j}", True, dev) for j in range(1, 8)]
         d = "conv_db"
         def branch(q, first_bias, last_act):
-            c0 = ops.Conv2d(sd[q + ".0.weight"], sd[q + ".0.bias"] if first_bias else None, padding=1, bn=_bn(sd, q + ".1"), act=ACT_RELU, device=dev)
-            t1 = ops.ConvTranspose2d(sd[q + ".3.weight"], sd[q + ".3.bias"], stride=2, padding=1, bn=_bn(sd, q + ".4"), act=ACT_RELU, device=dev)
+            c0 = ops.Conv2d(sd[q + ".0.weight"], sd[q + ".0.bias"] if first_bias else None, padding=1, bn=bn_params(sd, q + ".1"), act=ACT_RELU, device=dev)
+            t1 = ops.ConvTranspose2d(sd[q + ".3.weight"], sd[q + ".3.bias"], stride=2, padding=1, bn=bn_params(sd, q + ".4"), act=ACT_RELU, device=dev)
             t2 = ops.ConvTranspose2d(sd[q + ".6.weight"], sd[q + ".6.bias"], stride=2, padding=1, act=last_act, device=dev)
             return c0, t1, t2
         # det_batch_forward_default applies sigmoid to BOTH planes (default.py:23): logits -> sigmoid; the threshold map, which
@@ -70,14 +67,6 @@ class DbnetEngine:
         self.thresh = branch(d + ".thresh", False, ACT_SIGMOID)
         self.mask_convs = [ops.Conv2d(sd[f"conv_mask.{i}.weight"], sd[f"conv_mask.{i}.bias"], padding=1, act=ACT_RELU, device=dev) for i in (0, 2, 4)]
         self.mask_out = ops.Conv2d(sd["conv_mask.6.weight"], sd["conv_mask.6.bias"], act=ACT_SIGMOID, device=dev)
-        self._ws = ops.Workspace(self.device)
-
-    def _buf(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        """Named workspace slab, grown to the largest request (ops.Workspace): memory is bounded by the largest page seen."""
-        return self._ws.buf(name, *shape, dtype=dtype)
-
-    def release_workspace(self):
-        self._ws.release()
 
     def _triple(self, tr: _Triple, x, out, tag):
         B, H, W, _ = x.shape

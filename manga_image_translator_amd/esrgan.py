@@ -37,11 +37,12 @@ class _RDB:
                                 out_scale=torch.full((NF,), 0.2))
 
 
-class EsrganEngine:
+class EsrganEngine(ops.Engine):
     """Batched 4x upscaler: u8 RGB pages [B,H,W,3] -> u8 RGB [B,4H,4W,3] (device tensors)."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], nb: int = 23, device="cuda"):
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         self.nb = nb
         w0 = sd["model.0.weight"].detach().float().flip(1)  # network input is BGR (:541): flip the input channels instead
         self.fea = ops.Conv2d(w0, sd["model.0.bias"], padding=1, device=dev)
@@ -53,14 +54,6 @@ class EsrganEngine:
         # output is BGR (:545 flips back): emit RGB directly by flipping the output channels
         self.hr1 = ops.ConvSmallCout(sd["model.10.weight"].detach().float().flip(0), sd["model.10.bias"].detach().float().flip(0),
                                      pad_mode=PAD_ZERO, device=dev)
-        self._ws = ops.Workspace(self.device)
-
-    def _buf(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        """Named workspace slab, grown to the largest request (ops.Workspace): memory is bounded by the largest page seen."""
-        return self._ws.buf(name, *shape, dtype=dtype)
-
-    def release_workspace(self):
-        self._ws.release()
 
     @torch.no_grad()
     def forward(self, img_u8: torch.Tensor, taps=None) -> torch.Tensor:

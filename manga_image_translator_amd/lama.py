@@ -26,23 +26,15 @@ import torch
 
 from . import lib as _lib
 from . import ops
-from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, PAD_REFLECT, PAD_ZERO, conv_gemm_desc, launch_conv_gemm, tensor_map
+from .ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, PAD_REFLECT, PAD_ZERO, bn_params, conv_gemm_desc, launch_conv_gemm, tensor_map
 
 LOCAL_C, GLOBAL_C, SPEC_C = 128, 384, 192
 MPE_S = 256
 
 
-def _bn(sd, prefix, eps=1e-5):
-    return (sd[prefix + ".weight"], sd[prefix + ".bias"], sd[prefix + ".running_mean"], sd[prefix + ".running_var"], eps)
-
-
 def _cat_bn(sd, p1, p2):
-    a, b = _bn(sd, p1), _bn(sd, p2)
+    a, b = bn_params(sd, p1), bn_params(sd, p2)
     return tuple(torch.cat([x, y]) for x, y in zip(a[:4], b[:4])) + (a[4],)
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 # ------------------------------------------------------------------------------------------
@@ -59,7 +51,7 @@ def dft_matrices(h: int, w: int):
                        imaginary parts of the DC / Nyquist bins are ignored exactly like pocketfft's c2r)
     """
     wk = w // 2 + 1
-    wp = _round_up(w, 16)  # K of the GEMM: a multiple of the K-tile keeps it on conv_gemm's fast path
+    wp = ops._round_up(w, 16)  # K of the GEMM: a multiple of the K-tile keeps it on conv_gemm's fast path
     kw = np.arange(wk)[:, None]
     xs = np.arange(w)[None, :]
     ang = 2.0 * np.pi * ((kw * xs) % w) / w
@@ -72,13 +64,13 @@ def dft_matrices(h: int, w: int):
     angh = 2.0 * np.pi * ((kh * ys) % h) / h
     sh = 1.0 / math.sqrt(h)
     Gr, Gi = np.cos(angh) * sh, -np.sin(angh) * sh
-    k2p = _round_up(2 * h, 16)
+    k2p = ops._round_up(2 * h, 16)
     G2 = np.zeros((2 * h, k2p), dtype=np.float64)
     G2[:, :2 * h] = np.block([[Gr, -Gi], [Gi, Gr]])
     Gri, Gii = np.cos(angh) * sh, np.sin(angh) * sh
     G2i = np.zeros((2 * h, k2p), dtype=np.float64)
     G2i[:, :2 * h] = np.block([[Gri, -Gii], [Gii, Gri]])
-    kp = _round_up(2 * wk, 16)
+    kp = ops._round_up(2 * wk, 16)
     a = np.full(wk, 2.0)
     a[0] = 1.0
     if w % 2 == 0:
@@ -189,26 +181,26 @@ class _FFC:
         # what direct() needs and nothing else of the state dict: the three 3x3 weights and bn_l, as the checkpoint's own tensors (no
         # copy; the rest of the checkpoint can be freed by its owner).  Dropped once direct() has packed them.
         self._direct_src = (sd[p + ".ffc.convl2l.weight"], sd[p + ".ffc.convg2l.weight"], sd[p + ".ffc.convl2g.weight"],
-                            _bn(sd, p + ".bn_l"), device) if winograd else None
+                            bn_params(sd, p + ".bn_l"), device) if winograd else None
         if winograd:  # F(4x4, 3x3): both convs read the same transformed input (convl2g its first 128 channels)
-            self.to_l = ops.WinogradConv3x3(w_l, None, pad_mode=PAD_REFLECT, bn=_bn(sd, p + ".bn_l"), act=ACT_RELU, device=device)
+            self.to_l = ops.WinogradConv3x3(w_l, None, pad_mode=PAD_REFLECT, bn=bn_params(sd, p + ".bn_l"), act=ACT_RELU, device=device)
             self.l2g = ops.WinogradConv3x3(sd[p + ".ffc.convl2g.weight"], None, pad_mode=PAD_REFLECT, device=device)
         else:
-            self.to_l = ops.Conv2d(w_l, None, padding=1, pad_mode=PAD_REFLECT, bn=_bn(sd, p + ".bn_l"), act=ACT_RELU,
+            self.to_l = ops.Conv2d(w_l, None, padding=1, pad_mode=PAD_REFLECT, bn=bn_params(sd, p + ".bn_l"), act=ACT_RELU,
                                    device=device)
             self.l2g = ops.Conv2d(sd[p + ".ffc.convl2g.weight"], None, padding=1, pad_mode=PAD_REFLECT, device=device)
         st = p + ".ffc.convg2g"
-        self.st_in = ops.Conv2d(sd[st + ".conv1.0.weight"], None, bn=_bn(sd, st + ".conv1.1"), act=ACT_RELU, device=device)
+        self.st_in = ops.Conv2d(sd[st + ".conv1.0.weight"], None, bn=bn_params(sd, st + ".conv1.1"), act=ACT_RELU, device=device)
         # spectral 1x1 conv: reference channel index is c*2 + t (:229-231,245-246); ours is planar t*C + c
         wf = sd[st + ".fu.conv_layer.weight"].reshape(SPEC_C, 2, SPEC_C, 2)  # [c_out, t_out, c_in, t_in]
         wf = wf.permute(3, 2, 1, 0).reshape(2 * SPEC_C, 2 * SPEC_C)  # [(t_in, c_in), (t_out, c_out)]
         self.fu_w, self.fu_Kp, self.fu_Np = ops.pack_weight_kn(wf, device)
-        g, b, m, v, eps = _bn(sd, st + ".fu.bn")
+        g, b, m, v, eps = bn_params(sd, st + ".fu.bn")
         perm = lambda t: t.reshape(SPEC_C, 2).t().reshape(-1)
         sc, bi = ops.fold_bn(perm(g), perm(b), perm(m), perm(v), eps)
         self.fu_scale, self.fu_bias = sc.to(device), bi.to(device)
         # conv2 (192->384) carries the global branch's BN + ReLU (+ pre = convl2g(x_l), + residual)
-        self.st_out = ops.Conv2d(sd[st + ".conv2.weight"], None, bn=_bn(sd, p + ".bn_g"), act=ACT_RELU, device=device)
+        self.st_out = ops.Conv2d(sd[st + ".conv2.weight"], None, bn=bn_params(sd, p + ".bn_g"), act=ACT_RELU, device=device)
 
     def direct(self):
         """(to_l, l2g) in the direct 9-tap form.  Built on the first call of a Winograd engine's bf16 precision (F(4x4, 3x3) with bf16
@@ -225,25 +217,25 @@ class _FFC:
         return self._direct
 
 
-class LamaEngine:
+class LamaEngine(ops.Engine):
     """Batched LaMa generator. ``forward(img_u8[B,H,W,3], mask_u8[B,H,W]) -> u8 [B,H,W,3]`` (device tensors)."""
 
     def __init__(self, gen_sd: Dict[str, torch.Tensor], mpe_sd: Optional[Dict[str, torch.Tensor]] = None,
                  n_blocks: int = 9, device="cuda", fft_h: bool = True, winograd: bool = True, fft_w: bool = True,
                  row_packed_stem: bool = True):
-        self.device = torch.device(device)
+        super().__init__(device)
         self.winograd = winograd  # False: the FFC blocks' 3x3 convolutions in direct (9-tap) form, for A/B comparison
         self.fft_h = fft_h  # False: keep the H-axis transform on the dense DFT GEMM (for A/B comparison)
         self.fft_w = fft_w  # False: keep the W-axis transform on the dense DFT GEMM (for A/B comparison)
         self.n_blocks = n_blocks
         sd, dev = gen_sd, self.device
         self.stem = ops.Conv2d(sd["model.1.ffc.convl2l.weight"], None, padding=3, pad_mode=PAD_REFLECT,
-                               bn=_bn(sd, "model.1.bn_l"), act=ACT_RELU, device=dev)
+                               bn=bn_params(sd, "model.1.bn_l"), act=ACT_RELU, device=dev)
         self.stem_packed = _RowPackedStem(self.stem, sd["model.1.ffc.convl2l.weight"], dev) if row_packed_stem else None
         self.down1 = ops.Conv2d(sd["model.2.ffc.convl2l.weight"], None, stride=2, padding=1, pad_mode=PAD_REFLECT,
-                                bn=_bn(sd, "model.2.bn_l"), act=ACT_RELU, device=dev)
+                                bn=bn_params(sd, "model.2.bn_l"), act=ACT_RELU, device=dev)
         self.down2 = ops.Conv2d(sd["model.3.ffc.convl2l.weight"], None, stride=2, padding=1, pad_mode=PAD_REFLECT,
-                                bn=_bn(sd, "model.3.bn_l"), act=ACT_RELU, device=dev)
+                                bn=bn_params(sd, "model.3.bn_l"), act=ACT_RELU, device=dev)
         w3 = torch.cat([sd["model.4.ffc.convl2l.weight"], sd["model.4.ffc.convl2g.weight"]], dim=0)  # 256 -> 128+384
         self.down3 = ops.Conv2d(w3, None, stride=2, padding=1, pad_mode=PAD_REFLECT,
                                 bn=_cat_bn(sd, "model.4.bn_l", "model.4.bn_g"), act=ACT_RELU, device=dev)
@@ -254,7 +246,7 @@ class LamaEngine:
         for i in range(3):
             p = base + 3 * i
             self.ups.append(ops.ConvTranspose2d(sd[f"model.{p}.weight"], sd[f"model.{p}.bias"], stride=2, padding=1,
-                                                output_padding=1, bn=_bn(sd, f"model.{p + 1}"), act=ACT_RELU, device=dev))
+                                                output_padding=1, bn=bn_params(sd, f"model.{p + 1}"), act=ACT_RELU, device=dev))
         p = base + 10
         self.out_conv = ops.ConvSmallCout(sd[f"model.{p}.weight"], sd[f"model.{p}.bias"], pad_mode=PAD_REFLECT,
                                           act=ACT_SIGMOID, device=dev)
@@ -279,19 +271,14 @@ class LamaEngine:
         # LDS-DMA kernel, round 6), 16 = four 16-channel planes (its register-staged kernel, round 5), 0 = NHWC — same values
         self.planar_tail = 4
         self.mpe_in_stem = True   # False: the separate mit_lama_mpe_add pass (tests)
-        self._ws = ops.Workspace(self.device)
         self._tw: Dict[int, torch.Tensor] = {}
         self._tw_rows: Dict[int, torch.Tensor] = {}
         self._dft = ops.ShapeCache(4)       # per-(h, w) DFT matrices: a few page shapes stay resident, older ones are dropped
         self._mpe_tabs = ops.ShapeCache(4)  # per-(H, W) resize tap tables of the MPE index kernels
 
     # -- workspace -------------------------------------------------------------------------
-    def _buf(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        """Named workspace slab, grown to the largest request (ops.Workspace): memory is bounded by the largest page seen."""
-        return self._ws.buf(name, *shape, dtype=dtype)
-
     def release_workspace(self):
-        self._ws.release()
+        super().release_workspace()
         self._dft.clear()
         self._mpe_tabs.clear()
 

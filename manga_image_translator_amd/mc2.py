@@ -28,7 +28,7 @@ import torch
 
 from . import imgproc, mc2_schema as S, ops, synth
 from . import lib as _lib
-from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU
+from .ops import ACT_LEAKY, ACT_NONE, ACT_RELU, bn_params
 
 LEAK = 0.2
 FFD_CAP = 1200
@@ -36,10 +36,6 @@ FFD_CAP = 1200
 
 def _st():
     return C.c_void_p(ops.current_stream())
-
-
-def _bn(sd, p):
-    return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"], 1e-5)
 
 
 class _Grouped:
@@ -95,15 +91,16 @@ class _PixelShuffleConv:
             ops.launch_conv_gemm(d)
 
 
-class Mc2Engine:
+class Mc2Engine(ops.Engine):
     """``denoise`` (FFDNet), ``colorize`` (the generator) and ``forward`` (the whole ``_infer``) for B pages of one size."""
 
     def __init__(self, generator_sd: Dict[str, torch.Tensor], denoiser_sd: Optional[Dict[str, torch.Tensor]] = None, device="cuda"):
         synth.check_state_dict(generator_sd, S.generator_schema(), "mc2 generator")
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         g = generator_sd
         # encoder
-        self.conv1 = ops.Conv2d(g["encoder.conv1.weight"], stride=2, padding=3, bn=_bn(g, "encoder.bn1"), act=ACT_RELU, device=dev)
+        self.conv1 = ops.Conv2d(g["encoder.conv1.weight"], stride=2, padding=3, bn=bn_params(g, "encoder.bn1"), act=ACT_RELU, device=dev)
         self.layers = []
         inplanes = 64
         for layer, planes, blocks, stride in S.ENCODER:
@@ -112,12 +109,12 @@ class Mc2Engine:
                 p = f"encoder.layer{layer}.{i}"
                 s = stride if i == 0 else 1
                 mid, out = 2 * planes, 4 * planes
-                blk = dict(c1=ops.Conv2d(g[p + ".conv1.weight"], bn=_bn(g, p + ".bn1"), act=ACT_RELU, device=dev),
-                           c2=_Grouped(g[p + ".conv2.weight"], mid, s, 1, ACT_RELU, bn=_bn(g, p + ".bn2"), device=dev),
-                           c3=ops.Conv2d(g[p + ".conv3.weight"], bn=_bn(g, p + ".bn3"), device=dev),
+                blk = dict(c1=ops.Conv2d(g[p + ".conv1.weight"], bn=bn_params(g, p + ".bn1"), act=ACT_RELU, device=dev),
+                           c2=_Grouped(g[p + ".conv2.weight"], mid, s, 1, ACT_RELU, bn=bn_params(g, p + ".bn2"), device=dev),
+                           c3=ops.Conv2d(g[p + ".conv3.weight"], bn=bn_params(g, p + ".bn3"), device=dev),
                            se=_SE(g, p + ".selayer", dev), stride=s, mid=mid, out=out)
                 if i == 0:
-                    blk["ds"] = ops.Conv2d(g[p + ".downsample.0.weight"], stride=s, bn=_bn(g, p + ".downsample.1"), device=dev)
+                    blk["ds"] = ops.Conv2d(g[p + ".downsample.0.weight"], stride=s, bn=bn_params(g, p + ".downsample.1"), device=dev)
                 blks.append(blk)
                 inplanes = out
             self.layers.append(blks)
@@ -150,15 +147,8 @@ class Mc2Engine:
             p = "intermediate_dncnn.itermediate_dncnn"
             self.ffd = [ops.Conv2d(f[f"{p}.0.weight"], padding=1, act=ACT_RELU, device=dev)]
             for k in range(S.FFD_LAYERS - 2):
-                self.ffd.append(ops.Conv2d(f[f"{p}.{2 + 3 * k}.weight"], padding=1, bn=_bn(f, f"{p}.{3 + 3 * k}"), act=ACT_RELU, device=dev))
+                self.ffd.append(ops.Conv2d(f[f"{p}.{2 + 3 * k}.weight"], padding=1, bn=bn_params(f, f"{p}.{3 + 3 * k}"), act=ACT_RELU, device=dev))
             self.ffd.append(ops.Conv2d(f[f"{p}.{2 + 3 * (S.FFD_LAYERS - 2)}.weight"], padding=1, device=dev))
-        self._ws = ops.Workspace(dev)
-
-    def _buf(self, name, *shape, dtype=torch.float32):
-        return self._ws.buf(name, *shape, dtype=dtype)
-
-    def release_workspace(self):
-        self._ws.release()
 
     # -- squeeze-and-excitation --------------------------------------------------------------------------------------------------
     def se(self, se: _SE, t: torch.Tensor, res: torch.Tensor, out: torch.Tensor, act: int):

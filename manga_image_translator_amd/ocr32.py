@@ -15,14 +15,15 @@ MI355X layout
 from __future__ import annotations
 
 import ctypes as C
-import math
-from typing import Dict, List, Optional, Sequence, Tuple
+import functools
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import lib as _lib
 from . import ops
+from . import textline as TL
 from .lib import MitOcr32DecodeArgs, MitOcr32Decoder
 from .ocr48 import Linear
 from .ocr_ctc import FanBackbone
@@ -42,12 +43,13 @@ def _in_proj(sd, p, device, part: slice, scaled: bool):
     return Linear(w, b, device, sc)
 
 
-class Ocr32Engine:
+class Ocr32Engine(ops.Engine):
     """encode(): u8 line crops of one chunk -> cross-attention K / V of the encoder memory; decode(): beam search over any number of
     lines; recognize_lines(): a page's quads -> tokens / probabilities / colours in the reference's processing order."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], dict_size: int, device="cuda"):
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         self.dict_size = dict_size
         self.backbone = FanBackbone(sd, dev, LAYERS, 2)
         pe = sd["pe.pe"].detach().float().reshape(-1, EMBD)
@@ -88,19 +90,6 @@ class Ocr32Engine:
         d.color1, d.color_heads = self.color1.c_struct(), self.color_heads.c_struct()
         d.dict_size, d.pe_len = dict_size, self.pe.shape[0]
         self.dec = d
-        self._ws: Dict[Tuple, torch.Tensor] = {}
-
-    def _buf(self, name, *shape, dtype=torch.float32):
-        n = max(int(math.prod(shape)), 1)
-        key = (name, dtype)
-        t = self._ws.get(key)
-        if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t[:n].view(*shape)
-
-    def release_workspace(self):
-        self._ws.clear()
 
     @staticmethod
     def valid_len(width: int, L: int) -> int:
@@ -218,24 +207,11 @@ class Ocr32Engine:
         return out
 
     # -- Model32pxOCR._infer's batching (:68-87) ---------------------------------------------------------------------
-    @staticmethod
-    def make_chunks(region_imgs: List[np.ndarray], max_chunk_size: int = 16):
-        perm = sorted(range(len(region_imgs)), key=lambda i: region_imgs[i].shape[1])
-        for c in range(0, len(perm), max_chunk_size):
-            indices = perm[c:c + max_chunk_size]
-            widths = [region_imgs[i].shape[1] for i in indices]
-            max_width = 4 * (max(widths) + 7) // 4   # == max + 7 (:78); no + 128 here
-            region = np.zeros((len(indices), TEXT_HEIGHT, max_width, 3), dtype=np.uint8)
-            for j, i in enumerate(indices):
-                region[j, :, :widths[j], :] = region_imgs[i]
-            yield indices, widths, region
+    make_chunks = staticmethod(functools.partial(TL.pack_chunks, height=TEXT_HEIGHT))   # max_w + 7 (:78); no + 128 here
 
     def decode_chunks(self, encoded, max_seq_length: int, trace: bool = False, tiled: bool = False):
         """Pool the (mem_k, mem_v, mem_len, L) of several chunks (zero-padded to the longest memory; the pad is masked) and decode once."""
-        Lmax = max(e[3] for e in encoded)
-        pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(N_DEC, m.shape[1], Lmax - m.shape[2], EMBD)], 2)
-        mem_k = torch.cat([pad(e[0]) for e in encoded], 1)
-        mem_v = torch.cat([pad(e[1]) for e in encoded], 1)
+        mem_k, mem_v = TL.pool_memories([e[0] for e in encoded]), TL.pool_memories([e[1] for e in encoded])
         return self.decode(mem_k, mem_v, torch.cat([e[2] for e in encoded]), max_seq_length, trace=trace, tiled=tiled)
 
     @torch.no_grad()
@@ -250,42 +226,18 @@ class Ocr32Engine:
         return out
 
     @torch.no_grad()
-    def rectify(self, page_u8: torch.Tensor, records: np.ndarray, wp: int) -> torch.Tensor:
-        """Lines of ``records`` (textline.WARP_LINE_DTYPE) rectified into one zero-padded chunk u8 [n, 32, wp, 3] (mit_ocr_warp_lines)."""
-        n = len(records)
-        records = records.copy()
-        records["out_row"] = np.arange(n)
-        lines_dev = torch.frombuffer(bytearray(records.tobytes()), dtype=torch.uint8).to(self.device)
-        region = torch.empty(n, TEXT_HEIGHT, wp, 3, dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.load().mit_ocr_warp_lines(page_u8.data_ptr(), page_u8.shape[1], page_u8.shape[2], lines_dev.data_ptr(), n,
-                                                  region.data_ptr(), TEXT_HEIGHT, wp, C.c_void_p(ops.current_stream())), "mit_ocr_warp_lines")
-        return region
-
-    @torch.no_grad()
     def recognize_lines(self, page_u8: torch.Tensor, quads, directions, max_seq_length: int = 255, reject=None):
         """page_u8 [1,H,W,3] u8 (device); quads = textline.Quadrilateral list, directions per quad.  Every line is rectified on the GPU
         at height 32 straight into its chunk tensor, chunks (sorted by crop width, 16 lines, padded to max + 7) are encoded one by one and
         all lines decoded in one pooled beam search.  ``reject(crop u8 [32, w, 3] ndarray) -> bool`` (optional): a rejected line's rows
         are zeroed before encoding and it is still decoded, as the reference's ``continue`` leaves it (:84-86).
         Returns decode()'s dict plus ``order`` (quad index per result row)."""
-        from . import textline as TL
-
         if page_u8.dtype != torch.uint8 or page_u8.dim() != 4 or page_u8.shape[0] != 1 or page_u8.shape[-1] != 3:
             raise ValueError(f"recognize_lines expects u8 [1,H,W,3], got {page_u8.dtype} {tuple(page_u8.shape)}")
-        page_u8 = page_u8.contiguous()
-        H, W = int(page_u8.shape[1]), int(page_u8.shape[2])
         if len(quads) == 0:
             return dict(order=[], tokens=None)
-        rec = TL.warp_plans(quads, list(directions), H, W, TEXT_HEIGHT)
-        widths = np.where(rec["vertical"] != 0, rec["dh"], rec["dw"]).tolist()
         order, enc = [], []
-        for idx, ws, wp in TL.chunk_plan(widths):
-            region = self.rectify(page_u8, rec[idx], wp)
-            if reject is not None:
-                host = region.cpu().numpy()
-                for j, w_line in enumerate(ws):
-                    if reject(host[j, :, :w_line]):
-                        region[j] = 0
+        for idx, ws, region in TL.rectified_chunks(page_u8.contiguous(), quads, directions, TEXT_HEIGHT, reject=reject):
             enc.append(self.encode(region, ws))
             order += list(idx)
         out = self.decode_chunks(enc, max_seq_length)

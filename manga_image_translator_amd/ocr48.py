@@ -15,23 +15,20 @@ MI355X layout
 from __future__ import annotations
 
 import ctypes as C
-import math
-from typing import Dict, List, Optional, Sequence, Tuple
+import functools
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import lib as _lib
 from . import ops
+from . import textline as TL
 from .lib import MitLinear, MitOcr48DecodeArgs, MitOcr48Decoder, MitXposTables
-from .ops import ACT_GELU, ACT_NONE, ACT_RELU, launch_conv_gemm, conv_gemm_desc, tensor_map
+from .ops import ACT_GELU, ACT_NONE, ACT_RELU, bn_params, launch_conv_gemm, conv_gemm_desc, tensor_map
 
 EMBD, HEADS, HEAD_DIM, FF = 320, 4, 80, 2048
 XPOS_IMAX, XPOS_PMAX = 2048, 1024
-
-
-def _bn(sd, p, eps=1e-5):
-    return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"], eps)
 
 
 class Linear:
@@ -125,7 +122,7 @@ class _Block:
         self.ks = ks
         w = sd[p + ".dwconv.weight"].detach().float()  # [dim, 1, ks, ks]
         self.dw_w = w.reshape(dim, ks * ks).t().contiguous().to(device)  # [ks*ks][dim]
-        sc, bi = ops.fold_bn(*_bn(sd, p + ".norm", 1e-6), conv_bias=sd[p + ".dwconv.bias"])
+        sc, bi = ops.fold_bn(*bn_params(sd, p + ".norm", 1e-6), conv_bias=sd[p + ".dwconv.bias"])
         self.dw_scale, self.dw_bias = sc.to(device), bi.to(device)
         self.pw1 = ops.Conv2d(sd[p + ".pwconv1.weight"], sd[p + ".pwconv1.bias"], act=ACT_GELU, device=device)
         self.pw2 = ops.Conv2d(sd[p + ".pwconv2.weight"], sd[p + ".pwconv2.bias"], out_scale=sd[p + ".gamma"], device=device)
@@ -178,14 +175,15 @@ def set_fused_mlp(on: bool) -> bool:
     return prev
 
 
-class Ocr48Engine:
+class Ocr48Engine(ops.Engine):
     """encode(): u8 line crops of one chunk -> encoder memory; decode(): beam search over any number of lines."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], dict_size: int, device="cuda"):
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         self.dict_size = dict_size
         cbr = lambda p, i, s, pad: ops.Conv2d(sd[f"{p}.{i}.weight"], sd[f"{p}.{i}.bias"], stride=s, padding=pad,
-                                              bn=_bn(sd, f"{p}.{i + 1}"), act=ACT_RELU, device=dev)
+                                              bn=bn_params(sd, f"{p}.{i + 1}"), act=ACT_RELU, device=dev)
         b = "backbone."
         self.stem = [cbr(b + "stem", 0, 1, 3), cbr(b + "stem", 3, 2, 0), cbr(b + "stem", 6, 1, 1)]
         self.stages = []
@@ -240,23 +238,8 @@ class Ocr48Engine:
         d.xpos = self.xpos
         d.dict_size = dict_size
         self.dec = d
-        self._ws: Dict[Tuple, torch.Tensor] = {}
         self.lines_attention_max_len = int(_lib.load().mit_attention_lines_xpos_max_len(HEAD_DIM))   # longest line of the one-launch form
         self.per_chunk_attention = False   # True: the encoder's attention chunk by chunk (rotate q, rotate k, attention): the reference form for tests
-
-    def _buf(self, name, *shape, dtype=torch.float32):
-        """Named workspace slab, grown to the largest request (chunk widths vary from call to call; all users are
-        ordered on one stream, so a slab can be re-viewed at a new shape by the next chunk)."""
-        n = max(int(math.prod(shape)), 1)
-        key = (name, dtype)
-        t = self._ws.get(key)
-        if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t[:n].view(*shape)
-
-    def release_workspace(self):
-        self._ws.clear()
 
     # -- ConvNext_FeatureExtractor.forward (:262-276) -----------------------------------------
     def _backbone(self, x: torch.Tensor, tag: str) -> torch.Tensor:
@@ -549,17 +532,7 @@ class Ocr48Engine:
         return out
 
     # -- host batching of Model48pxOCR._infer (:79-91) -----------------------------------------
-    @staticmethod
-    def make_chunks(region_imgs: List[np.ndarray], max_chunk_size: int = 16):
-        perm = sorted(range(len(region_imgs)), key=lambda i: region_imgs[i].shape[1])
-        for c in range(0, len(perm), max_chunk_size):
-            indices = perm[c:c + max_chunk_size]
-            widths = [region_imgs[i].shape[1] for i in indices]
-            max_width = 4 * (max(widths) + 7) // 4  # == max + 7, the reference's precedence quirk (:86)
-            region = np.zeros((len(indices), 48, max_width, 3), dtype=np.uint8)
-            for j, i in enumerate(indices):
-                region[j, :, :widths[j], :] = region_imgs[i]
-            yield indices, widths, region
+    make_chunks = staticmethod(functools.partial(TL.pack_chunks, height=48))
 
     @torch.no_grad()
     def recognize(self, region_imgs: List[np.ndarray], max_seq_length: int = 255, suppress_eos: bool = False):
@@ -571,9 +544,7 @@ class Ocr48Engine:
             mks.append(mk)
             mvs.append(mv)
             lens.append(kl)
-        Lmax = max(m.shape[2] for m in mks)
-        pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], EMBD)], 2)
-        mem_k, mem_v = torch.cat([pad(m) for m in mks], 1), torch.cat([pad(m) for m in mvs], 1)
+        mem_k, mem_v = TL.pool_memories(mks), TL.pool_memories(mvs)
         out = self.decode(mem_k, mem_v, torch.cat(lens), max_seq_length, suppress_eos)
         out["order"] = order
         return out
@@ -585,8 +556,6 @@ class Ocr48Engine:
 
         Returns a dict: ``records`` (WARP_LINE_DTYPE, one per line, ordered chunk by chunk), ``chunks``
         [(first_record, n_lines, widths, padded_width, page)], ``order`` [(page, line)] per record, ``klens`` int32, ``Lmax``."""
-        from . import textline as TL
-
         recs, chunks, order, klens = [], [], [], []
         n = 0
         for p, quads in enumerate(quads_per_page):
@@ -625,17 +594,11 @@ class Ocr48Engine:
         rows [first_record, first_record + n) of the pooled ``mem_k`` / ``mem_v`` [5, n_lines, Lmax, 320]."""
         if not chunk_ids:
             return
-        lib = _lib.load()
-        st = C.c_void_p(ops.current_stream())
-        H, W = plan["H"], plan["W"]
-        rec_bytes = plan["records"].dtype.itemsize
+        lines, rec_bytes = plan["lines_dev"].data_ptr(), plan["records"].dtype.itemsize
         regions = []
         for ci in chunk_ids:
             first, n, ws, wp, _ = plan["chunks"][ci]
-            region = torch.empty(n, 48, wp, 3, dtype=torch.uint8, device=self.device)
-            _lib.check(lib.mit_ocr_warp_lines(pages_u8.data_ptr(), H, W, plan["lines_dev"].data_ptr() + first * rec_bytes, n,
-                                              region.data_ptr(), 48, wp, st), "mit_ocr_warp_lines")
-            regions.append(region)
+            regions.append(TL.rectify(pages_u8, (lines + first * rec_bytes, n), 48, wp))
         firsts = [plan["chunks"][ci][0] for ci in chunk_ids]
         keep = self.encode_group(regions, plan["klen_dev"], mem_k.shape[2], mem_k, mem_v, firsts)
         plan["_keep"].append(keep)

@@ -15,27 +15,25 @@ on the chunk; chunks are therefore formed exactly as the reference does and run 
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+import functools
+from typing import Dict, List, Optional, Sequence
 
-import numpy as np
 import torch
 
 from . import lib as _lib
 from . import ops
+from . import textline as TL
 from .ocr48 import Linear
-from .ops import ACT_GELU, ACT_NONE, ACT_RELU
+from .ops import ACT_GELU, ACT_NONE, ACT_RELU, bn_params
 
 EMBD, HEADS, HEAD_DIM, FFN = 320, 8, 40, 1280
 CHANNELS = [80, 160, 320, 320]
 LAYERS = [4, 6, 8, 6]
-
-
-def _bn(sd, p, eps=1e-5):
-    return (sd[p + ".weight"], sd[p + ".bias"], sd[p + ".running_mean"], sd[p + ".running_var"], eps)
+CHUNK_EXTRA = 128   # columns the reference pads every chunk with beyond max_w + 7 (:84); the encoder sees them (no key mask)
 
 
 def _affine(sd, p, device):
-    sc, bi = ops.fold_bn(*_bn(sd, p))
+    sc, bi = ops.fold_bn(*bn_params(sd, p))
     return sc.to(device).contiguous(), bi.to(device).contiguous()
 
 
@@ -44,14 +42,14 @@ class _Block:
 
     def __init__(self, sd, p, inpl, planes, device, closing_bn=None):
         self.pre = _affine(sd, p + ".bn1", device)                       # relu(bn1(x)): elementwise (x also feeds the residual)
-        self.conv1 = ops.Conv2d(sd[p + ".conv1.weight"], None, padding=1, bn=_bn(sd, p + ".bn2"), act=ACT_RELU, device=device)
+        self.conv1 = ops.Conv2d(sd[p + ".conv1.weight"], None, padding=1, bn=bn_params(sd, p + ".bn2"), act=ACT_RELU, device=device)
         # conv2 (+ residual); the layer's closing bn + relu (:345-347 etc.) rides here for the last block: act((acc + res) * s + b)
         self.conv2 = ops.Conv2d(sd[p + ".conv2.weight"], None, padding=1, bn=closing_bn, act=ACT_RELU if closing_bn else ACT_NONE,
                                 device=device)
         self.closing = closing_bn is not None
         self.down = None
         if (p + ".downsample.1.weight") in sd:  # Sequential(BatchNorm2d, conv1x1) on the residual (:321-326): fold BN into the conv
-            g, b, m, v, eps = _bn(sd, p + ".downsample.0")
+            g, b, m, v, eps = bn_params(sd, p + ".downsample.0")
             s = (g.double() / torch.sqrt(v.double() + eps))
             t = b.double() - m.double() * s
             w = sd[p + ".downsample.1.weight"].double()                   # [planes, inpl, 1, 1]
@@ -66,13 +64,13 @@ class FanBackbone:
     def __init__(self, sd: Dict[str, torch.Tensor], device, layers: Sequence[int] = tuple(LAYERS), tail_kernel: int = 3):
         dev = device
         p = "backbone.ConvNet"
-        self.conv0_1 = ops.Conv2d(sd[p + ".conv0_1.weight"], None, padding=1, bn=_bn(sd, p + ".bn0_1"), act=ACT_RELU, device=dev)
+        self.conv0_1 = ops.Conv2d(sd[p + ".conv0_1.weight"], None, padding=1, bn=bn_params(sd, p + ".bn0_1"), act=ACT_RELU, device=dev)
         self.conv0_2 = ops.Conv2d(sd[p + ".conv0_2.weight"], None, padding=1, device=dev)
         self.layers: List[List[_Block]] = []
         self.tails = []
         inpl = 40
         for li, (planes, n) in enumerate(zip(CHANNELS, layers), start=1):
-            closing = _bn(sd, f"{p}.bn{li}") if li < 4 else _bn(sd, p + ".bn4_1")
+            closing = bn_params(sd, f"{p}.bn{li}") if li < 4 else bn_params(sd, p + ".bn4_1")
             blocks = []
             for b in range(n):
                 blocks.append(_Block(sd, f"{p}.layer{li}.{b}", inpl, planes, dev, closing_bn=closing if b == n - 1 else None))
@@ -82,9 +80,9 @@ class FanBackbone:
                 self.tails.append(ops.Conv2d(sd[f"{p}.conv{li}.weight"], None, padding=1, device=dev))
         # conv4_1 (s(2,1)) carries bn4_2 + relu, conv4_2 (p0) carries bn4_3 (:362-368)
         pad41 = (1, 1) if tail_kernel == 3 else (0, 1)
-        self.conv4_1 = ops.Conv2d(sd[p + ".conv4_1.weight"], None, stride=(2, 1), padding=pad41, bn=_bn(sd, p + ".bn4_2"),
+        self.conv4_1 = ops.Conv2d(sd[p + ".conv4_1.weight"], None, stride=(2, 1), padding=pad41, bn=bn_params(sd, p + ".bn4_2"),
                                   act=ACT_RELU, device=dev)
-        self.conv4_2 = ops.Conv2d(sd[p + ".conv4_2.weight"], None, padding=0, bn=_bn(sd, p + ".bn4_3"), device=dev)
+        self.conv4_2 = ops.Conv2d(sd[p + ".conv4_2.weight"], None, padding=0, bn=bn_params(sd, p + ".bn4_3"), device=dev)
 
     def out_width(self, Wp: int) -> int:
         """Feature columns for a padded crop width Wp (two 2 x 2 pools, then +1 at the third pool, +/- the tail convs)."""
@@ -146,11 +144,12 @@ class FanBackbone:
         return f
 
 
-class OcrCtcEngine:
+class OcrCtcEngine(ops.Engine):
     """forward(): u8 line crops of one reference chunk -> (logits [N,T,dict], colours [N,T,6]); decode(): greedy CTC."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], dict_size: int, device="cuda"):
-        self.device = dev = torch.device(device)
+        super().__init__(device)
+        dev = self.device
         self.dict_size = dict_size
         self.backbone = FanBackbone(sd, dev, LAYERS, 3)
         self.enc = []
@@ -173,19 +172,6 @@ class OcrCtcEngine:
         self.pred_ln = (sd["char_pred_norm.0.weight"].float().to(dev), sd["char_pred_norm.0.bias"].float().to(dev))
         self.char_pred = Linear(sd["char_pred.weight"], sd["char_pred.bias"], dev)
         self.color_pred = Linear(sd["color_pred1.0.weight"], sd["color_pred1.0.bias"], dev)
-        self._ws: Dict[Tuple, torch.Tensor] = {}
-
-    def _buf(self, name, *shape, dtype=torch.float32):
-        n = max(int(np.prod(shape)), 1)
-        key = (name, dtype)
-        t = self._ws.get(key)
-        if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=dtype, device=self.device)
-            self._ws[key] = t
-        return t[:n].view(*shape)
-
-    def release_workspace(self):
-        self._ws.clear()
 
     def _backbone(self, x: torch.Tensor) -> torch.Tensor:
         """ResNet.forward (:335-370). x [N,48,Wp,4] -> [N,1,T,320]."""
@@ -273,18 +259,8 @@ class OcrCtcEngine:
             out.append(line)
         return out
 
-    @staticmethod
-    def make_chunks(region_imgs: List[np.ndarray], max_chunk_size: int = 16):
-        """Model48pxCTCOCR._infer's batching (:77-88): sorted by width, groups of 16, padded to max_w + 7 + 128."""
-        perm = sorted(range(len(region_imgs)), key=lambda i: region_imgs[i].shape[1])
-        for c in range(0, len(perm), max_chunk_size):
-            indices = perm[c:c + max_chunk_size]
-            widths = [region_imgs[i].shape[1] for i in indices]
-            max_width = (4 * (max(widths) + 7) // 4) + 128
-            region = np.zeros((len(indices), 48, max_width, 3), dtype=np.uint8)
-            for j, i in enumerate(indices):
-                region[j, :, :widths[j], :] = region_imgs[i]
-            yield indices, widths, region
+    # Model48pxCTCOCR._infer's batching (:77-88): sorted by width, groups of 16, padded to max_w + 7 + 128
+    make_chunks = staticmethod(functools.partial(TL.pack_chunks, height=48, extra=CHUNK_EXTRA))
 
 
 def _sinus_pe(max_len: int, d_model: int) -> torch.Tensor:

@@ -47,9 +47,7 @@ class Workspace:
         self._slabs = {}
 
     def buf(self, name: str, *shape, dtype=torch.float32) -> torch.Tensor:
-        n = 1
-        for d in shape:
-            n *= int(d)
+        n = int(math.prod(shape))
         key = (name, dtype)
         t = self._slabs.get(key)
         if t is None or t.numel() < max(n, 1):
@@ -62,6 +60,30 @@ class Workspace:
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self._slabs.values())
+
+
+class Engine:
+    """Base of the model engines: the device and one ``Workspace``.  ``_buf(name, *shape)`` is a named slab grown to the largest
+    request, so an engine's memory is bounded by the largest page seen; ``release_workspace()`` hands the slabs back to the allocator
+    (the weights stay)."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        self._ws = Workspace(self.device)
+
+    @property
+    def _buf(self):
+        """``_buf(name, *shape, dtype=torch.float32)`` is the workspace's own method: one call deep, an engine asks for hundreds a step."""
+        return self._ws.buf
+
+    def release_workspace(self) -> None:
+        self._ws.release()
+
+
+def bn_params(sd, prefix: str, eps: float = 1e-5):
+    """(weight, bias, running_mean, running_var, eps) of the BatchNorm at ``prefix``: the ``bn=`` argument of the convolutions and the
+    arguments of ``fold_bn``."""
+    return (sd[prefix + ".weight"], sd[prefix + ".bias"], sd[prefix + ".running_mean"], sd[prefix + ".running_var"], eps)
 
 
 class ShapeCache:

@@ -136,11 +136,26 @@ def _own_quad(q) -> Quadrilateral:
     return q if type(q) is Quadrilateral else Quadrilateral(np.asarray(q.pts))
 
 
-def _weights_handed_over(plugin, *given) -> None:
-    """State dicts injected through the constructor stand for the checkpoint files: nothing is left to download, so
-    ModelWrapper.load() (utils/inference.py:330-338) must not try to fetch ``_MODEL_MAPPING`` (there is no network offline)."""
-    if all(g is not None for g in given):
-        plugin._downloaded = True
+class _EnginePlugin:
+    """What the plugins share around their engine.  A mixin listed before the reference's ``Offline*`` class (or its stand-alone mirror),
+    whose ``__init__`` it leaves alone: a plugin's constructor calls ``_hand_over`` once the base's has run."""
+
+    def _hand_over(self, weights, *also) -> None:
+        """The constructor's tail.  State dicts injected through the constructor (``also``: what else the model needs, e.g. the OCR
+        dictionary) stand for the checkpoint files: nothing is left to download, so ModelWrapper.load() (utils/inference.py:330-338)
+        must not try to fetch ``_MODEL_MAPPING`` (there is no network offline)."""
+        self._weights, self.engine = weights, None
+        if all(g is not None for g in (weights, *also)):
+            self._downloaded = True
+
+    async def _unload(self):
+        if self.engine is not None:
+            self.engine.release_workspace()  # device slabs go back to the allocator before the weights do
+        self.engine = None
+
+    def _page_on_device(self, image: np.ndarray) -> torch.Tensor:
+        """Host page [H,W,C] -> [1,H,W,C] on the engine's device: the page crosses PCIe once, as bytes."""
+        return torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device)[None]
 
 
 def _gpu_device(device: str) -> torch.device:
@@ -152,7 +167,30 @@ def _gpu_device(device: str) -> torch.device:
     return torch.device(device)
 
 
-class HipComicTextDetector(_DetBase):
+def _ocr_options(config, default_threshold: float) -> Tuple[float, int]:
+    """(probability threshold, ignore_bubble) of an OCR call: ``config.prob`` or the model's default, ``config.ignore_bubble`` or 0."""
+    threshold = default_threshold if config is None or getattr(config, "prob", None) is None else config.prob
+    ignore_bubble = int(getattr(config, "ignore_bubble", 0) or 0) if config is not None else 0
+    return threshold, ignore_bubble
+
+
+def _bubble_reject(ignore_bubble: int) -> Optional[Callable]:
+    """``textline.is_ignore`` at this setting as the ``reject`` of ``textline.rectified_chunks``; None where the filter is off (outside
+    1..50), so that no crop is fetched to the host for it."""
+    from . import textline as TL
+
+    return (lambda crop: TL.is_ignore(crop, ignore_bubble)) if 1 <= ignore_bubble <= 50 else None
+
+
+def _accept(q, text: str, prob: float, fg, bg):
+    """Write a recognised line's result on its Quadrilateral, the way every reference OCR does; returns the object."""
+    q.text, q.prob = text, prob
+    q.fg_r, q.fg_g, q.fg_b = fg
+    q.bg_r, q.bg_g, q.bg_b = bg
+    return q
+
+
+class HipComicTextDetector(_EnginePlugin, _DetBase):
     """``--detector ctd`` on the HIP engine."""
     _KEY = _key = "ctd_hip"
     # the torch checkpoint of the reference's own mapping (detection/ctd.py:63-74; its ONNX twin is the reference's CPU path)
@@ -167,10 +205,9 @@ class HipComicTextDetector(_DetBase):
     def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None,
                  boxes_from_maps: Optional[Callable] = None, refine: Optional[Callable] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._weights, self._boxes, self._refine = weights, boxes_from_maps, refine
-        self.engine = None
+        self._boxes, self._refine = boxes_from_maps, refine
         self.input_size = (1024, 1024)  # ctd.py:84: fixed, whatever detect_size the caller passes
-        _weights_handed_over(self, weights)
+        self._hand_over(weights)
 
     async def _load(self, device: str, input_size=1024, **_):
         from . import ctd
@@ -180,11 +217,6 @@ class HipComicTextDetector(_DetBase):
         self.engine = ctd.CtdEngine(w["ctd.yolo"], w["ctd.seg"], w["ctd.det"], device=dev)
         self.device, self.input_size = device, (input_size, input_size)
 
-    async def _unload(self):
-        if self.engine is not None:
-            self.engine.release_workspace()  # device slabs go back to the allocator before the weights do
-        self.engine = None
-
     @torch.no_grad()
     async def _infer(self, image: np.ndarray, detect_size: int, text_threshold: float, box_threshold: float,
                      unclip_ratio: float, verbose: bool = False):
@@ -193,7 +225,7 @@ class HipComicTextDetector(_DetBase):
         if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
             raise ValueError(f"expected uint8 RGB [H,W,3], got {image.dtype} {image.shape}")
         im_h, im_w = image.shape[:2]
-        page = torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device)[None]
+        page = self._page_on_device(image)
         from . import hostglue, imgproc, rearrange
 
         S = self.input_size[0]
@@ -236,7 +268,7 @@ class HipComicTextDetector(_DetBase):
         return lines.cpu().numpy(), self.engine.last_mask_f32.cpu().numpy()[:, None]
 
 
-class HipDefaultDetector(_DetBase):
+class HipDefaultDetector(_EnginePlugin, _DetBase):
     """``--detector default`` (DBNet on ResNet-34) on the HIP engine."""
     _KEY = _key = "default_hip"
     _MODEL_MAPPING: Dict = {  # detection/default.py:28-34
@@ -250,9 +282,8 @@ class HipDefaultDetector(_DetBase):
     def __init__(self, *args, weights: Optional[Dict[str, torch.Tensor]] = None, preprocess: Optional[Callable] = None,
                  boxes_from_maps: Optional[Callable] = None, resize2x: Optional[Callable] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._weights, self._pre, self._boxes, self._resize2x = weights, preprocess, boxes_from_maps, resize2x
-        self.engine = None
-        _weights_handed_over(self, weights)
+        self._pre, self._boxes, self._resize2x = preprocess, boxes_from_maps, resize2x
+        self._hand_over(weights)
 
     async def _load(self, device: str):
         from . import dbnet
@@ -260,15 +291,9 @@ class HipDefaultDetector(_DetBase):
         dev = _gpu_device(device)
         sd = self._weights
         if sd is None:
-            ck = torch.load(_ckpt_path(self, "detect-20241225.ckpt"), map_location="cpu")
-            sd = ck["model"] if "model" in ck else ck
+            sd = _bare_state_dict(torch.load(_ckpt_path(self, "detect-20241225.ckpt"), map_location="cpu"))
         self.engine = dbnet.DbnetEngine(sd, device=dev)
         self.device = device
-
-    async def _unload(self):
-        if self.engine is not None:
-            self.engine.release_workspace()  # device slabs go back to the allocator before the weights do
-        self.engine = None
 
     @torch.no_grad()
     async def _infer(self, image: np.ndarray, detect_size: int, text_threshold: float, box_threshold: float,
@@ -295,10 +320,9 @@ class HipDefaultDetector(_DetBase):
         else:
             if self._pre is not None:
                 img_resized, target_ratio, pad_w, pad_h = self._pre(image, detect_size)
-                page = torch.from_numpy(np.ascontiguousarray(img_resized)).to(self.engine.device)[None]
+                page = self._page_on_device(img_resized)
             else:  # cv2.bilateralFilter + resize_aspect_ratio (:62) on the device: the page crosses PCIe once, as bytes
-                page, target_ratio, pad_w, pad_h = default_preprocess_gpu(
-                    torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device), detect_size)
+                page, target_ratio, pad_w, pad_h = default_preprocess_gpu(self._page_on_device(image)[0], detect_size)
             ratio = 1 / target_ratio
             h, w = int(page.shape[1]), int(page.shape[2])
             db, mask = self.engine.forward(page)
@@ -325,7 +349,7 @@ class HipDefaultDetector(_DetBase):
         return textlines, np.clip(mask_resized * 255, 0, 255).astype(np.uint8), None
 
 
-class HipModel48pxOCR(_OcrBase):
+class HipModel48pxOCR(_EnginePlugin, _OcrBase):
     """``--ocr 48px`` on the HIP engine."""
     _KEY = _key = "48px_hip"
     _MODEL_MAPPING: Dict = {  # ocr/model_48px.py:28-37
@@ -342,9 +366,8 @@ class HipModel48pxOCR(_OcrBase):
     def __init__(self, *args, weights: Optional[Dict[str, torch.Tensor]] = None, dictionary: Optional[Sequence[str]] = None,
                  **kwargs):
         super().__init__(*args, **kwargs)
-        self._weights, self.dictionary = weights, dictionary
-        self.engine = None
-        _weights_handed_over(self, weights, dictionary)
+        self.dictionary = dictionary
+        self._hand_over(weights, dictionary)
 
     async def _load(self, device: str):
         from . import ocr48
@@ -354,11 +377,6 @@ class HipModel48pxOCR(_OcrBase):
             self._weights, self.dictionary = _load_ocr_checkpoint(self)
         self.engine = ocr48.Ocr48Engine(self._weights, len(self.dictionary), device=dev)
         self.device = device
-
-    async def _unload(self):
-        if self.engine is not None:
-            self.engine.release_workspace()  # device slabs go back to the allocator before the weights do
-        self.engine = None
 
     def _directions(self, textlines):
         """(line, direction) in processing order: the merge-graph majority vote of ocr/common.py:12-39 (the reference's own
@@ -371,34 +389,35 @@ class HipModel48pxOCR(_OcrBase):
         back = {id(o): q for o, q in zip(own, textlines)}
         return [(back[id(o)], d) for o, d in TL.generate_text_direction(own)]
 
+    def _prepare(self, textlines):
+        """-> (quads, dirs, own): the caller's lines in processing order, the direction of each, and the same lines in this package's
+        geometry type.  Three empty lists for a page without lines."""
+        pairs = self._directions(textlines)
+        quads = [q for q, _ in pairs]
+        return quads, [d for _, d in pairs], [_own_quad(q) for q in quads]
+
     @torch.no_grad()
     async def _infer(self, image: np.ndarray, textlines: List, config=None, verbose: bool = False, ignore_bubble: int = 0,
                      max_seq_length: int = 255, suppress_eos: bool = False):
         """Sets text / prob / fg_* / bg_* on the same Quadrilateral objects and returns those above the threshold,
         in the reference's sorted-by-width chunk order (model_48px.py:67-180)."""
-        threshold = 0.2 if config is None or getattr(config, "prob", None) is None else config.prob
-        pairs = self._directions(textlines)
-        if not pairs:
+        threshold, _ = _ocr_options(config, 0.2)
+        quads, dirs, own = self._prepare(textlines)
+        if not quads:
             return []
-        quads = [q for q, _ in pairs]
-        dirs = [[d for _, d in pairs]]
-        page = torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device)[None]
-        own = [_own_quad(q) for q in quads]  # geometry in this package's type
-        r = self.engine.recognize_pages(page, [own], max_seq_length=max_seq_length, suppress_eos=suppress_eos, directions=dirs)
+        r = self.engine.recognize_pages(self._page_on_device(image), [own], max_seq_length=max_seq_length, suppress_eos=suppress_eos,
+                                        directions=[dirs])
         toks, lens = r["tokens"].cpu().numpy(), r["length"].cpu().numpy()
         probs, cols = r["prob"].cpu().numpy(), r["colors"].cpu().numpy()
         out = []
         decoded = decode_lines(toks, lens, cols, self.dictionary, rows=[row for row in range(len(r["order"])) if probs[row] >= threshold])
         for row, (_, i) in enumerate(r["order"]):
             q, prob = quads[i], float(probs[row])
-            q.assigned_direction = dirs[0][i]
+            q.assigned_direction = dirs[i]
             if prob < threshold:
                 continue
             txt, fgc, bgc = decoded[row]            # (decode_line of the tokens after the start symbol)
-            q.text, q.prob = txt, prob
-            q.fg_r, q.fg_g, q.fg_b = fgc
-            q.bg_r, q.bg_g, q.bg_b = bgc
-            out.append(q)
+            out.append(_accept(q, txt, prob, fgc, bgc))
         return out
 
 
@@ -425,21 +444,7 @@ class HipModel48pxCTCOCR(HipModel48pxOCR):
         self.engine = ocr_ctc.OcrCtcEngine(self._weights, len(self.dictionary), device=dev)
         self.device = device
 
-    def _rectify(self, page: torch.Tensor, quads, dirs, idx, records: np.ndarray, wp: int) -> torch.Tensor:
-        """Lines ``idx`` of the page rectified into one zero-padded chunk tensor u8 [n, 48, wp, 3] on the device (mit_ocr_warp_lines:
-        get_transformed_region + the chunk packing of model_48px_ctc.py:83-91).  ``quads`` / ``dirs`` are not needed by the kernel — the
-        records carry the geometry — they are there for host stand-ins in tests."""
-        import ctypes as C
-
-        from . import lib as _lib, ops
-
-        dev = page.device
-        records["out_row"] = np.arange(len(idx))
-        lines_dev = torch.frombuffer(bytearray(records.tobytes()), dtype=torch.uint8).to(dev)
-        region = torch.empty(len(idx), 48, wp, 3, dtype=torch.uint8, device=dev)
-        _lib.check(_lib.load().mit_ocr_warp_lines(page.data_ptr(), page.shape[1], page.shape[2], lines_dev.data_ptr(), len(idx), region.data_ptr(), 48, wp,
-                                                  C.c_void_p(ops.current_stream())), "mit_ocr_warp_lines")
-        return region
+    _rectify = None   # a callable here replaces textline.rectify (``rectify_fn`` of textline.rectified_chunks): host stand-ins in tests
 
     @torch.no_grad()
     async def _infer(self, image: np.ndarray, textlines: List, config=None, verbose: bool = False):
@@ -447,30 +452,15 @@ class HipModel48pxCTCOCR(HipModel48pxOCR):
         exp(mean log-prob) against a 0.5 default threshold (:66,:124), colours average over non-space characters (:116-123).
         ``config.ignore_bubble`` in 1..50 applies the reference's frame / colour heuristic to every rectified crop (:91-93, utils/bubble.py):
         a rejected line's row of the chunk stays zero and is recognised as such, exactly as the reference's ``continue`` leaves it."""
-        from . import textline as TL
+        from . import ocr_ctc, textline as TL
 
-        threshold = 0.5 if config is None or getattr(config, "prob", None) is None else config.prob
-        ignore_bubble = int(getattr(config, "ignore_bubble", 0) or 0) if config is not None else 0
-        pairs = self._directions(textlines)
-        if not pairs:
+        threshold, ignore_bubble = _ocr_options(config, 0.5)
+        quads, dirs, own = self._prepare(textlines)
+        if not quads:
             return []
-        quads = [q for q, _ in pairs]
-        dirs = [d for _, d in pairs]
-        H, W = image.shape[:2]
-        dev = self.engine.device
-        page = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]
-        own = [_own_quad(q) for q in quads]
-        rec = TL.warp_plans(own, dirs, H, W, 48)
-        widths = np.where(rec["vertical"] != 0, rec["dh"], rec["dw"]).tolist()
         out = []
-        for idx, ws, wp in TL.chunk_plan(widths):
-            wp += 128
-            region = self._rectify(page, own, dirs, idx, rec[idx].copy(), wp)
-            if 1 <= ignore_bubble <= 50:
-                host = region.cpu().numpy()
-                for j, w_line in enumerate(ws):
-                    if TL.is_ignore(host[j, :, :w_line], ignore_bubble):
-                        region[j] = 0
+        for idx, _, region in TL.rectified_chunks(self._page_on_device(image), own, dirs, 48, ocr_ctc.CHUNK_EXTRA, _bubble_reject(ignore_bubble),
+                                                  self._rectify):
             logits, colors = self.engine.forward(region)
             for j, line in enumerate(self.engine.decode(logits, colors, 0)):
                 q = quads[idx[j]]
@@ -478,10 +468,7 @@ class HipModel48pxCTCOCR(HipModel48pxOCR):
                 res = decode_ctc_line(line, self.dictionary)
                 if res is None or res[1] < threshold:
                     continue
-                q.text, q.prob = res[0], res[1]
-                q.fg_r, q.fg_g, q.fg_b = res[2]
-                q.bg_r, q.bg_g, q.bg_b = res[3]
-                out.append(q)
+                out.append(_accept(q, *res))
         return out
 
 
@@ -514,19 +501,11 @@ class HipModel32pxOCR(HipModel48pxOCR):
         probability exp(mean log-prob) against a 0.7 default threshold (:62), each colour the mean of the clipped head over ALL positions of
         the chosen hypothesis's history (:104-109).  ``config.ignore_bubble`` in 1..50: a rejected line's rows of the chunk stay zero and it
         is decoded as such (:84-86).  Returns the accepted lines in processing order."""
-        from . import textline as TL
-
-        threshold = 0.7 if config is None or getattr(config, "prob", None) is None else config.prob
-        ignore_bubble = int(getattr(config, "ignore_bubble", 0) or 0) if config is not None else 0
-        pairs = self._directions(textlines)
-        if not pairs:
+        threshold, ignore_bubble = _ocr_options(config, 0.7)
+        quads, dirs, own = self._prepare(textlines)
+        if not quads:
             return []
-        quads = [q for q, _ in pairs]
-        dirs = [d for _, d in pairs]
-        page = torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device)[None]
-        own = [_own_quad(q) for q in quads]
-        reject = (lambda crop: TL.is_ignore(crop, ignore_bubble)) if 1 <= ignore_bubble <= 50 else None
-        r = self.engine.recognize_lines(page, own, dirs, max_seq_length=max_seq_length, reject=reject)
+        r = self.engine.recognize_lines(self._page_on_device(image), own, dirs, max_seq_length=max_seq_length, reject=_bubble_reject(ignore_bubble))
         toks, lens = r["tokens"].cpu().numpy(), r["length"].cpu().numpy()
         probs, cols = r["prob"].cpu().numpy(), r["colors"].cpu().numpy()
         out = []
@@ -537,10 +516,7 @@ class HipModel32pxOCR(HipModel48pxOCR):
                 continue
             n = int(lens[row])
             txt, fgc, bgc = decode_32px_line(toks[row, :n], cols[row, :n - 1], self.dictionary)
-            q.text, q.prob = txt, prob
-            q.fg_r, q.fg_g, q.fg_b = fgc
-            q.bg_r, q.bg_g, q.bg_b = bgc
-            out.append(q)
+            out.append(_accept(q, txt, prob, fgc, bgc))
         return out
 
 
@@ -682,7 +658,7 @@ def resolve_lama_precision(setting: str, config=None) -> str:
     raise ValueError(f"config.inpainting_precision must be fp32, fp16 or bf16 (got {v!r})")
 
 
-class HipLamaMPEInpainter(_InpBase):
+class HipLamaMPEInpainter(_EnginePlugin, _InpBase):
     """``--inpainter lama_mpe`` on the HIP engine.  ``precision``: "fp32" (default), "bf16", or "config" = what the call's
     ``config.inpainting_precision`` says, as in the reference (``resolve_lama_precision``); None = ``lama_precision_default()``."""
     _KEY = _key = "lama_mpe_hip"
@@ -698,11 +674,10 @@ class HipLamaMPEInpainter(_InpBase):
     def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None,
                  resize: Optional[Callable] = None, precision: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._weights, self._resize = weights, resize
+        self._resize = resize
         self.precision = lama_precision_default() if precision is None else precision
         resolve_lama_precision(self.precision)      # a bad value raises here, not at the first page
-        self.engine = None
-        _weights_handed_over(self, weights)
+        self._hand_over(weights)
 
     def precision_for(self, config=None) -> str:
         """The engine precision of a call with this ``config``: "fp32" or "bf16"."""
@@ -717,11 +692,6 @@ class HipLamaMPEInpainter(_InpBase):
                                       device=dev)
         self.device = device
 
-    async def _unload(self):
-        if self.engine is not None:
-            self.engine.release_workspace()  # device slabs go back to the allocator before the weights do
-        self.engine = None
-
     @torch.no_grad()
     async def _infer(self, image: np.ndarray, mask: np.ndarray, config=None, inpainting_size: int = 1024,
                      verbose: bool = False) -> np.ndarray:
@@ -734,9 +704,7 @@ class HipLamaMPEInpainter(_InpBase):
             raise ValueError(f"bad shapes: image {image.shape}, mask {mask.shape}")
         if image.dtype != np.uint8 or mask.dtype != np.uint8:
             raise ValueError(f"expected uint8 page and mask, got {image.dtype} / {mask.dtype}")
-        dev = self.engine.device
-        img0 = torch.from_numpy(np.ascontiguousarray(image)).to(dev)[None]     # the page crosses PCIe once, as bytes
-        msk0 = torch.from_numpy(np.ascontiguousarray(mask)).to(dev)[None]
+        img0, msk0 = self._page_on_device(image), self._page_on_device(mask)
         # optional injected callable (img, (w, h), "keep_aspect" | "linear") -> ndarray: e.g. the real OpenCV
         return inpaint_pages(self.engine, img0, msk0, inpainting_size, self._resize, precision=self.precision_for(config))[0].cpu().numpy()
 
@@ -826,7 +794,7 @@ class HipAotInpainter(HipLamaMPEInpainter):
         self.device = device
 
 
-class HipESRGANUpscaler(_UpBase):
+class HipESRGANUpscaler(_EnginePlugin, _UpBase):
     """``--upscaler 4xultrasharp`` (RRDBNet 4x) on the HIP engine."""
     _KEY = _key = "4xultrasharp_hip"
     _MODEL_MAPPING: Dict = {  # upscaling/esrgan_pytorch.py:513-518
@@ -839,23 +807,15 @@ class HipESRGANUpscaler(_UpBase):
 
     def __init__(self, *args, weights: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._weights = weights
-        self.engine = None
-        _weights_handed_over(self, weights)
+        self._hand_over(weights)
 
     async def _load(self, device: str):
         from . import esrgan
 
         dev = _gpu_device(device)
         sd = self._weights or _load_esrgan_checkpoint(self)
-        nb = 1 + max(int(k.split(".")[3]) for k in sd if k.startswith("model.1.sub.") and ".RDB" in k)  # infer_params (:470-509)
-        self.engine = esrgan.EsrganEngine(sd, nb=nb, device=dev)
+        self.engine = esrgan.EsrganEngine(sd, nb=_esrgan_blocks(sd), device=dev)
         self.device = device
-
-    async def _unload(self):
-        if self.engine is not None:
-            self.engine.release_workspace()  # device slabs go back to the allocator before the weights do
-        self.engine = None
 
     @torch.no_grad()
     async def _infer(self, image_batch: List, upscale_ratio: float) -> List:
@@ -866,14 +826,13 @@ class HipESRGANUpscaler(_UpBase):
         ratio = upscale_ratio / 4
         out = []
         for img in image_batch:  # pages of a batch may differ in size: one launch sequence per page
-            rgb = np.ascontiguousarray(np.array(img.convert("RGB")))
-            up = self.engine.forward(torch.from_numpy(rgb).to(self.engine.device)[None])[0].cpu().numpy()
+            up = self.engine.forward(self._page_on_device(np.array(img.convert("RGB"))))[0].cpu().numpy()
             im = Image.fromarray(up)
             out.append(im.resize(size=(int(round(im.size[0] * ratio)), int(round(im.size[1] * ratio))), resample=Image.Resampling.BILINEAR))
         return out
 
 
-class HipMangaColorizer(_ColBase):
+class HipMangaColorizer(_EnginePlugin, _ColBase):
     """``--colorizer mc2`` (manga-colorization-v2: FFDNet denoiser + SE-ResNeXt generator) on the HIP engine.  Same ``_infer(image,
     colorization_size, denoise_sigma=25)`` -> RGB ``PIL.Image`` at the network's size, like the reference.  ``weights``:
     {"generator": state_dict, "denoiser": state_dict}."""
@@ -894,9 +853,7 @@ class HipMangaColorizer(_ColBase):
 
     def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._weights = weights
-        self.engine = None
-        _weights_handed_over(self, weights)
+        self._hand_over(weights)
 
     async def _load(self, device: str):
         from . import mc2
@@ -906,18 +863,12 @@ class HipMangaColorizer(_ColBase):
         self.engine = mc2.Mc2Engine(w["generator"], w["denoiser"], device=dev)
         self.device = device
 
-    async def _unload(self):
-        if self.engine is not None:
-            self.engine.release_workspace()
-        self.engine = None
-
     @torch.no_grad()
     async def _infer(self, image, colorization_size: int, denoise_sigma=25, **kwargs):
         """PIL page -> colorized RGB PIL image (manga_colorization_v2.py:42-74); ``kwargs`` takes the context keys dispatch passes."""
         from PIL import Image
 
-        page = np.ascontiguousarray(np.array(image.convert("RGBA")))
-        out = self.engine.forward(torch.from_numpy(page).to(self.engine.device)[None], colorization_size, denoise_sigma)
+        out = self.engine.forward(self._page_on_device(np.array(image.convert("RGBA"))), colorization_size, denoise_sigma)
         return Image.fromarray(out[0].cpu().numpy())
 
 
@@ -977,6 +928,19 @@ def _resize2x_f32(m: np.ndarray) -> np.ndarray:
     return (rows[y0] * wy0[:, None] + rows[y1] * wy1[:, None]).astype(np.float32)
 
 
+def _bare_state_dict(ck):
+    """A checkpoint saved as {'model': state_dict} or as the bare state_dict -> the state_dict."""
+    return ck["model"] if "model" in ck else ck
+
+
+def _esrgan_blocks(sd) -> int:
+    """RRDB blocks of an RRDBNet state_dict, from its keys (esrgan_pytorch.py infer_params :470-509)."""
+    nb = 1 + max((int(k.split(".")[3]) for k in sd if k.startswith("model.1.sub.") and ".RDB" in k), default=-1)
+    if nb <= 0:
+        raise ValueError("4xESRGAN.pth: no RRDB trunk (model.1.sub.<n>.…) in the state_dict")
+    return nb
+
+
 def _ckpt_path(plugin, name: str) -> str:
     if hasattr(plugin, "_get_file_path"):
         return plugin._get_file_path(name)
@@ -1014,8 +978,7 @@ def _load_ocr_ctc_checkpoint(plugin):
     from . import ocr_ctc_schema, synth
 
     dictionary = _read_dictionary(_ckpt_path(plugin, "alphabet-all-v5.txt"))
-    sd = torch.load(_ckpt_path(plugin, "ocr-ctc.ckpt"), map_location="cpu")
-    sd = sd["model"] if "model" in sd else sd
+    sd = _bare_state_dict(torch.load(_ckpt_path(plugin, "ocr-ctc.ckpt"), map_location="cpu"))
     return synth.check_state_dict(sd, ocr_ctc_schema.ocr_ctc_schema(len(dictionary)), "ocr-ctc.ckpt"), dictionary
 
 
@@ -1024,8 +987,7 @@ def _load_ocr32_checkpoint(plugin):
     from . import ocr32_schema, synth
 
     dictionary = _read_dictionary(_ckpt_path(plugin, "alphabet-all-v5.txt"))
-    sd = torch.load(_ckpt_path(plugin, "ocr.ckpt"), map_location="cpu")
-    sd = sd["model"] if "model" in sd else sd
+    sd = _bare_state_dict(torch.load(_ckpt_path(plugin, "ocr.ckpt"), map_location="cpu"))
     return synth.check_state_dict(sd, ocr32_schema.ocr32_schema(len(dictionary)), "ocr.ckpt"), dictionary
 
 
@@ -1046,8 +1008,7 @@ def _load_aot_checkpoint(plugin):
     """inpainting.ckpt: {'model': state_dict} or a bare state_dict (inpainting_aot.py:27-28), schema-checked."""
     from . import aot_schema, synth
 
-    ck = torch.load(_ckpt_path(plugin, plugin.CKPT), map_location="cpu")
-    sd = ck["model"] if "model" in ck else ck
+    sd = _bare_state_dict(torch.load(_ckpt_path(plugin, plugin.CKPT), map_location="cpu"))
     return {"aot": synth.check_state_dict(sd, aot_schema.aot_generator_schema(), plugin.CKPT)}
 
 
@@ -1056,10 +1017,7 @@ def _load_esrgan_checkpoint(plugin):
     from . import esrgan_schema, synth
 
     sd = torch.load(_ckpt_path(plugin, "4xESRGAN.pth"), map_location="cpu")
-    nb = 1 + max((int(k.split(".")[3]) for k in sd if k.startswith("model.1.sub.") and ".RDB" in k), default=-1)
-    if nb <= 0:
-        raise ValueError("4xESRGAN.pth: no RRDB trunk (model.1.sub.<n>.…) in the state_dict")
-    return synth.check_state_dict(sd, esrgan_schema.rrdbnet_schema(nb), "4xESRGAN.pth")
+    return synth.check_state_dict(sd, esrgan_schema.rrdbnet_schema(_esrgan_blocks(sd)), "4xESRGAN.pth")
 
 
 def _load_mc2_checkpoint(plugin):

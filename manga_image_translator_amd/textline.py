@@ -9,15 +9,24 @@ because any other formulation changes which lines merge; results are pinned to t
 (tests/golden/textline.npz, direction.npz).  The pixel half of that function
 (cv2.warpPerspective + cv2.rotate) runs on the GPU: ``warp_plan`` only produces the crop rectangle, the destination
 size and the inverse homography that ``mit_ocr_warp_lines`` (csrc/ocr_warp.hip) consumes.
+
+The steps the three OCR models share around those plans live here too, once: the reference's chunking (``chunk_plan`` /
+``pack_chunks``), the launch of the rectification kernel (``rectify``), the per-page chunk loop (``rectified_chunks``) and the pooling
+of encoder memories for one beam search (``pool_memories``).
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import math
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
+import torch
+
+from . import lib as _lib
+from . import ops
 
 
 def _sort_pnts_np(pts: np.ndarray) -> Tuple[np.ndarray, bool]:
@@ -498,7 +507,8 @@ def warp_plan(quad: Quadrilateral, direction: str, im_h: int, im_w: int, texthei
 
 def chunk_plan(widths: Sequence[int], max_chunk_size: int = 16) -> List[Tuple[List[int], List[int], int]]:
     """Model48pxOCR._infer's batching (model_48px.py:79-86): lines sorted by crop width, consecutive groups of 16,
-    each padded to ``4 * (max(widths) + 7) // 4`` (== max + 7).  Returns [(indices, widths, padded_width)]."""
+    each padded to ``4 * (max(widths) + 7) // 4`` (== max + 7, the reference's precedence quirk).
+    Returns [(indices, widths, padded_width)]."""
     perm = sorted(range(len(widths)), key=lambda i: widths[i])
     out = []
     for c in range(0, len(perm), max_chunk_size):
@@ -506,6 +516,17 @@ def chunk_plan(widths: Sequence[int], max_chunk_size: int = 16) -> List[Tuple[Li
         ws = [int(widths[i]) for i in idx]
         out.append((idx, ws, 4 * (max(ws) + 7) // 4))
     return out
+
+
+def pack_chunks(region_imgs: List[np.ndarray], max_chunk_size: int = 16, *, height: int, extra: int = 0):
+    """The reference's host batching of rectified crops u8 [height, w, 3], the same for its three OCR models: ``chunk_plan`` over the crop
+    widths, every chunk one zero-padded u8 [n, height, max + 7 + extra, 3].  48px (model_48px.py:79-91) and 32px (model_32px.py:68-87)
+    add nothing, 48px_ctc 128 columns (model_48px_ctc.py:77-88).  Yields (indices, widths, region)."""
+    for indices, widths, wp in chunk_plan([im.shape[1] for im in region_imgs], max_chunk_size):
+        region = np.zeros((len(indices), height, wp + extra, 3), dtype=np.uint8)
+        for j, i in enumerate(indices):
+            region[j, :, :widths[j], :] = region_imgs[i]
+        yield indices, widths, region
 
 
 # numpy mirror of the C struct MitWarpLine (include/mit_hip.h): 9 doubles + 10 int32 = 112 bytes
@@ -579,3 +600,50 @@ def is_ignore(region_img: np.ndarray, ignore_bubble: int = 0) -> bool:
     img = np.asarray(region_img)
     gray = np.dot(img[..., :3], [0.299, 0.587, 0.114])[..., np.newaxis]
     return bool(np.sum(np.sum((img - gray) ** 2, axis=-1) > 100) > 10)
+
+
+# ---- the OCR models' shared device steps ---------------------------------------------------------------------------------------
+
+def rectify(page_u8: torch.Tensor, records, height: int, wp: int) -> torch.Tensor:
+    """Lines of device pages u8 [P,H,W,3] rectified into one zero-padded chunk u8 [n, height, wp, 3] (mit_ocr_warp_lines:
+    get_transformed_region + the reference's chunk packing).  ``records``: WARP_LINE_DTYPE array (line j goes to row j; uploaded here),
+    or ``(device address, n)`` of n such records already on the device with ``out_row`` set (a chunk of an uploaded plan)."""
+    if isinstance(records, np.ndarray):
+        records = records.copy()
+        records["out_row"] = np.arange(len(records))
+        table = torch.frombuffer(bytearray(records.tobytes()), dtype=torch.uint8).to(page_u8.device)
+        records = (table.data_ptr(), len(records))
+    ptr, n = records
+    region = torch.empty(n, height, wp, 3, dtype=torch.uint8, device=page_u8.device)
+    _lib.check(_lib.load().mit_ocr_warp_lines(page_u8.data_ptr(), page_u8.shape[1], page_u8.shape[2], ptr, n,
+                                              region.data_ptr(), height, wp, ctypes.c_void_p(ops.current_stream())), "mit_ocr_warp_lines")
+    return region
+
+
+def rectified_chunks(page_u8: torch.Tensor, quads, directions, height: int, extra: int = 0, reject=None, rectify_fn=None):
+    """The chunk loop of the reference's ``_infer`` for one page u8 [1,H,W,3]: ``warp_plans`` -> ``chunk_plan`` (+ ``extra`` padding
+    columns) -> ``rectify`` -> ``reject``.  ``reject(crop u8 [height, w, 3] ndarray) -> bool`` (optional): a rejected line's rows are
+    zeroed and it stays in its chunk, as the reference's ``continue`` leaves it.  ``rectify_fn(page, quads, directions, indices,
+    records, wp)`` (optional) stands in for ``rectify`` (a host twin in tests).  Yields (indices, widths, region u8 [n, height, wp, 3])."""
+    rec = warp_plans(quads, list(directions), int(page_u8.shape[1]), int(page_u8.shape[2]), height)
+    widths = np.where(rec["vertical"] != 0, rec["dh"], rec["dw"]).tolist()
+    for idx, ws, wp in chunk_plan(widths):
+        wp += extra
+        if rectify_fn is None:
+            region = rectify(page_u8, rec[idx], height, wp)
+        else:
+            region = rectify_fn(page_u8, quads, directions, idx, rec[idx].copy(), wp)
+        if reject is not None:
+            host = region.cpu().numpy()
+            for j, w_line in enumerate(ws):
+                if reject(host[j, :, :w_line]):
+                    region[j] = 0
+        yield idx, ws, region
+
+
+def pool_memories(mems: Sequence[torch.Tensor]) -> torch.Tensor:
+    """Encoder memories [layers, n_i, L_i, E] of several chunks -> one [layers, sum n_i, Lmax, E], zero-padded to the longest (the
+    decoders mask the pad)."""
+    Lmax = max(m.shape[2] for m in mems)
+    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(m.shape[0], m.shape[1], Lmax - m.shape[2], m.shape[3])], 2)
+    return torch.cat([pad(m) for m in mems], 1)

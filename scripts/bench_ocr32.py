@@ -59,7 +59,7 @@ def main():
     enc32 = [None]
 
     def encode32():
-        enc32[0] = [e32.encode(e32.rectify(page, rec[idx], wp), ws) for idx, ws, wp in plan32]
+        enc32[0] = [e32.encode(TL.rectify(page, rec[idx], ocr32.TEXT_HEIGHT, wp), ws) for idx, ws, wp in plan32]
 
     out32 = [None]
 
