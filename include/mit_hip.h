@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 17
+#define MIT_ABI_VERSION 18
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -318,6 +318,16 @@ int mit_prof_kernels_read(MitProfKernelStat *stats, int max_stats, int *n_stats)
  * <= 65535), result (2 N + H W) / (2 H W) with N the integer weighted sum. */
 int mit_resize_u8(const uint8_t *src_dev, int B, int H, int W, int C, uint8_t *dst_dev, int dh, int dw, int mode, const int *yidx_dev,
                   const uint16_t *ycoef_dev, const int *xidx_dev, const uint16_t *xcoef_dev, void *stream);
+/* Pillow's 8-bit ImagingResample for ONE axis of device bytes [B,H,W,C] (C = 1 or 3; ABI 18): axis 0 resamples W -> n_out
+ * (dst [B,H,n_out,C]), axis 1 resamples H -> n_out (dst [B,n_out,W,C]).  `Image.resize` is the horizontal pass followed by the vertical
+ * pass on its 8-bit result, a pass whose size does not change skipped: the caller launches this once per pass.  It is the final
+ * BILINEAR resize by ratio / 4 of the ESRGAN upscaler (upscaling/esrgan_pytorch.py:546) and the BICUBIC resizes of the ratio
+ * correction (upscaling/common.py:32) and of the revert to the input size (manga_translator.py:629).  Tables from the host
+ * (manga_image_translator_amd/imgproc.py pil_coeffs): bounds int32 [n_out, 2] = {xmin, cnt} with xmin >= 0, xmin + cnt <= the axis
+ * length and cnt <= ksize; coef int32 [n_out, ksize], Pillow's 22-bit integer coefficients.  Output byte
+ * clamp((2^21 + sum_x src[xmin + x] * coef[x]) >> 22, 0, 255), int32 arithmetic.  src and dst must not alias. */
+int mit_resample_pil_u8(const uint8_t *src_dev, int B, int H, int W, int C, uint8_t *dst_dev, int n_out, int axis, const int *bounds_dev,
+                        const int *coef_dev, int ksize, void *stream);
 /* cv2.bilateralFilter on 8-bit RGB pages [B,H,W,3] (mask_refinement/text_mask_utils.py:159 and detection/default.py:64 call it
  * with d = 17, sigmaColor = sigmaSpace = 80): BORDER_REFLECT_101, `ntaps` taps of the circular support in row-major order, tap k at
  * (dy, dx) = (tap_ofs[k] >> 16, (int16)(tap_ofs[k] & 0xffff)) with spatial weight tap_w[k]; colour weight

@@ -12,12 +12,14 @@ Same network as ``RRDBNet(3, 3, nf=64, nb=23, upscale=4)`` of the reference
 * the BGR flip of :541/:545 lives in the first conv's input-channel order and the last conv's output-channel order; the
   3-channel output conv runs on the VALU small-Cout kernel; clip + x255 truncation to uint8 on the GPU.
 
-The final PIL bilinear resize by ratio/4 (:546) is host glue outside the dense path.
+``upscale`` adds what surrounds the network in the reference, still on the device: Pillow's BILINEAR resize by ratio / 4 after every
+pass (:546), the pass loop of ``CommonUpscaler.upscale`` (upscaling/common.py:10-33) and its BICUBIC correction (:32), through
+``imgproc.pil_resize_u8`` (csrc/pil_resample.hip, byte-identical to Pillow).  Only the final page leaves the GPU.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -26,6 +28,40 @@ from . import ops
 from .ops import ACT_LEAKY, ACT_NONE, PAD_ZERO
 
 NF, GC = 64, 32
+VALID_UPSCALE_RATIOS = (2, 3, 4)   # ESRGANUpscalerPytorch._VALID_UPSCALE_RATIOS (esrgan_pytorch.py:519)
+
+
+def pass_size(w: int, h: int, ratio: float) -> Tuple[int, int]:
+    """(w, h) one ``_infer(…, ratio)`` returns for a (w, h) page: the 4x output resized by ratio / 4 (esrgan_pytorch.py:539,546)."""
+    r = ratio / 4
+    return int(round(4 * w * r)), int(round(4 * h * r))
+
+
+def upscale_plan(w: int, h: int, upscale_ratio: float, valid: Sequence[float] = VALID_UPSCALE_RATIOS):
+    """The size arithmetic of ``CommonUpscaler.upscale`` (upscaling/common.py:10-33) for a (w, h) page: ([(pass ratio, (w, h) after the
+    pass)], correction (w, h) or None).  Passes are taken while ``ratio_left > 0``, each the smallest valid ratio that covers what is left
+    (the largest when none does); a negative rest is corrected by a resize by (ratio + ratio_left) / ratio, its sides TRUNCATED (:32)."""
+    if upscale_ratio == 1:
+        return [], None
+    valid = sorted(valid)
+    assert valid[0] > 1
+    passes: List[Tuple[float, Tuple[int, int]]] = []
+    ratio_left = upscale_ratio
+    ratio = valid[-1]
+    while ratio_left > 0:
+        ratio = valid[-1]
+        for v in valid:
+            if ratio_left <= v:
+                ratio = v
+                break
+        ratio_left -= ratio
+        w, h = pass_size(w, h, ratio)
+        passes.append((ratio, (w, h)))
+    correction: Optional[Tuple[int, int]] = None
+    if ratio_left < 0:
+        d = (ratio + ratio_left) / ratio
+        correction = (int(w * d), int(h * d))
+    return passes, correction
 
 
 class _RDB:
@@ -110,6 +146,24 @@ class EsrganEngine(ops.Engine):
         out = torch.empty(B, 4 * H, 4 * W, 3, dtype=torch.uint8, device=self.device)
         _lib.check(lib.mit_map_to_u8(y.data_ptr(), out.data_ptr(), y.numel(), 2, 0.0, st), "mit_map_to_u8")
         return out
+
+    @torch.no_grad()
+    def upscale(self, pages_u8: torch.Tensor, upscale_ratio: float) -> torch.Tensor:
+        """``CommonUpscaler.upscale`` around ``_infer`` for u8 RGB pages [B,H,W,3] of one size, on the device: per pass ``forward`` and
+        Pillow's BILINEAR resize to ``pass_size``; a BICUBIC correction when the ratios overshoot; ratio 1 returns the input."""
+        from . import imgproc
+
+        if upscale_ratio == 1:
+            return pages_u8
+        if pages_u8.dim() != 4:
+            raise ValueError(f"EsrganEngine.upscale expects u8 [B,H,W,3], got {tuple(pages_u8.shape)}")
+        passes, correction = upscale_plan(int(pages_u8.shape[2]), int(pages_u8.shape[1]), upscale_ratio)
+        x = pages_u8
+        for _, size in passes:
+            x = imgproc.pil_resize_u8(self.forward(x), size, "bilinear")
+        if correction is not None:
+            x = imgproc.pil_resize_u8(x, correction, "bicubic")
+        return x
 
     def flops_per_input_pixel(self) -> float:
         """Executed MACs x 2 per low-resolution pixel (the up-convs counted at their merged 2x2 form)."""

@@ -222,6 +222,143 @@ def select_u8(mask: torch.Tensor, thr: int, a: torch.Tensor, b: torch.Tensor) ->
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# PIL.Image.resize (8-bit, modes RGB and L, BILINEAR / BICUBIC) — upscaling/esrgan_pytorch.py:546, upscaling/common.py:32,
+# manga_translator.py:629.  Pillow's ImagingResample restated: double-precision coefficients per output index, normalised, rounded to
+# 22-bit integers; a horizontal pass into 8 bits, then a vertical pass on that; a pass whose size is unchanged is skipped.  Pillow is
+# installed wherever this runs, so the tests hold both forms to the real library byte for byte.
+# ------------------------------------------------------------------------------------------------------------------------
+
+PIL_PRECISION_BITS = 32 - 8 - 2
+_PIL_SUPPORT = {"bilinear": 1.0, "bicubic": 2.0}
+
+
+def _pil_filter_name(resample) -> str:
+    name = resample.lower() if isinstance(resample, str) else {2: "bilinear", 3: "bicubic"}.get(int(resample))   # Image.Resampling values
+    if name not in _PIL_SUPPORT:
+        raise ValueError(f"resample must be 'bilinear' or 'bicubic' (got {resample!r})")
+    return name
+
+
+def _pil_filter(name: str, x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)
+    if name == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+@lru_cache(maxsize=128)
+def pil_coeffs(n_in: int, n_out: int, resample="bilinear") -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for one axis ``n_in -> n_out``: (coef int32 [n_out, ksize], bounds int32
+    [n_out, 2] = {xmin, cnt}).  Everything in double precision, the weight sum taken one add at a time in index order; the integer
+    coefficient is the C cast (truncation) of w * 2^22 +- 0.5.  Coefficients past ``cnt`` are zero."""
+    name = _pil_filter_name(resample)
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in <= 0 or n_out <= 0:
+        raise ValueError(f"pil_coeffs: sizes must be positive (got {n_in} -> {n_out})")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = _PIL_SUPPORT[name] * fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    cnt = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), n_in) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    live = x < cnt[:, None]
+    ss = 1.0 / fs
+    w = np.where(live, _pil_filter(name, ((x + xmin[:, None]) - center[:, None] + 0.5) * ss), 0.0)
+    ww = np.cumsum(w, axis=1)[:, -1:]       # sequential adds, as the C loop (the zeros past cnt change nothing)
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    half = np.where(w < 0, -0.5, 0.5)
+    coef = np.trunc(half + w * float(1 << PIL_PRECISION_BITS)).astype(np.int32)
+    bounds = np.stack([xmin, cnt], 1).astype(np.int32)
+    coef.setflags(write=False)
+    bounds.setflags(write=False)
+    return coef, bounds
+
+
+def _pil_pass_host(s: np.ndarray, axis: int, n_out: int, name: str) -> np.ndarray:
+    """One resampling pass of a [H,W,C] array along ``axis`` (0 = rows, 1 = columns) in integers."""
+    n_in = s.shape[axis]
+    coef, bounds = pil_coeffs(n_in, n_out, name)
+    t = np.moveaxis(s, axis, 0).astype(np.int64)
+    acc = np.full((n_out,) + t.shape[1:], 1 << (PIL_PRECISION_BITS - 1), np.int64)
+    for k in range(coef.shape[1]):
+        acc += t[np.minimum(bounds[:, 0] + k, n_in - 1)] * coef[:, k].astype(np.int64)[:, None, None]
+    out = np.clip(acc >> PIL_PRECISION_BITS, 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.moveaxis(out, 0, axis))
+
+
+def pil_resize_u8_host(src: np.ndarray, size: Tuple[int, int], resample="bilinear") -> np.ndarray:
+    """``Image.fromarray(src).resize(size, resample)`` for uint8 [H,W,C] (C = 1 or 3) or [H,W] in numpy; ``size`` = (w, h) as in Pillow."""
+    name = _pil_filter_name(resample)
+    if not isinstance(src, np.ndarray) or src.dtype != np.uint8 or src.ndim not in (2, 3) or (src.ndim == 3 and src.shape[2] not in (1, 3)):
+        raise ValueError(f"pil_resize_u8_host expects uint8 [H,W] or [H,W,C] with C in (1, 3), got {getattr(src, 'dtype', None)} "
+                         f"{getattr(src, 'shape', None)}")
+    w, h = int(size[0]), int(size[1])
+    if w <= 0 or h <= 0:
+        raise ValueError(f"pil_resize_u8_host: size must be positive (got {size})")
+    squeeze = src.ndim == 2
+    s = src[..., None] if squeeze else src
+    if s.shape[1] != w:
+        s = _pil_pass_host(s, 1, w, name)
+    if s.shape[0] != h:
+        s = _pil_pass_host(s, 0, h, name)
+    s = s.copy() if s is src or s.base is src else s
+    return s[..., 0] if squeeze else s
+
+
+_PIL_DEV = {}
+
+
+def _pil_tables_dev(n_in: int, n_out: int, name: str, device):
+    key = (n_in, n_out, name, str(device))
+    if key not in _PIL_DEV:
+        if len(_PIL_DEV) >= 64:
+            _PIL_DEV.clear()
+        coef, bounds = pil_coeffs(n_in, n_out, name)
+        _PIL_DEV[key] = (torch.from_numpy(coef.copy()).to(device), torch.from_numpy(bounds.copy()).to(device), coef.shape[1])
+    return _PIL_DEV[key]
+
+
+def pil_resize_u8(src: torch.Tensor, size: Tuple[int, int], resample="bilinear") -> torch.Tensor:
+    """``Image.resize(size, resample)`` of every page of a uint8 device tensor [B,H,W,C] (C = 1 or 3; ``size`` = (w, h)) through
+    ``mit_resample_pil_u8``: the horizontal pass, then the vertical pass on its 8-bit result, each only when that size changes.
+    Byte-identical to Pillow.  The input is not modified; an unchanged size returns a copy, as Pillow does."""
+    from . import lib as _lib
+    from . import ops
+
+    name = _pil_filter_name(resample)
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
+        raise ValueError(f"pil_resize_u8 expects a uint8 tensor, got {getattr(src, 'dtype', type(src))}")
+    if src.dim() != 4 or src.shape[3] not in (1, 3):
+        raise ValueError(f"pil_resize_u8 expects [B,H,W,C] with C in (1, 3), got {tuple(src.shape)}")
+    if not src.is_cuda:
+        raise ValueError("pil_resize_u8 runs on device tensors (pil_resize_u8_host is the numpy form for host arrays)")
+    w, h = int(size[0]), int(size[1])
+    if w <= 0 or h <= 0 or src.numel() == 0:
+        raise ValueError(f"pil_resize_u8: sizes must be positive (got {tuple(src.shape)} -> {size})")
+    s = src.contiguous()
+    B, H, W, Cc = s.shape
+    if (H, W) == (h, w):
+        return src.clone()
+    lib, st = _lib.load(), C.c_void_p(ops.current_stream())
+    if W != w:
+        coef, bounds, ksize = _pil_tables_dev(W, w, name, s.device)
+        out = torch.empty(B, H, w, Cc, dtype=torch.uint8, device=s.device)
+        _lib.check(lib.mit_resample_pil_u8(s.data_ptr(), B, H, W, Cc, out.data_ptr(), w, 0, bounds.data_ptr(), coef.data_ptr(), ksize, st),
+                   "mit_resample_pil_u8")
+        s = out
+    if H != h:
+        coef, bounds, ksize = _pil_tables_dev(H, h, name, s.device)
+        out = torch.empty(B, h, w, Cc, dtype=torch.uint8, device=s.device)
+        _lib.check(lib.mit_resample_pil_u8(s.data_ptr(), B, H, w, Cc, out.data_ptr(), h, 1, bounds.data_ptr(), coef.data_ptr(), ksize, st),
+                   "mit_resample_pil_u8")
+        s = out
+    return s
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # cv2.bilateralFilter (8-bit, 3 channels) — mask_refinement/text_mask_utils.py:159, detection/default.py:64
 # ------------------------------------------------------------------------------------------------------------------------
 

@@ -817,18 +817,44 @@ class HipESRGANUpscaler(_EnginePlugin, _UpBase):
         self.engine = esrgan.EsrganEngine(sd, nb=_esrgan_blocks(sd), device=dev)
         self.device = device
 
+    @staticmethod
+    def _pil_resized(t: torch.Tensor, size, resample: str) -> torch.Tensor:
+        """[B,H,W,3] u8 -> (w, h) = size as Pillow resizes it: ``mit_resample_pil_u8`` for the engine's device tensor; what a host
+        stand-in for the engine returns (the boundary checks against the reference's ``_infer`` run without a GPU) goes through the
+        numpy form of the same tables, page by page."""
+        from . import imgproc
+
+        if t.is_cuda:
+            return imgproc.pil_resize_u8(t, size, resample)
+        return torch.from_numpy(np.stack([imgproc.pil_resize_u8_host(x.numpy(), size, resample) for x in t]))
+
+    MAX_LR_PIXELS = 2048 * 1440   # low-resolution pixels of one ``forward``: the page the engine is known to hold (bench.py's config-5 leg)
+
     @torch.no_grad()
     async def _infer(self, image_batch: List, upscale_ratio: float) -> List:
-        """List[PIL.Image] -> List[PIL.Image]: 4x on the GPU, then PIL's bilinear resize by ratio/4 (esrgan_pytorch.py:537-549)."""
+        """List[PIL.Image] -> List[PIL.Image] (RGB), in input order: 4x on the GPU, then Pillow's bilinear resize by ratio / 4 on the GPU
+        too (esrgan_pytorch.py:537-549, ``imgproc.pil_resize_u8``), so only the final page crosses PCIe.  Images of equal size go through
+        one ``forward`` together, as the reference concatenates its batch (:541), in micro-batches of at most ``MAX_LR_PIXELS``
+        low-resolution pixels; images of other sizes form groups of their own."""
         from PIL import Image
 
+        from . import esrgan
+
         assert upscale_ratio <= 4
-        ratio = upscale_ratio / 4
-        out = []
-        for img in image_batch:  # pages of a batch may differ in size: one launch sequence per page
-            up = self.engine.forward(self._page_on_device(np.array(img.convert("RGB"))))[0].cpu().numpy()
-            im = Image.fromarray(up)
-            out.append(im.resize(size=(int(round(im.size[0] * ratio)), int(round(im.size[1] * ratio))), resample=Image.Resampling.BILINEAR))
+        pages = [np.array(img.convert("RGB")) for img in image_batch]
+        groups: Dict[Tuple[int, int], List[int]] = {}
+        for i, p in enumerate(pages):
+            groups.setdefault(p.shape[:2], []).append(i)
+        out: List = [None] * len(pages)
+        for (h, w), idx in groups.items():
+            mb = max(1, self.MAX_LR_PIXELS // max(1, h * w))
+            size = esrgan.pass_size(w, h, upscale_ratio)
+            for a in range(0, len(idx), mb):
+                run = idx[a:a + mb]
+                dev = torch.from_numpy(np.ascontiguousarray(np.stack([pages[i] for i in run]))).to(self.engine.device)
+                res = self._pil_resized(self.engine.forward(dev), size, "bilinear").cpu().numpy()
+                for k, i in enumerate(run):
+                    out[i] = Image.fromarray(res[k])
         return out
 
 

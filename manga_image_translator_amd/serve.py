@@ -97,6 +97,27 @@ class DenseStages:
         self.pages_looped = 0      # pages of translate_batch requests that took the page loop (translate); last_batch_plan says why
         self.last_batch_plan: List[Tuple[List[int], str]] = []
         self.last_coupled_seconds: List[Dict[str, float]] = []
+        self.up = None             # the upscaler plugin: loaded by the first request that asks for upscaling
+
+    async def _load_upscaler(self):
+        """The ``4xultrasharp`` plugin, on the first request with ``config["upscale"]["upscale_ratio"]``: from the checkpoint under
+        ``model_dir``, else seeded synthetic weights of the RRDBNet schema with ``esrgan_blocks`` blocks (default 23, the checkpoint's)."""
+        if self.up is None:
+            from . import esrgan_schema, plugins as P, synth
+
+            if self.params.get("model_dir"):
+                up = P.HipESRGANUpscaler()
+            else:
+                up = P.HipESRGANUpscaler(weights=synth.synth_state_dict(esrgan_schema.rrdbnet_schema(int(self.params.get("esrgan_blocks", 23)))))
+            await up.load("cuda")
+            self.up = up
+        return self.up
+
+    @staticmethod
+    def _upscale_options(cfg: dict) -> Tuple[float, bool]:
+        """(upscale_ratio or 0, revert_upscaling) of a request: the fields of the reference's UpscaleConfig (config.py:211-216)."""
+        up = _as_dict(cfg.get("upscale")) if cfg.get("upscale") is not None else {}
+        return (up.get("upscale_ratio") or 0), bool(up.get("revert_upscaling", False))
 
     async def _load(self):
         if self._loaded:
@@ -133,6 +154,13 @@ class DenseStages:
         page = np.ascontiguousarray(np.asarray(image.convert("RGB") if hasattr(image, "convert") else image, dtype=np.uint8))
         if page.ndim != 3 or page.shape[2] != 3:
             raise ValueError(f"image must be HxWx3 (got {page.shape})")
+        ratio, revert = self._upscale_options(cfg)
+        in_h, in_w = page.shape[:2]
+        if ratio:   # the page is upscaled first and every later stage sees the upscaled page (manga_translator.py:453-465, :683)
+            import torch
+
+            up = await self._load_upscaler()
+            page = np.ascontiguousarray(up.engine.upscale(torch.from_numpy(page).to(up.engine.device)[None], ratio)[0].cpu().numpy())
         H, W = page.shape[:2]
         det = cfg.get("detector", {})
         tls, mask_raw, _ = await self.det.infer(page, int(det.get("detection_size", 1024)), float(det.get("text_threshold", 0.5)),
@@ -168,6 +196,13 @@ class DenseStages:
             out = await self.inp.infer(page, mask, None, int(inp.get("inpainting_size", 2048)))
         else:   # no text: the orchestrator returns the page as it is (manga_translator.py:500-504)
             mask, out = np.zeros((H, W), np.uint8), page
+        if ratio and revert and (W, H) != (in_w, in_h):   # ctx.result.resize(ctx.input.size): Pillow's default BICUBIC (manga_translator.py:626-629)
+            import torch
+
+            from . import imgproc
+
+            dev = torch.from_numpy(np.ascontiguousarray(np.asarray(out, dtype=np.uint8))).to(self.up.engine.device)[None]
+            out = imgproc.pil_resize_u8(dev, (in_w, in_h), "bicubic")[0].cpu().numpy()
         return {"textlines": [{"pts": np.asarray(l.pts).tolist(), "text": l.text, "prob": float(l.prob),
                                "fg": [int(l.fg_r), int(l.fg_g), int(l.fg_b)], "bg": [int(l.bg_r), int(l.bg_g), int(l.bg_b)]} for l in lines],
                 "mask_raw": np.asarray(mask_raw), "mask": np.asarray(mask), "inpainted": np.asarray(out), "device": self.device_name,
@@ -219,6 +254,8 @@ class DenseStages:
 
         if page.ndim != 3 or page.shape[2] != 3:
             return "not HxWx3"
+        if self._upscale_options(cfg)[0]:
+            return "upscale"
         if rearrange.plan(page.shape[0], page.shape[1], 1024) is not None:
             return "webtoon strip (rearranged detection)"
         if int(_as_dict(cfg.get("ocr", {})).get("ignore_bubble", 0)):
@@ -678,11 +715,13 @@ def _main(argv=None) -> int:
     w.add_argument("--nonce", default=os.getenv("MT_WEB_NONCE") or None)
     w.add_argument("--model-dir", default=None, help="directory with the reference's checkpoints; synthetic weights without it")
     w.add_argument("--dict-size", type=int, default=512)
+    w.add_argument("--esrgan-blocks", type=int, default=23, help="RRDB blocks of the synthetic upscaler weights (without --model-dir)")
     w.add_argument("--lazy", action="store_true", help="load the plugins at the first request instead of before listening (default: before, so "
                                                       "that a worker without its GPU or its checkpoints never reports ready)")
     w.add_argument("--preload", action="store_true", help=argparse.SUPPRESS)   # the default since round 6
     a = ap.parse_args(argv)
-    params = {"host": a.host, "port": a.port, "nonce": a.nonce, "model_dir": a.model_dir, "dict_size": a.dict_size, "use_gpu": True}
+    params = {"host": a.host, "port": a.port, "nonce": a.nonce, "model_dir": a.model_dir, "dict_size": a.dict_size, "esrgan_blocks": a.esrgan_blocks,
+              "use_gpu": True}
     worker = make_worker(params)
     loop = asyncio.new_event_loop()
     asyncio.set_event_loop(loop)
