@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 18
+#define MIT_ABI_VERSION 19
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -151,6 +151,12 @@ int mit_conv_gemm(const MitConvGemm *desc, void *stream);
  * reported by mit_conv_gemm_config_name(). */
 int mit_conv_gemm_cfg(const MitConvGemm *desc, int cfg, void *stream);
 const char *mit_conv_gemm_config_name(int cfg);
+/* What mit_conv_gemm_cfg(desc, cfg, stream) would do, without doing it: the same validation (same return value and mit_last_error()
+ * text for a refused descriptor), then *tile = the tile of the first launch and *nb_run = its images — desc->NB unless the batch is
+ * cut into runs (activations past 2^31 elements, or past the 2^31 bytes the buffer-load tiles address); a shorter last run is planned
+ * by itself when it is launched.  Makes no HIP call and dereferences no operand pointer: it works without a GPU, which is how
+ * tests/test_conv_gemm_plan.py pins the automatic tile choice. */
+int mit_conv_gemm_plan(const MitConvGemm *desc, int cfg, int32_t *tile, int32_t *nb_run);
 /* the kernel's template-id as rocprofv3 prints it (without namespace), e.g. "conv_gemm_fast_kernel<128, 128, 16, 1, 4, 4, 4>":
  * lets bench.py join its per-tile probe numbers with the profiler's kernel-trace / PMC rows; NULL past the table. */
 const char *mit_conv_gemm_config_kernel(int cfg);

@@ -1,50 +1,27 @@
-// conv_gemm.hip — configuration table, tile choice, kernel-time probe and C entry points of mit_conv_gemm.
-// The kernels are in conv_gemm_kernels.h; their instantiations are compiled in conv_gemm_inst<group>.hip.
-#include "conv_gemm_kernels.h"
-#include <string.h>
-#include <string>
+// conv_gemm.hip — tile choice, kernel-time probe and C entry points of mit_conv_gemm (validate -> plan -> launch).
+// The kernels are in conv_gemm_kernels.h, their instantiations are compiled in conv_gemm_inst<group>.hip, the tile table is conv_gemm_table.h.
+#include "conv_gemm_table.h"
 #include <atomic>
 
 using namespace mitcg;
 
-#define X(g, name, fast, BM, BN, BK, fn, ...) \
-    extern template void mitcg::fn<BM, BN, BK, __VA_ARGS__>(const MitConvGemm &, int, int, int, int, hipStream_t);
-#include "conv_gemm_cfgs.inc"
-#undef X
-
 namespace {
 
-const CfgEntry kCfgs[] = {
-#define KNAME_launch_cfg "conv_gemm_kernel"
-#define KNAME_launch_fast "conv_gemm_fast_kernel"
-#define KNAME_launch_gemv "conv_gemv_kernel"
-#define KNAME_launch_split "conv_gemm_split_kernel"
-#define X(g, name, fast, BM, BN, BK, fn, ...) \
-    {name, BM, BN, BK, fn<BM, BN, BK, __VA_ARGS__>, fast, KNAME_##fn "<" #BM ", " #BN ", " #BK ", " #__VA_ARGS__ ">"},
-#include "conv_gemm_cfgs.inc"
-#undef X
-};
-
+// the largest element offset of A that a kernel forms, relative to the slice base; -1 for a negative stride or tap offset
+int64_t max_a_offset(const MitConvGemm &p) {
+    if (p.a_bs < 0 || p.a_ys < 0 || p.a_xs < 0) return -1;
+    int tmax = 0;
+    for (int t = 0; t < p.ntaps; ++t) {
+        if (p.tap_off[t] < 0) return -1;
+        if (p.tap_off[t] > tmax) tmax = p.tap_off[t];
+    }
+    return (int64_t)(p.NB - 1) * p.a_bs + (int64_t)(p.Hi - 1) * p.a_ys + (int64_t)(p.Wi - 1) * p.a_xs + p.Cin + tmax;
+}
 // fast kernel preconditions: whole K-tiles inside one tap, table fits, 32-bit element offsets
 bool fast_eligible(const MitConvGemm &p, int BK) {
     if (p.Cin % BK || p.ntaps > FAST_MAX_TAPS) return false;
-    int64_t maxoff = (int64_t)(p.NB - 1) * p.a_bs + (int64_t)(p.Hi - 1) * p.a_ys + (int64_t)(p.Wi - 1) * p.a_xs + p.Cin;
-    int64_t minoff = 0;
-    if (p.a_bs < 0 || p.a_ys < 0 || p.a_xs < 0) return false;
-    int tmax = 0;
-    for (int t = 0; t < p.ntaps; ++t) {
-        if (p.tap_off[t] < 0) return false;
-        if (p.tap_off[t] > tmax) tmax = p.tap_off[t];
-    }
-    (void)minoff;
-    return maxoff + tmax < 0x7fffffffLL;
-}
-constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
-
-int cfg_by_name(const char *name) {
-    for (int i = 0; i < (int)(sizeof(kCfgs) / sizeof(kCfgs[0])); ++i)
-        if (!strcmp(kCfgs[i].name, name)) return i;
-    return -1;
+    const int64_t maxoff = max_a_offset(p);
+    return maxoff >= 0 && maxoff < 0x7fffffffLL;
 }
 
 // conv_gemm_split_kernel preconditions: the fast kernel's, plus split planes of W laid out by mit_gemm_split_pack
@@ -58,30 +35,11 @@ bool split_eligible(const MitConvGemm &p, int BK) {
 // the "u" tiles (operand loads through buffer instructions: 32-bit byte offsets against a 2 GB descriptor, conv_gemm_split.h VAR bit
 // 2048): every byte offset of A — relative to the slice base the kernel forms — and of the packed W planes must stay below 2^31
 bool buf_eligible(const MitConvGemm &p) {
-    if (p.a_bs < 0 || p.a_ys < 0 || p.a_xs < 0) return false;
-    int tmax = 0;
-    for (int t = 0; t < p.ntaps; ++t)
-        if (p.tap_off[t] > tmax) tmax = p.tap_off[t];
-    const int64_t maxoff = (int64_t)(p.NB - 1) * p.a_bs + (int64_t)(p.Hi - 1) * p.a_ys + (int64_t)(p.Wi - 1) * p.a_xs + p.Cin + tmax;
-    if (maxoff * 4 >= 0x80000000LL) return false;
-    return (int64_t)3 * (p.Kw >> 3) * p.ldw * 16 < 0x80000000LL;
+    const int64_t maxoff = max_a_offset(p);
+    return maxoff >= 0 && maxoff * 4 < 0x80000000LL && (int64_t)3 * (p.Kw >> 3) * p.ldw * 16 < 0x80000000LL;
 }
-// the buffer-load twin of a shipped p6 / p1 tile ("...p6o" -> "...p6u"), or the tile itself
-int buf_twin(int c) {
-    static const std::vector<int> twin = [] {
-        std::vector<int> t(kNumCfgs);
-        for (int i = 0; i < kNumCfgs; ++i) {
-            t[i] = i;
-            const std::string n = kCfgs[i].name;
-            if (n.size() > 3 && (n.compare(n.size() - 3, 3, "p6o") == 0 || n.compare(n.size() - 3, 3, "p1o") == 0)) {
-                const int u = cfg_by_name((n.substr(0, n.size() - 1) + "u").c_str());
-                if (u >= 0) t[i] = u;
-            }
-        }
-        return t;
-    }();
-    return c >= 0 && c < kNumCfgs ? twin[c] : c;
-}
+// a split tile as the automatic choice launches it: same arithmetic, operand loads through buffer instructions where the offsets fit
+int buf_form(const MitConvGemm &p, int c) { return buf_eligible(p) ? kCfgs[c].twin : c; }
 
 // conv_gemv_kernel preconditions: <= 4 output columns, plain (unbatched, unsplit) maps, the whole weight panel in LDS
 bool gemv_eligible(const MitConvGemm &p, int lpr) {
@@ -110,93 +68,81 @@ int gemm_mode_now() {
 std::atomic<long long> g_split_min{0};
 int64_t split_min_now() { return g_split_min.load(std::memory_order_relaxed); }
 
-// MitConvGemm.nprod == 1: the one-product tiles, whatever the GEMM mode and the launch size (the caller checked split_eligible(p, 16)).
-// The choice follows the p6 one — narrow / 192-column / wide by N, 64 x 64 for under-filled launches — and every p1 tile gives the same
-// bits, so a result depends neither on it nor on how many pages share the launch.  Measured on LaMa's shapes only (N = 128 / 256 / 512
-// wide, 64 narrow, 192 / 384 on the 192-column tile: profiles/r17a_lama_precision.json); outside them the choice is UNMEASURED — the
-// 192-column tile for every N % 192 == 0, and no N <= 32 form (such a launch runs the 64-column tile with half its columns padded).
-int pick_cfg_p1(const MitConvGemm &p, int64_t M) {
-    static const int wide = cfg_by_name("split128x128x32p1o"), narrow = cfg_by_name("split128x64x32p1o"), t192 = cfg_by_name("split128x192x32p1o");
-    static const int small = cfg_by_name("split64x64x32p1o"), k16 = cfg_by_name("split64x64x16p1o");
-    int c;
-    if (!split_eligible(p, 32)) {
-        c = k16;  // Cin % 32 != 0
-    } else {
-        const int r = p.N % 128;
-        c = (p.N <= 64 || (r != 0 && r <= 64)) ? narrow : wide;
-        if (p.N % 192 == 0) c = t192;
-        if (p.Z == 1 && ((M + 127) / 128) * ((p.N + 63) / 64) < 768) c = small;
+// ---- the tile choice.  One ladder for every kernel family, parameterised by the family's tiles and thresholds (-1: the family has no
+// such tile).  All tiles of a family give the same bits, so a result depends neither on the rung nor on how many pages share the launch.
+struct TileSet {
+    int n32;                // N <= 32 (ESRGAN's growth-32 convolutions, small heads): a 128 x 32 tile, whatever the launch size
+    int narrow, wide;       // 64 / 128 columns
+    int small;              // 64 x 64 for under-filled launches (Z == 1, fewer than small_max 128 x 64 tiles)
+    int64_t small_max;
+    int small_k32;          // ... with two MFMA steps per barrier (BK = 32) for launches of at most 512 blocks
+};
+// measured on MI355X (scripts/bench_conv.py)
+constexpr TileSet kGenericTiles = {CFG("128x32x16"), CFG("128x64x16"), CFG("128x128x16"), -1, 0, -1};
+// small_max swept 640 .. 5120 on the OCR and detector stages (same-box A/B): 1280 = one full wave of workgroups.  wide: 4 waves of
+// 128 x 32, <= 128 registers: 4 workgroups per CU (+3-7 % over the 2 x 2 layout)
+constexpr TileSet kFp32Tiles = {CFG("fast128x32x16w4c"), CFG("fast128x64x16w5c"), CFG("fast128x128x16w4c"), CFG("fast64x64x16w8c"), 1280, -1};
+// small_max 768: one wave of 128-row split tiles (3 workgroups per CU)
+constexpr TileSet kP6Tiles = {CFG("split128x32x16p6o"), CFG("split128x64x16p6o"), CFG("split128x128x16p6o"), CFG("split64x64x16p6o"), 768, CFG("split64x64x32p6o")};
+constexpr TileSet kP9Tiles = {CFG("split128x32x16p9m"), CFG("split128x64x16p9"), CFG("split128x128x16p9m"), CFG("split64x64x16p9m"), 768, CFG("split64x64x32p9m")};
+// p1 (K-tile 32 throughout): no N <= 32 form — such a launch runs the 64-column tile with half its columns padded
+constexpr TileSet kP1Tiles = {-1, CFG("split128x64x32p1o"), CFG("split128x128x32p1o"), CFG("split64x64x32p1o"), 768, -1};
+
+int64_t tiles128(const MitConvGemm &p, int64_t M) { return ((M + 127) / 128) * ((p.N + 63) / 64); }
+
+// exact: the family's exact-N tile for this launch (the caller's rule), -1 = none
+int ladder(const TileSet &s, const MitConvGemm &p, int64_t M, int exact = -1) {
+    if (p.N <= 32 && s.n32 >= 0) return s.n32;
+    const int rem = p.N % 128;
+    int c = (p.N <= 64 || (rem != 0 && rem <= 64)) ? s.narrow : s.wide;  // e.g. N = 192: 3 x 64 beats 2 x 128 with a half-empty tile
+    if (exact >= 0) c = exact;
+    // under-filled launches (one page through the plugins, the decoder's GEMMs: M = lines x beams = 10240; its Linears at M = 160): a
+    // 128-row tiling leaves most CUs with one workgroup or none, 64 x 64 tiles double to quadruple the workgroup count; the arithmetic
+    // per output element is that of the large tiles
+    if (s.small >= 0 && p.Z == 1 && tiles128(p, M) < s.small_max) {
+        c = s.small;
+        // launches of at most two workgroups per CU (one page through the plugins: the decoder at M = 160 rows, the detector's deep
+        // layers) are bound by the latency of a K-loop iteration, not by its throughput: two MFMA steps per barrier (BK = 32) take
+        // 10-22 % off them and cost 2 % on fuller launches (profiles/r03l_split_check_bk32.log).  Same MFMA sequence per element.
+        if (s.small_k32 >= 0 && ((M + 63) / 64) * ((p.N + 63) / 64) <= 512 && split_eligible(p, 32)) c = s.small_k32;
     }
-    return buf_eligible(p) ? buf_twin(c) : c;
+    return c;
+}
+
+// Exact-N p6 tiles (round 5; wave tile 32 x BN, the A tile split once for all BN columns) where the 64-column tile would otherwise
+// run 3 or 5 times over the same rows, or the 128-column tile would compute 48 padded columns — measured per shape
+// (profiles/r07f_split_check_exact_n_tiles.log, r07g_split_check_tile192.log; same bits as every other p6 tile):
+//   N = 160, K = 640 (ConvNeXt stage-2 pw2): 1.36x of 3 x 64;   N = 320, K = 1280 (stage-3 pw2): 1.13x of 5 x 64;
+//   N = 80, K = 320 (stage-1 pw2): 1.08x of the 128-column tile;   N = 192, K = 384 (LaMa spectral conv1): 1.09x of 3 x 64.
+// The short-K expansions (pw1: K = 80 / 160 / 320 into N = 4K) are 5-10 % SLOWER on them and keep the tiles of the ladder.
+int exact_n_p6(const MitConvGemm &p) {
+    if (p.Z != 1) return -1;
+    const int K = p.ntaps * p.Cin;
+    if ((p.N == 160 || p.N == 320) && K >= 512) return CFG("split128x160x16p6o");
+    if (p.N > 64 && p.N <= 96 && K >= 256) return CFG("split128x96x16p6o");
+    if (p.N == 192 && K >= 256) return CFG("split128x192x16p6o");
+    return -1;
 }
 
 int pick_cfg(const MitConvGemm &p, int64_t M) {
-    if (p.nprod == 1) return pick_cfg_p1(p, M);
-    // measured on MI355X (scripts/bench_conv.py)
-    static const int wide = cfg_by_name("fast128x128x16w4c"), narrow = cfg_by_name("fast128x64x16w5c"), m192 = cfg_by_name("fast192x64x16w4c");
-    static const int kCfgGemv16 = cfg_by_name("gemv16"), kCfgGemv4 = cfg_by_name("gemv4"), kCfgGemv16N1 = cfg_by_name("gemv16n1"), kCfgGemv4N1 = cfg_by_name("gemv4n1");
-    static const int kCfgSmall = cfg_by_name("fast64x64x16w8c"), kCfgGen128 = cfg_by_name("128x128x16"), kCfgGen64 = cfg_by_name("128x64x16"), kCfgGen32 = cfg_by_name("128x32x16");
-    const bool f16 = fast_eligible(p, 16);
-    if (gemv_eligible(p, 16)) return p.N == 1 ? kCfgGemv16N1 : kCfgGemv16;
-    if (gemv_eligible(p, 4)) return p.N == 1 ? kCfgGemv4N1 : kCfgGemv4;
-    if (p.N <= 32) {  // ESRGAN's growth-32 convolutions, small heads: a 128 x 32 tile on the best kernel the layer is eligible for
-        static const int n32_split6 = cfg_by_name("split128x32x16p6o"), n32_split9 = cfg_by_name("split128x32x16p9m");
-        static const int n32_fast = cfg_by_name("fast128x32x16w4c");
-        const int sp = gemm_mode_now();
-        if ((sp == 6 || sp == 9) && p.w_split && split_eligible(p, 16) && ((M + 127) / 128) * p.Z >= split_min_now()) {
-            const int c = sp == 6 ? n32_split6 : n32_split9;
-            if (c >= 0) return buf_eligible(p) ? buf_twin(c) : c;
-        }
-        if (f16 && n32_fast >= 0) return n32_fast;
-        return kCfgGen32;
+    // MitConvGemm.nprod == 1: the one-product tiles, whatever the GEMM mode and the launch size (the caller checked split_eligible(p, 16)).
+    // Measured on LaMa's shapes only (N = 128 / 256 / 512 wide, 64 narrow, 192 / 384 on the 192-column tile:
+    // profiles/r17a_lama_precision.json); outside them the choice is UNMEASURED — the 192-column tile for every N % 192 == 0.
+    if (p.nprod == 1) {
+        if (!split_eligible(p, 32)) return buf_form(p, CFG("split64x64x16p1o"));  // Cin % 32 != 0
+        return buf_form(p, ladder(kP1Tiles, p, M, p.N % 192 == 0 ? CFG("split128x192x32p1o") : -1));
     }
+    if (gemv_eligible(p, 16)) return p.N == 1 ? CFG("gemv16n1") : CFG("gemv16");
+    if (gemv_eligible(p, 4)) return p.N == 1 ? CFG("gemv4n1") : CFG("gemv4");
     // split-bf16 tiles (GEMM mode 6 | 9, mit_gemm_mode_set): layers whose packer attached split planes of W, large enough to fill the chip
-    const int split = gemm_mode_now();
-    const int64_t split_min = split_min_now();
-    const int64_t tiles128 = ((M + 127) / 128) * ((p.N + 63) / 64);
-    if ((split == 6 || split == 9) && p.w_split && split_eligible(p, 16) && tiles128 * p.Z >= split_min) {
-        static const int wide6 = cfg_by_name("split128x128x16p6o"), wide9 = cfg_by_name("split128x128x16p9m");
-        static const int narrow6 = cfg_by_name("split128x64x16p6o"), narrow9 = cfg_by_name("split128x64x16p9");
-        static const int small6 = cfg_by_name("split64x64x16p6o"), small9 = cfg_by_name("split64x64x16p9m");
-        constexpr int64_t ssmall_max = 768;  // one wave of 128-row split tiles (3 workgroups per CU)
-        const int r = p.N % 128;
-        int c = (p.N <= 64 || (r != 0 && r <= 64)) ? (split == 6 ? narrow6 : narrow9) : (split == 6 ? wide6 : wide9);
-        // Exact-N tiles (round 5; wave tile 32 x BN, the A tile split once for all BN columns) where the 64-column tile would otherwise
-        // run 3 or 5 times over the same rows, or the 128-column tile would compute 48 padded columns — measured per shape
-        // (profiles/r07f_split_check_exact_n_tiles.log, r07g_split_check_tile192.log; same bits as every other p6 tile):
-        //   N = 160, K = 640 (ConvNeXt stage-2 pw2): 1.36x of 3 x 64;   N = 320, K = 1280 (stage-3 pw2): 1.13x of 5 x 64;
-        //   N = 80, K = 320 (stage-1 pw2): 1.08x of the 128-column tile;   N = 192, K = 384 (LaMa spectral conv1): 1.09x of 3 x 64.
-        // The short-K expansions (pw1: K = 80 / 160 / 320 into N = 4K) are 5-10 % SLOWER on them and keep the tiles above.
-        if (split == 6 && p.Z == 1) {
-            static const int t160 = cfg_by_name("split128x160x16p6o"), t96 = cfg_by_name("split128x96x16p6o"), t192 = cfg_by_name("split128x192x16p6o");
-            const int K = p.ntaps * p.Cin;
-            if (t160 >= 0 && (p.N == 160 || p.N == 320) && K >= 512) c = t160;
-            else if (t96 >= 0 && p.N > 64 && p.N <= 96 && K >= 256) c = t96;
-            else if (t192 >= 0 && p.N == 192 && K >= 256) c = t192;
-        }
-        // under-filled launches (one page through the plugins, the decoder's Linears): 64 x 64 tiles quadruple the workgroup count;
-        // the arithmetic per output element is that of the large tiles, so a result does not depend on the choice
-        const int sm = split == 6 ? small6 : small9;
-        if (sm >= 0 && p.Z == 1 && tiles128 < ssmall_max) {
-            c = sm;
-            // launches of at most two workgroups per CU (one page through the plugins: the decoder at M = 160 rows, the detector's deep
-            // layers) are bound by the latency of a K-loop iteration, not by its throughput: two MFMA steps per barrier (BK = 32) take
-            // 10-22 % off them and cost 2 % on fuller launches (profiles/r03l_split_check_bk32.log).  Same MFMA sequence per element.
-            static const int small6k = cfg_by_name("split64x64x32p6o"), small9k = cfg_by_name("split64x64x32p9m");
-            const int smk = split == 6 ? small6k : small9k;
-            if (smk >= 0 && ((M + 63) / 64) * ((p.N + 63) / 64) <= 512 && split_eligible(p, 32)) c = smk;
-        }
-        if (c >= 0) return buf_eligible(p) ? buf_twin(c) : c;  // same arithmetic, operand loads through buffer instructions where offsets fit
-    }
-    if (f16 && m192 >= 0 && M > 128 && M <= 192 && p.Z >= 8) return m192;  // batched launches (Z entries of M = 184 rows: W-axis DFTs): 2 x 128 rows would run a 40 % empty second tile.  Unbatched, one row of 192 x 64 tiles leaves the chip empty (the decoder at B = 1: M = 160)
-    // under-filled launches (the decoder's GEMMs: M = lines x beams = 10240): a 128-row tiling leaves most CUs with one workgroup or
-    // none, 64 x 64 tiles double the count
-    constexpr int64_t small_max = 1280;  // swept 640 .. 5120 on the OCR and detector stages (same-box A/B): 1280 = one full wave of workgroups
-    if (f16 && kCfgSmall >= 0 && p.Z == 1 && p.N > 32 && ((M + 127) / 128) * ((p.N + 63) / 64) < small_max) return kCfgSmall;
-    constexpr int narrow_max = 64;  // N % 128 up to this takes the 64-column tile
-    const int rem = p.N % 128;
-    if (p.N <= 64 || (rem != 0 && rem <= narrow_max)) return f16 ? narrow : kCfgGen64;  // e.g. N = 192: 3 x 64 beats 2 x 128 with a half-empty tile
-    return f16 ? wide : kCfgGen128;  // 4 waves of 128 x 32, <= 128 registers: 4 workgroups per CU (+3-7 % over the 2 x 2 layout)
+    const int mode = gemm_mode_now();
+    if ((mode == 6 || mode == 9) && p.w_split && split_eligible(p, 16) && tiles128(p, M) * p.Z >= split_min_now())
+        return buf_form(p, mode == 6 ? ladder(kP6Tiles, p, M, exact_n_p6(p)) : ladder(kP9Tiles, p, M));
+    if (!fast_eligible(p, 16)) return ladder(kGenericTiles, p, M);
+    // batched launches (Z entries of M = 184 rows: W-axis DFTs): 2 x 128 rows would run a 40 % empty second tile.  Unbatched, one row of
+    // 192 x 64 tiles leaves the chip empty (the decoder at B = 1: M = 160)
+    if (p.N > 32 && M > 128 && M <= 192 && p.Z >= 8) return CFG("fast192x64x16w4c");
+    return ladder(kFp32Tiles, p, M);
 }
 
 // ---- kernel-time probe (mit_prof_*): HIP events around every launch while enabled ----
@@ -295,14 +241,14 @@ bool vec_epilogue_ok(const MitConvGemm &p) {
     if (p.lut_rows && ((p.lut_ld & 3) || (reinterpret_cast<uintptr_t>(p.lut1) & 15) || (reinterpret_cast<uintptr_t>(p.lut2) & 15))) return false;
     return !(reinterpret_cast<uintptr_t>(p.scale) & 15) && !(reinterpret_cast<uintptr_t>(p.bias) & 15);
 }
-}  // namespace
 
-extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
+// ---- validate -> plan -> launch ----
+// stage 1: the descriptor by itself, whatever tile it takes.  p = *d with MIT_ACT_VEC_OK set where the float4 epilogue applies.
+int validate(const MitConvGemm *d, MitConvGemm &p) {
     if (!d) return mit_set_error("mit_conv_gemm: null descriptor");
-    MitConvGemm pv = *d;
-    if (pv.act & MIT_ACT_VEC_OK) return mit_set_error("mit_conv_gemm: reserved activation bits set");
-    if (vec_epilogue_ok(pv)) pv.act |= MIT_ACT_VEC_OK;
-    const MitConvGemm &p = pv;
+    p = *d;
+    if (p.act & MIT_ACT_VEC_OK) return mit_set_error("mit_conv_gemm: reserved activation bits set");
+    if (vec_epilogue_ok(p)) p.act |= MIT_ACT_VEC_OK;
     if (!p.a || !p.w || !p.c.base) return mit_set_error("mit_conv_gemm: null operand");
     if (p.Cin <= 0 || (p.Cin & 3)) return mit_set_error("mit_conv_gemm: Cin must be a positive multiple of 4 (got %d)", p.Cin);
     if ((p.ldw & 3) || (p.Nw & 3)) return mit_set_error("mit_conv_gemm: ldw/Nw must be multiples of 4 (ldw=%lld Nw=%d)", (long long)p.ldw, p.Nw);
@@ -322,8 +268,7 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
             if (ady >= p.Hi || adx >= p.Wi) return mit_set_error("mit_conv_gemm: reflect pad larger than input");
         }
     }
-    const int64_t M64 = (int64_t)p.NB * p.Ho * p.Wo;
-    if (M64 > 0x7fffffffLL) return mit_set_error("mit_conv_gemm: M too large");
+    if ((int64_t)p.NB * p.Ho * p.Wo > 0x7fffffffLL) return mit_set_error("mit_conv_gemm: M too large");
     if (p.lut_rows) {  // the row-lookup epilogue: both tables, rows long enough, one slice (lut_rows is indexed by the output row)
         if (!p.lut1 || !p.lut2 || p.lut_ld < p.N) return mit_set_error("mit_conv_gemm: lut_rows needs lut1, lut2 and lut_ld >= N");
         if (p.Z != 1) return mit_set_error("mit_conv_gemm: the row-lookup epilogue is for Z == 1 launches");
@@ -332,75 +277,81 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
     if (p.Z > 65535) return mit_set_error("mit_conv_gemm: Z too large");
     if (p.nprod != 0 && p.nprod != 1) return mit_set_error("mit_conv_gemm: nprod must be 0 (the GEMM mode) or 1 (one bf16 product) (got %d)", p.nprod);
     if (p.nprod == 1 && !p.w_split) return mit_set_error("mit_conv_gemm: nprod = 1 needs w_split (mit_gemm_split_pack): there is no fp32 fallback for a requested precision");
-    // The fast kernels index A with 32-bit element offsets.  A batch whose activations exceed 2^31 elements (16 pages of
-    // 2048 x 1456 x 64: LaMa's first stride-2 conv) is cut into runs of whole images that fit, instead of falling to the generic kernel.
-    // Round 6: in the split mode the runs are cut to what the buffer-load tiles address (2^31 BYTES per run: buf_eligible) when one
-    // image fits that — every run is still thousands of workgroups, and each takes the "u" tile instead of its "o" twin.
-    bool want_buf = false;
-    if (cfg < 0 && p.Z == 1 && p.NB > 1 && (gemm_mode_now() == 6 || p.nprod == 1) && p.w_split != nullptr && split_eligible(p, 16)) {
-        MitConvGemm one = p;
-        one.NB = 1;
-        want_buf = buf_eligible(one);
+    return 0;
+}
+
+// stage 2a: images per run of an automatic launch (p.NB: the batch is not cut).
+// The fast kernels index A with 32-bit element offsets.  A batch whose activations exceed 2^31 elements (16 pages of
+// 2048 x 1456 x 64: LaMa's first stride-2 conv) is cut into runs of whole images that fit, instead of falling to the generic kernel.
+// Round 6: in the split mode the runs are cut to what the buffer-load tiles address (2^31 BYTES per run: buf_eligible) when one
+// image fits that — every run is still thousands of workgroups, and each takes the "u" tile instead of its "o" twin.
+int images_per_run(const MitConvGemm &p) {
+    if (p.Z != 1 || p.NB <= 1) return p.NB;
+    MitConvGemm q = p;
+    q.NB = 1;
+    const bool want_buf = (gemm_mode_now() == 6 || p.nprod == 1) && p.w_split != nullptr && split_eligible(p, 16) && buf_eligible(q);
+    auto run_ok = [&](const MitConvGemm &r) { return fast_eligible(r, 16) && (!want_buf || buf_eligible(r)); };
+    if (p.Cin % 16 != 0 || p.ntaps > FAST_MAX_TAPS || p.a_bs <= 0 || run_ok(p) || !fast_eligible(q, 16)) return p.NB;
+    int nb = p.NB;
+    while (nb > 1) {
+        q.NB = nb;
+        if (run_ok(q)) break;
+        nb = (nb + 1) / 2;
     }
-    auto run_ok = [&](const MitConvGemm &q) { return fast_eligible(q, 16) && (!want_buf || buf_eligible(q)); };
-    if (cfg < 0 && p.Z == 1 && p.NB > 1 && p.Cin % 16 == 0 && p.ntaps <= FAST_MAX_TAPS && p.a_bs > 0 && !run_ok(p)) {
-        MitConvGemm one = p;
-        one.NB = 1;
-        if (fast_eligible(one, 16)) {
-            int nbc = p.NB;
-            while (nbc > 1) {
-                one.NB = nbc;
-                if (run_ok(one)) break;
-                nbc = (nbc + 1) / 2;
-            }
-            for (int b0 = 0; b0 < p.NB; b0 += nbc) {
-                MitConvGemm sub = *d;
-                sub.NB = p.NB - b0 < nbc ? p.NB - b0 : nbc;
-                sub.a = d->a + (int64_t)b0 * d->a_bs;
-                sub.c.base = d->c.base + (int64_t)b0 * d->c.bs;
-                if (d->pre.base) sub.pre.base = d->pre.base + (int64_t)b0 * d->pre.bs;
-                if (d->post.base) sub.post.base = d->post.base + (int64_t)b0 * d->post.bs;
-                if (d->lut_rows) sub.lut_rows = d->lut_rows + (int64_t)b0 * p.Ho * p.Wo;
-                if (g_next_alg_flops >= 0.0) g_next_alg_flops = -1.0;  // a tagged cost does not survive the split
-                const int rc = mit_conv_gemm_cfg(&sub, -1, stream);
-                if (rc) return rc;
-            }
-            return 0;
-        }
-    }
-    if (p.nprod == 1) {  // (after the cut into runs above: a batch past 2^31 elements is eligible run by run)
+    return nb;
+}
+// the run of `nb` images from image b0 on
+MitConvGemm run_of(const MitConvGemm &p, int b0, int nb) {
+    MitConvGemm r = p;
+    r.NB = nb;
+    r.a += (int64_t)b0 * p.a_bs;
+    r.c.base += (int64_t)b0 * p.c.bs;
+    if (p.pre.base) r.pre.base += (int64_t)b0 * p.pre.bs;
+    if (p.post.base) r.post.base += (int64_t)b0 * p.post.bs;
+    if (p.lut_rows) r.lut_rows += (int64_t)b0 * p.Ho * p.Wo;
+    return r;
+}
+
+// stage 2b: the tile of one run (cfg < 0: the automatic choice) and what that tile refuses
+int plan_run(const MitConvGemm &p, int cfg, int *tile) {
+    const int64_t M = (int64_t)p.NB * p.Ho * p.Wo;
+    if (p.nprod == 1) {  // (per run: a batch past 2^31 elements is eligible run by run)
         if (!split_eligible(p, 16))
             return mit_set_error("mit_conv_gemm: nprod = 1 needs the split tiles' preconditions (Cin %% 16 == 0, <= %d taps, 32-bit element offsets, 16-byte aligned w_split with w_zs1 == 0 and Kw %% 8 == 0): there is no fp32 fallback for a requested precision", FAST_MAX_TAPS);
-        if (cfg >= 0 && cfg < kNumCfgs && !strstr(kCfgs[cfg].name, "p1")) return mit_set_error("mit_conv_gemm: nprod = 1 with tile %s, which is not a one-product tile", kCfgs[cfg].name);
+        if (cfg >= 0 && cfg < kNumCfgs && kCfgs[cfg].nprod() != 1) return mit_set_error("mit_conv_gemm: nprod = 1 with tile %s, which is not a one-product tile", kCfgs[cfg].name);
     }
-    if (cfg < 0) cfg = pick_cfg(p, M64);
+    if (cfg < 0) cfg = pick_cfg(p, M);
     if (cfg >= kNumCfgs) return mit_set_error("mit_conv_gemm: bad cfg %d", cfg);
     const CfgEntry &c = kCfgs[cfg];
+    const bool fast = c.family == TileFamily::fast, split = c.family == TileFamily::split, gemv = c.family == TileFamily::gemv;
     if (p.lut_rows) {  // the row-lookup epilogue exists as an instantiation of the vector store path of the fast / split tiles only
-        if (c.fast != 1 && c.fast != 4)
+        if (!fast && !split)
             return mit_set_error("mit_conv_gemm: the row-lookup epilogue (lut_rows) needs a fast or split tile (Cin %% 16 == 0, <= %d taps); this launch takes %s", FAST_MAX_TAPS, c.name);
         if (!(p.act & MIT_ACT_VEC_OK)) return mit_set_error("mit_conv_gemm: lut_rows needs the float4 epilogue (N %% 4 == 0, 16-byte aligned maps, tables and lut_ld %% 4 == 0)");
         if (p.post.base) return mit_set_error("mit_conv_gemm: lut_rows together with a post residual is not implemented");
         if ((p.act & 0xff) != MIT_ACT_NONE && (p.act & 0xff) != MIT_ACT_RELU) return mit_set_error("mit_conv_gemm: lut_rows is implemented for act none / relu");
     }
-    if (p.dyn && c.fast == 3) return mit_set_error("mit_conv_gemm: the device-side step offset (dyn) is not implemented by the N <= 4 kernel");
+    if (p.dyn && gemv) return mit_set_error("mit_conv_gemm: the device-side step offset (dyn) is not implemented by the N <= 4 kernel");
     if (p.dyn && ((p.a_dyn | p.c_dyn) & 3)) return mit_set_error("mit_conv_gemm: a_dyn / c_dyn must be multiples of 4 floats");
-    if (c.fast == 3) {
-        const int lpr = (!strcmp(c.name, "gemv16") || !strcmp(c.name, "gemv16n1")) ? 16 : 4;
-        if (!gemv_eligible(p, lpr) || p.N > c.BN)
-            return mit_set_error("mit_conv_gemm: cfg %s needs N <= %d, Z == 1, unsplit maps and Cin %% %d == 0", c.name, c.BN, 4 * lpr);
-    }
-    if (c.fast == 4 && !split_eligible(p, c.BK))
+    if (gemv && (!gemv_eligible(p, c.lanes_per_row()) || p.N > c.BN))
+        return mit_set_error("mit_conv_gemm: cfg %s needs N <= %d, Z == 1, unsplit maps and Cin %% %d == 0", c.name, c.BN, 4 * c.lanes_per_row());
+    if (split && !split_eligible(p, c.BK))
         return mit_set_error("mit_conv_gemm: cfg %s needs w_split (mit_gemm_split_pack, 16-byte aligned, w_zs1 == 0, Kw %% 8 == 0) and the fast tiles' preconditions", c.name);
-    if (c.fast == 1 && !fast_eligible(p, c.BK))
+    if (fast && !fast_eligible(p, c.BK))
         return mit_set_error("mit_conv_gemm: cfg %s needs Cin %% %d == 0, <= %d taps and 32-bit element offsets", c.name, c.BK, FAST_MAX_TAPS);
-    const int M = (int)M64;
+    if ((M + c.BM - 1) / c.BM * ((p.N + c.BN - 1) / c.BN) > 0x7fffffffLL) return mit_set_error("mit_conv_gemm: grid too large");
+    *tile = cfg;
+    return 0;
+}
+
+// stage 3: one planned run, inside the probe while it is enabled
+int launch_run(const MitConvGemm &p, int cfg, hipStream_t hs) {
+    const CfgEntry &c = kCfgs[cfg];
+    const int M = p.NB * p.Ho * p.Wo;
     const int MT = (M + c.BM - 1) / c.BM;
     const int NT = (p.N + c.BN - 1) / c.BN;
     const int Ktot = p.ntaps * p.Cin;
     const int KT = (Ktot + c.BK - 1) / c.BK;
-    if ((int64_t)MT * NT > 0x7fffffffLL) return mit_set_error("mit_conv_gemm: grid too large");
-    hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
     const double tagged = g_next_alg_flops;
     g_next_alg_flops = -1.0;
     if (g_probe_on) {
@@ -421,6 +372,47 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return mit_set_error("mit_conv_gemm: launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
+}  // namespace
+
+// The cut is applied twice, as two nested loops: to 2^31 elements first, and each such run — only now eligible for the split tiles — to
+// the 2^31 bytes of the buffer-load tiles.  (Sixteen 2048 x 1456 x 64 pages run as 2 x 4 runs of two.)
+extern "C" int mit_conv_gemm_plan(const MitConvGemm *d, int cfg, int32_t *tile, int32_t *nb_run) {
+    if (!tile || !nb_run) return mit_set_error("mit_conv_gemm_plan: null output");
+    MitConvGemm p;
+    if (int rc = validate(d, p)) return rc;
+    if (cfg < 0)
+        for (int pass = 0; pass < 2; ++pass) {
+            const int nb = images_per_run(p);
+            if (nb < p.NB) p = run_of(p, 0, nb);
+        }
+    int t = -1;
+    if (int rc = plan_run(p, cfg, &t)) return rc;
+    *tile = t, *nb_run = p.NB;
+    return 0;
+}
+
+extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
+    MitConvGemm p;
+    if (int rc = validate(d, p)) return rc;
+    hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+    int tile = -1;
+    const int nb1 = cfg < 0 ? images_per_run(p) : p.NB;
+    if (nb1 == p.NB) {
+        if (int rc = plan_run(p, cfg, &tile)) return rc;
+        return launch_run(p, tile, hs);
+    }
+    for (int b1 = 0; b1 < p.NB; b1 += nb1) {  // (a shorter last run is planned by itself)
+        const MitConvGemm r1 = run_of(p, b1, p.NB - b1 < nb1 ? p.NB - b1 : nb1);
+        const int nb2 = images_per_run(r1);
+        for (int b2 = 0; b2 < r1.NB; b2 += nb2) {
+            const MitConvGemm r2 = run_of(r1, b2, r1.NB - b2 < nb2 ? r1.NB - b2 : nb2);
+            g_next_alg_flops = -1.0;  // a tagged cost does not survive the cut
+            if (int rc = plan_run(r2, -1, &tile)) return rc;
+            if (int rc = launch_run(r2, tile, hs)) return rc;
+        }
+    }
     return 0;
 }
 

@@ -710,14 +710,6 @@ __global__ __launch_bounds__(256) void conv_gemv_kernel(const MitConvGemm p, con
     }
 }
 
-struct CfgEntry {
-    const char *name;
-    int BM, BN, BK;
-    void (*launch)(const MitConvGemm &, int M, int MT, int NT, int KT, hipStream_t);
-    int fast;  // 1: conv_gemm_fast_kernel (needs fast_eligible()); 3: conv_gemv_kernel (needs gemv_eligible()); 4: conv_gemm_split_kernel (needs split_eligible())
-    const char *kernel;  // the kernel's template-id as profilers print it, e.g. "conv_gemm_fast_kernel<128, 128, 16, 1, 4, 4, 4>"
-};
-
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
 size_t smem_bytes() {
     constexpr int LDA = BM + (BK == 16 ? 2 : 1);
@@ -728,7 +720,7 @@ size_t smem_bytes() {
 }
 
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
-void launch_cfg(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {
+void launch_generic(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {
     dim3 grid(MT * NT, p.Z, 1);
     size_t smem = smem_bytes<BM, BN, BK, WAVES_M, WAVES_N>();
     auto kern = conv_gemm_kernel<BM, BN, BK, WAVES_M, WAVES_N>;

@@ -192,11 +192,11 @@ __device__ __forceinline__ void pg_store_rows(const MitPGemm &p, f32x16 (&acc)[T
     }
 }
 
-// ---- planar epilogue (OUTP = 1 | 2): acc[mi][ni] holds D[row = n local][col = m local] (operands swapped in the MFMA), lane (li, lh):
+// ---- planar epilogue (OUTP = 1): acc[mi][ni] holds D[row = n local][col = m local] (operands swapped in the MFMA), lane (li, lh):
 // m = li, register r <-> n = (r & 3) + 4 lh + 8 (r >> 2).  v_permlane32_swap exchanges the upper half-wave of its first operand with the
 // lower half-wave of its second: after swapping register q of cell 2 pp with register q of cell 2 pp + 1 (q < 4) a lane of half lh holds
-// all eight columns of cell 2 pp + lh.  (OUTP = 2 does the same exchange with __shfl_xor(.., 32): the reference form for scripts/pgemm_check.)
-template <int TM, int TN, int ACT, int OUTP>
+// all eight columns of cell 2 pp + lh.
+template <int TM, int TN, int ACT>
 __device__ __forceinline__ void pg_store_planes(const MitPGemm &p, f32x16 (&acc)[TM][TN], const int z, const int m0w, const int n0w,
                                                 const int lane) {
     const int li = lane & 31, lh = lane >> 5;
@@ -227,15 +227,9 @@ __device__ __forceinline__ void pg_store_planes(const MitPGemm &p, f32x16 (&acc)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const unsigned int x = __float_as_uint(acc[mi][ni][8 * pp + q]), y = __float_as_uint(acc[mi][ni][8 * pp + 4 + q]);
-                    if (OUTP == 1) {
-                        const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);  // x' = [x.lo, y.lo], y' = [x.hi, y.hi]
-                        v0[q] = __uint_as_float(sw[0]);
-                        v1[q] = __uint_as_float(sw[1]);
-                    } else {  // the same exchange through a cross-half shuffle: each lane sends what the other half's cell lacks
-                        const unsigned int got = (unsigned int)__shfl_xor((int)(lh ? x : y), 32);
-                        v0[q] = __uint_as_float(lh ? got : x);
-                        v1[q] = __uint_as_float(lh ? y : got);
-                    }
+                    const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);  // x' = [x.lo, y.lo], y' = [x.hi, y.hi]
+                    v0[q] = __uint_as_float(sw[0]);
+                    v1[q] = __uint_as_float(sw[1]);
                 }
                 const int m = m0w + mi * 32 + li;
                 v0 = v0 * sc[ni][pp][0] + bi[ni][pp][0];
@@ -265,23 +259,21 @@ __device__ __forceinline__ void pg_epilogue(const MitPGemm &p, f32x16 (&acc)[TM]
         pg_store_rows<TM, TN>(p, acc, tbuf, z, m0w, n0w, lane);
     } else {
         switch (p.act & 0xff) {  // the activations the plain GEMMs of the path use; anything else is refused by the launcher
-            case MIT_ACT_RELU: pg_store_planes<TM, TN, MIT_ACT_RELU, OUTP>(p, acc, z, m0w, n0w, lane); break;
-            case MIT_ACT_GELU: pg_store_planes<TM, TN, MIT_ACT_GELU, OUTP>(p, acc, z, m0w, n0w, lane); break;
-            default: pg_store_planes<TM, TN, MIT_ACT_NONE, OUTP>(p, acc, z, m0w, n0w, lane); break;
+            case MIT_ACT_RELU: pg_store_planes<TM, TN, MIT_ACT_RELU>(p, acc, z, m0w, n0w, lane); break;
+            case MIT_ACT_GELU: pg_store_planes<TM, TN, MIT_ACT_GELU>(p, acc, z, m0w, n0w, lane); break;
+            default: pg_store_planes<TM, TN, MIT_ACT_NONE>(p, acc, z, m0w, n0w, lane); break;
         }
     }
 }
 
-// VAR: schedule variants for scripts/pgemm_check (same results): 16 = all DMA pieces of an iteration right behind the first fragment reads, in the shadow of their latency, instead of
-// spread behind the MFMA groups; 32 = s_setprio 1 around the MFMAs
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NPROD, int OUTP, int MINW, int VAR = 0>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NPROD, int OUTP, int MINW>
 __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(const MitPGemm p, const int MT, const int NT, const int KT,
                                                                            const int tiles_total, const int order) {
     constexpr int NW = WAVES_M * WAVES_N, NTHR = 64 * NW;
     constexpr int KH = 2;  // 16-byte cells along k per K-tile (BK = 16: one MFMA k step)
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, TM = WM / 32, TN = WN / 32;
     static_assert(TM >= 1 && TN >= 1 && WM % 32 == 0 && WN % 32 == 0, "wave tile");
-    static_assert(NS >= 2 && NS <= 4, "ring depth");
+    static_assert(NS == 3, "ring depth (two and four stages were measured and removed: DESIGN.md)");
     static_assert(NPROD == 6 || NPROD == 9, "plane pairs");
     constexpr int A_CELLS = 3 * KH * BM, B_CELLS = 3 * KH * BN;
     constexpr int GA = (A_CELLS + NTHR - 1) / NTHR, GB = (B_CELLS + NTHR - 1) / NTHR, G = GA + GB;  // DMA pieces per wave and K-tile
@@ -396,14 +388,10 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
     {                                                                                                            \
         if constexpr (TM >= 1) af[PA[o]][0] = lds_read16<(PA[o] * KH * BM) * 16>(aa);                            \
         if constexpr (TM >= 2) af[PA[o]][TM >= 2 ? 1 : 0] = lds_read16<(PA[o] * KH * BM + 32) * 16>(aa);         \
-        if constexpr (TM >= 3) af[PA[o]][TM >= 3 ? 2 : 0] = lds_read16<(PA[o] * KH * BM + 64) * 16>(aa);         \
-        if constexpr (TM >= 4) af[PA[o]][TM >= 4 ? 3 : 0] = lds_read16<(PA[o] * KH * BM + 96) * 16>(aa);         \
         if constexpr (TN >= 1) bf[PB[o]][0] = lds_read16<(PB[o] * KH * BN) * 16>(ba);                            \
         if constexpr (TN >= 2) bf[PB[o]][TN >= 2 ? 1 : 0] = lds_read16<(PB[o] * KH * BN + 32) * 16>(ba);         \
-        if constexpr (TN >= 3) bf[PB[o]][TN >= 3 ? 2 : 0] = lds_read16<(PB[o] * KH * BN + 64) * 16>(ba);         \
-        if constexpr (TN >= 4) bf[PB[o]][TN >= 4 ? 3 : 0] = lds_read16<(PB[o] * KH * BN + 96) * 16>(ba);         \
     }
-        static_assert(TM <= 4 && TN <= 4, "fragment read macro");
+        static_assert(TM <= 2 && TN <= 2, "fragment read macro");
         auto tie_group = [&](const int o) __attribute__((always_inline)) {
 #pragma unroll
             for (int mi = 0; mi < TM; ++mi) lds_tie(af[PA[o]][mi]);
@@ -422,9 +410,7 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
                 }
         };
         constexpr int PER = (G + 2) / 3;  // DMA pieces behind each of the first three MFMA groups
-        int dma_calls = 0;  // (compile-time after unrolling: with VAR & 16 the first three calls issue, the later ones are empty)
         auto dma_group = [&](const int g) __attribute__((always_inline)) {
-            if ((VAR & 16) != 0 && dma_calls++ >= 3) return;  // VAR & 16: the first three calls (ahead of the MFMAs) issue, the ones behind the MFMA groups are empty
             __builtin_amdgcn_sched_barrier(0);
             if (do_issue) {  // wave-uniform: a scalar branch around the pieces; ONE instance of the MFMA chain keeps the accumulators in place
 #pragma unroll
@@ -438,14 +424,8 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
             // they are needed) so that their registers can be the ones planes 2 leave — twelve fragments live instead of eighteen
             MIT_PG_READ_GROUP(0)
             MIT_PG_READ_GROUP(1)
-            if constexpr ((VAR & 16) != 0) {
-                dma_group(0);
-                dma_group(1);
-                dma_group(2);
-            }
             lds_wait<TM + TN>();
             tie_group(0);
-            if constexpr ((VAR & 32) != 0) __builtin_amdgcn_s_setprio(1);
             mfma_pair(3);
             dma_group(0);
             lds_wait<0>();
@@ -461,7 +441,6 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
             mfma_pair(6);
             mfma_pair(7);
             mfma_pair(8);
-            if constexpr ((VAR & 32) != 0) __builtin_amdgcn_s_setprio(0);
         } else {
             MIT_PG_READ_GROUP(0)
             MIT_PG_READ_GROUP(1)
@@ -488,90 +467,6 @@ __global__ __launch_bounds__(64 * WAVES_M *WAVES_N, MINW) void pgemm_kernel(cons
             ++issued;
         }
     zero_acc();
-
-    if constexpr ((VAR & 64) != 0) {
-        // ---- ping-pong form (round 6 experiment): eight waves = two per SIMD (waves w and w + 4 share one); the second
-        // half runs ONE barrier behind the first, so that between any two barriers one wave of a SIMD is in its compute segment (the 24
-        // MFMAs of a K-tile, nothing else, s_setprio 1) and its partner in its load segment (fragment reads of its next K-tile, the DMA
-        // pieces of K-tile + NS - 1, the counted wait).  Two barriers per K-tile; per accumulator the same pairs in the same order as
-        // every other tile.  Hazards (g = global barrier count, first half: L(t) in [2t, 2t+1], C(t) in [2t+1, 2t+2]; second half one
-        // later): a stage is re-filled in L(t) with K-tile t + NS - 1 after both halves' reads of K-tile t - 1 have completed
-        // (lgkmcnt(0) before the barrier that ends every L); every wave has waited for its own pieces of K-tile t + 1 before barrier
-        // 2t + 2, the first barrier ahead of anybody's reads of it.
-        static_assert(NW == 8 && NPROD == 6 && TM <= 2 && TN <= 2, "ping-pong form: 8 waves, 6 pairs, 64 x 64 wave tile");
-        const bool second = wave >= NW / 2;
-        bf16x8 af[3][TM], bf[3][TN];
-        int it = 0, slot = 0, fslot = NS - 1;
-        for (int ti = 0;; ++ti) {
-            wait_vmcnt<0>();
-            wg_barrier();
-            if (ti > 0) {
-                const int t = tile_lo + (ti - 1) * tile_step;
-                const int z = uni(t / tiles_per_z), tt = t - z * tiles_per_z;
-                const int mt = uni(tt / NT), nt = tt - mt * NT;
-                float *tbuf = reinterpret_cast<float *>(ring + fslot * STAGE) + wave * (32 * EPI_PITCH);
-                pg_epilogue<TM, TN, OUTP>(p, acc, tbuf, z, mt * BM + wm0, nt * BN + wn0, lane);
-                if (ti == tile_n) break;
-                if (OUTP == 0) wg_barrier();
-            }
-            zero_acc();
-            if (second) wg_barrier();  // the stagger
-            for (int kt = 0; kt < KT; ++kt, ++it) {
-                // -- load segment
-                const unsigned int aa = a_frag0 + (unsigned int)slot * (STAGE * 16u), ba = b_frag0 + (unsigned int)slot * (STAGE * 16u);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-                    af[pl][0] = pl == 0 ? lds_read16<0>(aa) : pl == 1 ? lds_read16<(1 * KH * BM) * 16>(aa) : lds_read16<(2 * KH * BM) * 16>(aa);
-                    if constexpr (TM >= 2)
-                        af[pl][TM >= 2 ? 1 : 0] = pl == 0 ? lds_read16<32 * 16>(aa) : pl == 1 ? lds_read16<(1 * KH * BM + 32) * 16>(aa) : lds_read16<(2 * KH * BM + 32) * 16>(aa);
-                    bf[pl][0] = pl == 0 ? lds_read16<0>(ba) : pl == 1 ? lds_read16<(1 * KH * BN) * 16>(ba) : lds_read16<(2 * KH * BN) * 16>(ba);
-                    if constexpr (TN >= 2)
-                        bf[pl][TN >= 2 ? 1 : 0] = pl == 0 ? lds_read16<32 * 16>(ba) : pl == 1 ? lds_read16<(1 * KH * BN + 32) * 16>(ba) : lds_read16<(2 * KH * BN + 32) * 16>(ba);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                const bool do_issue = issued < total;
-                if (do_issue) {
-#pragma unroll
-                    for (int i = 0; i < G; ++i) issue_piece(fslot, i);
-                    issue_done();
-                }
-                issued += do_issue ? 1 : 0;
-                __builtin_amdgcn_sched_barrier(0);
-                {
-                    const int ahead = issued - it - 2;  // K-tiles issued behind K-tile it + 1
-                    if (ahead <= 0) wait_vmcnt<0>();
-                    else if (ahead == 1 || NS == 3) wait_vmcnt<G>();
-                    else wait_vmcnt<2 * G>();
-                }
-                lds_wait<0>();
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-                    for (int mi = 0; mi < TM; ++mi) lds_tie(af[pl][mi]);
-#pragma unroll
-                    for (int ni = 0; ni < TN; ++ni) lds_tie(bf[pl][ni]);
-                }
-                wg_barrier();
-                // -- compute segment
-                __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-                for (int pr = 3; pr < 9; ++pr)
-#pragma unroll
-                    for (int mi = 0; mi < TM; ++mi)
-#pragma unroll
-                        for (int ni = 0; ni < TN; ++ni)
-                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[kSplitPA[pr]][mi], bf[kSplitPB[pr]][ni], acc[mi][ni], 0, 0, 0);
-                __builtin_amdgcn_s_setprio(0);
-                __builtin_amdgcn_sched_barrier(0);
-                wg_barrier();
-                fslot = slot;
-                slot = slot + 1 == NS ? 0 : slot + 1;
-            }
-            if (!second) wg_barrier();  // the halves meet again for the epilogue
-        }
-        return;
-    }
 
     // ---- the walk over this workgroup's output tiles and their K-tiles (`it` counts K-tiles over all of them; the DMA runs NS-1 of
     // them ahead, across tile boundaries).  The DMA pieces of K-tile `it` must have landed before its fragments are read.  In issue
@@ -842,12 +737,12 @@ struct PgTile {
     PgLaunch launch;
 };
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NPROD, int OUTP, int MINW, int VAR = 0>
+template <int BM, int BN, int WAVES_M, int WAVES_N, int NS, int NPROD, int OUTP, int MINW>
 void pg_launch(const MitPGemm &p, int MT, int NT, int KT, int tiles, int grid, int order, hipStream_t s) {
     constexpr int NTHR = 64 * WAVES_M * WAVES_N, KH = 2;
     constexpr int GA = (3 * KH * BM + NTHR - 1) / NTHR, GB = (3 * KH * BN + NTHR - 1) / NTHR;
     const size_t smem = (size_t)NS * (GA + GB) * NTHR * 16;
-    auto kern = pgemm_kernel<BM, BN, WAVES_M, WAVES_N, NS, NPROD, OUTP, MINW, VAR>;
+    auto kern = pgemm_kernel<BM, BN, WAVES_M, WAVES_N, NS, NPROD, OUTP, MINW>;
     static DynSmemOptIn optin;
     optin.ensure(reinterpret_cast<const void *>(kern), smem);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHR), smem, s, p, MT, NT, KT, tiles, order);
@@ -861,10 +756,11 @@ void pg_rows_launch(const MitPGemm &p, int, int, int, int, int, int, hipStream_t
 
 #define PG_TILE(name, BM, BN, WMV, WNV, NS, NPROD, OUTP, MINW, WGS) \
     {name, "pgemm_kernel<" name ">", BM, BN, NPROD, OUTP, WGS, pg_launch<BM, BN, WMV, WNV, NS, NPROD, OUTP, MINW>}
-#define PG_TILE_V(name, BM, BN, WMV, WNV, NS, NPROD, OUTP, MINW, WGS, VARV) \
-    {name, "pgemm_kernel<" name ">", BM, BN, NPROD, OUTP, WGS, pg_launch<BM, BN, WMV, WNV, NS, NPROD, OUTP, MINW, VARV>}
 const PgTile kPgTiles[] = {
-    // the shipped set (pick_tile): 128 x 128 and 128 x 64, fp32 and planar output, 6 and 9 plane pairs; 3 stages, two workgroups per CU
+    // the shipped set (mit_pgemm's choice): 128 x 128 and 128 x 64, fp32 and planar output, 6 and 9 plane pairs; 3 stages, two workgroups
+    // per CU.  The alternatives that were measured and rejected (other ring depths, 256-row tiles, a shuffle form of the planar epilogue,
+    // DMA placement and s_setprio schedules, the ping-pong tiles, other prefetch depths of the rows kernel) were removed: DESIGN.md keeps
+    // their measurements, git history their code.
     PG_TILE("pg128x128s3p6", 128, 128, 2, 2, 3, 6, 0, 2, 2),       // 0
     PG_TILE("pg128x64s3p6", 128, 64, 2, 2, 3, 6, 0, 2, 2),         // 1
     PG_TILE("pg128x128s3p6P", 128, 128, 2, 2, 3, 6, 1, 2, 2),      // 2: planar output
@@ -873,26 +769,11 @@ const PgTile kPgTiles[] = {
     PG_TILE("pg128x64s3p9", 128, 64, 2, 2, 3, 9, 0, 2, 2),         // 5
     PG_TILE("pg128x128s3p9P", 128, 128, 2, 2, 3, 9, 1, 2, 2),      // 6
     PG_TILE("pg128x64s3p9P", 128, 64, 2, 2, 3, 9, 1, 2, 2),        // 7
-    // measured alternatives (scripts/pgemm_check)
-    PG_TILE("pg128x128s2p6", 128, 128, 2, 2, 2, 6, 0, 2, 2),       // 8: two stages
-    PG_TILE("pg128x128s4p6", 128, 128, 2, 2, 4, 6, 0, 1, 1),       // 9: four stages, one workgroup per CU
-    PG_TILE("pg256x128s3p6", 256, 128, 4, 2, 3, 6, 0, 2, 1),       // 10: eight waves, wave tile 64 x 64
-    PG_TILE("pg256x128s3p6P", 256, 128, 4, 2, 3, 6, 1, 2, 1),      // 11
-    PG_TILE("pg128x128s3p6Q", 128, 128, 2, 2, 3, 6, 2, 2, 2),      // 12: 2 with the cell exchange through __shfl_xor instead of v_permlane32_swap
-    PG_TILE("pg256x256s3p6P", 256, 256, 2, 4, 3, 6, 1, 2, 1),      // 13: eight waves, wave tile 128 x 64: 12 KB of DMA per 128 x 128 of output and K-tile (24 for tile 0); the fp32-output form does not fit 256 registers
-    PG_TILE("pg256x128s4p6", 256, 128, 4, 2, 4, 6, 0, 2, 1),       // 14: 10 with four stages
-    PG_TILE_V("pg128x128s3p6d", 128, 128, 2, 2, 3, 6, 0, 2, 2, 16),  // 15: tile 0 with the DMA pieces in the shadow of the fragment reads
-    PG_TILE_V("pg128x128s3p6dp", 128, 128, 2, 2, 3, 6, 0, 2, 2, 48), // 16: ... and s_setprio around the MFMAs
-    PG_TILE_V("pg128x128s3p6p", 128, 128, 2, 2, 3, 6, 0, 2, 2, 32),  // 17: tile 0 with s_setprio around the MFMAs
-    PG_TILE_V("pg256x128s3p6pp", 256, 128, 4, 2, 3, 6, 0, 2, 1, 64),  // ping-pong halves (round 6 experiment): see the VAR & 64 loop
-    PG_TILE_V("pg128x256s3p6pp", 128, 256, 2, 4, 3, 6, 0, 2, 1, 64),
     // few-row launches (the decoder's Linears at one page): one wave per 32 x 32 block, operands streamed through registers
-    PG_ROWS_TILE("pgrows32d6p6", 6, 6, 0),    // 18: six k steps ahead (mit_pgemm_rows: the native decoder loop)
-    PG_ROWS_TILE("pgrows32d6p6P", 6, 6, 1),   // 19
-    PG_ROWS_TILE("pgrows32d6p9", 9, 6, 0),    // 20
-    PG_ROWS_TILE("pgrows32d6p9P", 9, 6, 1),   // 21
-    PG_ROWS_TILE("pgrows32d4p6", 6, 4, 0),    // 22: prefetch depth 4 (scripts/pgemm_check: 4 / 6 / 8 within 10 % of each other, 10 slower)
-    PG_ROWS_TILE("pgrows32d8p6", 6, 8, 0),    // 23: ... 8
+    PG_ROWS_TILE("pgrows32d6p6", 6, 6, 0),    // 8: six k steps ahead (mit_pgemm_rows: the native decoder loop; depths 4 / 6 / 8 measured within 10 % of each other, 10 slower)
+    PG_ROWS_TILE("pgrows32d6p6P", 6, 6, 1),   // 9
+    PG_ROWS_TILE("pgrows32d6p9", 9, 6, 0),    // 10
+    PG_ROWS_TILE("pgrows32d6p9P", 9, 6, 1),   // 11
 };
 constexpr int kNumPgTiles = sizeof(kPgTiles) / sizeof(kPgTiles[0]);
 

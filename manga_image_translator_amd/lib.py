@@ -9,7 +9,7 @@ import ctypes as C
 from pathlib import Path
 
 MIT_MAX_TAPS = 64
-MIT_ABI_VERSION = 18
+MIT_ABI_VERSION = 19
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SILU, ACT_SIGMOID, ACT_GELU = range(6)
 ACT_POST_FIRST = 0x100
@@ -191,6 +191,7 @@ SYMBOLS = {
     "mit_conv_gemm": (C.c_int, [C.POINTER(MitConvGemm), C.c_void_p]),
     "mit_conv_gemm_cfg": (C.c_int, [C.POINTER(MitConvGemm), C.c_int, C.c_void_p]),
     "mit_conv_gemm_config_name": (C.c_char_p, [C.c_int]),
+    "mit_conv_gemm_plan": (C.c_int, [C.POINTER(MitConvGemm), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mit_conv_gemm_config_kernel": (C.c_char_p, [C.c_int]),
     "mit_gemm_split_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "mit_gemm_mode_set": (C.c_int, [C.c_int]),

@@ -7,8 +7,7 @@
 //   reference  : mit_conv_gemm on the split tile (split128x128x16p6o or split128x64x16p6o), fp32 output
 //   planes     : mit_split_planes(A) must join back to A exactly (mit_join_planes)
 //   fp32 out   : every "pg*" tile with fp32 output must reproduce the reference BIT FOR BIT
-//   planar out : every "pg*P" / "pg*Q" tile must equal mit_split_planes(reference) BIT FOR BIT (the Q tile does the lane exchange of the
-//                planar epilogue with __shfl_xor: if P fails and Q passes, v_permlane32_swap pairs the halves the other way round)
+//   planar out : every "pg*P" tile must equal mit_split_planes(reference) BIT FOR BIT
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -231,7 +230,7 @@ int main(int argc, char **argv) {
             if (!tn) break;
             const std::string nm = tn;
             if (only_tile && *only_tile && nm.find(only_tile) == std::string::npos) continue;
-            const bool is_planar = nm.back() == 'P' || nm.back() == 'Q';
+            const bool is_planar = nm.back() == 'P';
             const bool is9 = nm.find("p9") != std::string::npos;
             if (is9 && s_wide9 < 0) continue;
             if (is_planar && !planar_ok) continue;

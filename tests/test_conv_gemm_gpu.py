@@ -265,3 +265,39 @@ def test_narrow_fast_tile_is_bit_identical_to_the_generic_kernel(cuda):
         generic = layer(x, cfg=names["128x32x16"])
         torch.cuda.synchronize()
         assert torch.equal(fast, generic) and torch.equal(auto, generic)
+
+
+def test_launch_is_filed_under_the_planned_tile(cuda):
+    """mit_conv_gemm_plan against what a launch does: six small launches, each the smallest that still reaches its branch of the
+    automatic choice (N <= 4 kernel, generic kernel, under-filled fp32, the BK = 32 small tile in buffer-load form in modes 6 and 9, the
+    K-tile-16 one-product tile), run under the kernel-time probe.  The probe must file each under exactly the planned tile, and the
+    planned tile is the one tests/golden/conv_gemm_plan.json pins."""
+    import ctypes as C
+    import json
+    import os
+
+    from _conv_gemm_plan_cases import GPU_CASES, desc, plan, tile_names
+    from manga_image_translator_amd import lib as L, ops
+
+    lib = L.load()
+    names = tile_names(lib)
+    golden = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_gemm_plan.json")))["gpu_cases"]
+    for name, (mode, kw) in GPU_CASES.items():
+        M, K = kw["NB"] * kw["Ho"] * kw["Wo"], kw["taps"] * kw["Cin"]
+        Kp, Np = (K + 15) // 16 * 16, (kw["N"] + 3) // 4 * 4
+        a, w, c = torch.zeros(M, kw["Cin"], device=cuda), torch.zeros(Kp, Np, device=cuda), torch.zeros(M, Np, device=cuda)
+        planes = torch.zeros(3 * Kp * Np, dtype=torch.int16, device=cuda)
+        d = desc(**kw, a=a.data_ptr(), w=w.data_ptr(), c=c.data_ptr(), w_split=planes.data_ptr())
+        with ops.gemm_mode(mode, min_tiles=0):
+            planned = plan(lib, d)
+            assert planned == golden[name], name
+            L.check(lib.mit_prof_enable(1), "mit_prof_enable")
+            try:
+                ops.launch_conv_gemm(d)
+                torch.cuda.synchronize()
+                stats, n = (L.MitProfStat * 64)(), C.c_int(0)
+                L.check(lib.mit_prof_read(stats, 64, C.byref(n)), "mit_prof_read")
+            finally:
+                lib.mit_prof_enable(0)
+        filed = {names[i]: stats[i].launches for i in range(n.value) if stats[i].launches}
+        assert filed == {planned.rsplit(":", 1)[0]: 1}, name
