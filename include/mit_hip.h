@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 19
+#define MIT_ABI_VERSION 20
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -106,11 +106,6 @@ typedef struct MitConvGemm {
      * ws_zs0 = uint16 elements between z0 slices (the z1 stride must be 0 when this is set). */
     const uint16_t *w_split;
     int64_t ws_zs0;
-    /* optional: a device-resident step counter, for launch sequences that are replayed from a hipGraph with the same arguments every
-     * time (the beam-search steps of mit_ocr48_decode): when non-NULL the A operand starts a_dyn * (*dyn) floats and the C map
-     * c_dyn * (*dyn) floats further than the descriptor says.  NULL everywhere else. */
-    const int32_t *dyn;
-    int64_t a_dyn, c_dyn;
     /* optional: a two-table row lookup joined AFTER the activation and the post residual — y += lut1[r1][n]; y += lut2[r2][n], in that
      * order — where output row m (= its pixel index, batch-major) carries lut_rows[m] = r1 | r2 << 16 and both tables have lut_ld floats
      * per row.  LaMa's masked position encoding rides on it: the 7x7 stem writes relu(bn(conv)) + alpha5 * emb[rel] + alpha6 * dir in
@@ -732,9 +727,6 @@ typedef struct MitOcr48DecodeArgs {
     float *trace_logits;        /* optional [T][N*5][dict] raw logits (pred(pred1(decoded)), :713); NULL in production */
     int32_t *trace_hist;        /* optional [T][N*5][T+1] beam tokens after each step */
     int32_t steps_run;          /* out: steps executed */
-    int32_t graph_mode;         /* 1: replay the steps from a hipGraph (one launch per step instead of 74); else launch by launch
-                                 * (the default: measured 50.2 vs 50.6 ms per page, the loop is bound by its kernels' latency, not by
-                                 * launches).  Same kernels either way: identical results. */
 } MitOcr48DecodeArgs;
 
 /* One text line to rectify: cv2.warpPerspective of the page crop [y1:y1+ch, x1:x1+cw] to (dw, dh) with inverse map minv

@@ -331,8 +331,6 @@ int plan_run(const MitConvGemm &p, int cfg, int *tile) {
         if (p.post.base) return mit_set_error("mit_conv_gemm: lut_rows together with a post residual is not implemented");
         if ((p.act & 0xff) != MIT_ACT_NONE && (p.act & 0xff) != MIT_ACT_RELU) return mit_set_error("mit_conv_gemm: lut_rows is implemented for act none / relu");
     }
-    if (p.dyn && gemv) return mit_set_error("mit_conv_gemm: the device-side step offset (dyn) is not implemented by the N <= 4 kernel");
-    if (p.dyn && ((p.a_dyn | p.c_dyn) & 3)) return mit_set_error("mit_conv_gemm: a_dyn / c_dyn must be multiples of 4 floats");
     if (gemv && (!gemv_eligible(p, c.lanes_per_row()) || p.N > c.BN))
         return mit_set_error("mit_conv_gemm: cfg %s needs N <= %d, Z == 1, unsplit maps and Cin %% %d == 0", c.name, c.BN, 4 * c.lanes_per_row());
     if (split && !split_eligible(p, c.BK))

@@ -614,7 +614,7 @@ extern "C" int mit_ocr32_decode(const MitOcr32Decoder *dec, MitOcr32DecodeArgs *
                 if (layernorm(w.y, ly.ln2_w, ly.ln2_b, w.x, E, R, x_pl, s)) return 1;
                 // feed forward (:457-460): the hidden activations exist as planes only
                 if (pgemm(ly.ff1, w.x_p, Rp, R, nullptr, 0, MIT_ACT_RELU, nullptr, 0, w.ffh_p, Rp, s)) return 1;
-                if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.y, E, MIT_ACT_NONE, w.x, E, nullptr, 0, s, 0, 0, nullptr, 0, ff2_splitk)) return 1;
+                if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.y, E, MIT_ACT_NONE, w.x, E, nullptr, 0, s, 0, 0, ff2_splitk)) return 1;
                 if (layernorm(w.y, ly.ln3_w, ly.ln3_b, out3, out3_rs, R, x_pl, s)) return 1;
             } else {
                 if (gemm(ly.qkv, w.x, E, qc + so, PE_, R, MIT_ACT_NONE, nullptr, 0, s, E, (int64_t)R * PE_)) return 1;

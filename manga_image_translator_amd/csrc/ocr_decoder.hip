@@ -12,8 +12,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include <string.h>
-#include <vector>
 #include "../../include/mit_hip.h"
 #include <atomic>
 #include "common.h"
@@ -32,7 +30,7 @@ constexpr int FF2_SPLITK_MAX_ROWS = 640;   // rows (lines x beams) up to which t
 
 struct Ws {
     float *tgt, *nrm, *qkv, *att, *q2, *ffh, *decoded, *p1, *logits, *vals, *logp, *cfeat;
-    int *idx, *hist, *done, *done_count, *dstep;
+    int *idx, *hist, *done, *done_count;
     // the few-row form (rows_path): activations that only feed a Linear live as bf16 planes [3][K / 8][Rp][8] (pgemm_rows.h)
     uint16_t *nrm_p, *att_p, *ffh_p, *dec_p, *p1_p;
     int64_t Rp;
@@ -63,14 +61,13 @@ int64_t carve(Ws *w, char *base, int N, int T, int D) {
     int *hist = (int *)take(2 * R * (T + 1) * 4);
     int *done = (int *)take((int64_t)N * 4);
     int *done_count = (int *)take(256);
-    int *dstep = (int *)take(256);
     const int64_t Rp = (R + 31) / 32 * 32;
     uint16_t *nrm_p = (uint16_t *)take(3 * E * Rp * 2);
     uint16_t *att_p = (uint16_t *)take(3 * E * Rp * 2);
     uint16_t *ffh_p = (uint16_t *)take(3 * FF * Rp * 2);
     uint16_t *dec_p = (uint16_t *)take(3 * E * Rp * 2);
     uint16_t *p1_p = (uint16_t *)take(3 * E * Rp * 2);
-    if (w) *w = Ws{tgt, nrm, qkv, att, q2, ffh, decoded, p1, logits, vals, logp, cfeat, idx, hist, done, done_count, dstep,
+    if (w) *w = Ws{tgt, nrm, qkv, att, q2, ffh, decoded, p1, logits, vals, logp, cfeat, idx, hist, done, done_count,
                    nrm_p, att_p, ffh_p, dec_p, p1_p, Rp};
     return off;
 }
@@ -82,39 +79,6 @@ __global__ void fill_int_kernel(int *p, int64_t n, int v) {
     for (; i < n; i += stride) p[i] = v;
 }
 
-__global__ void copy_hist_kernel(const int *src, int *dst, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dst[i] = src[i];
-}
-
-
-// instantiated step graphs whose launches may still be in flight; destroyed once their event has completed
-struct PendingGraph {
-    hipGraphExec_t exec;
-    hipGraph_t graph;
-    hipEvent_t done;
-};
-thread_local std::vector<PendingGraph> g_pending;
-
-void reap_graphs() {
-    size_t k = 0;
-    for (size_t i = 0; i < g_pending.size(); ++i) {
-        PendingGraph &p = g_pending[i];
-        if (p.done && hipEventQuery(p.done) == hipSuccess) {
-            (void)hipGraphExecDestroy(p.exec);
-            (void)hipGraphDestroy(p.graph);
-            (void)hipEventDestroy(p.done);
-        } else {
-            g_pending[k++] = p;
-        }
-    }
-    g_pending.resize(k);
-}
-
-}  // namespace
-
-namespace {
 std::atomic<int> g_rows_max{2560};  // 16 pages of 32 lines
 int rows_max_now() { return g_rows_max.load(std::memory_order_relaxed); }
 }  // namespace
@@ -156,10 +120,7 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
     ocrk_embed(hist[0], hist_ld, dec->embd, w.tgt, R, E, s);   // step 0: the start tokens; every later step's rows come from the beam kernel
 
     int cur = 0, steps = 0;
-    // One beam-search step as a launch sequence.  ``dyn`` == nullptr: the step-dependent arguments are host values (the classic form);
-    // ``dyn`` != nullptr: every kernel takes them from the device-resident counter w.dstep, so the SAME sequence serves every step and
-    // can be replayed from a hipGraph (one graph launch instead of 74 kernel launches per step: at one page — R = 160 rows — the loop
-    // was bound by launch cost, not by its kernels).  Both forms run the same kernels on the same operands: identical results.
+    // One beam-search step is a launch sequence on the stream (body below); its step-dependent arguments are host values.
     // rows_path: the few-row form of a step (see body).  mit_ocr48_decode_rows_max_set: largest R = 5 N it is used for; measured equal to
     // the 64 x 64 split tiles at R = 2560 (16 pages) and 2-3.5x faster per Linear at R = 160 .. 640 (profiles/r04u_pgemm_rows.log)
     const int rows_max = rows_max_now();
@@ -182,10 +143,10 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
     const bool q2_fused = ln_fused && gmode == 6 && !(q2_env && *q2_env && atoi(q2_env) == 0);
     const char *sk_env = getenv("MIT_OCR_FF2_SPLITK");
     const int ff2_splitk = (rows_path && R <= FF2_SPLITK_MAX_ROWS && !(sk_env && *sk_env && atoi(sk_env) == 0)) ? 1 : 0;
-    auto body = [&](const int step, const int *dyn, hipStream_t st) -> int {
-        const int64_t so = dyn ? 0 : (int64_t)step * E;  // host-side step offset; the dyn form adds step * E on the device
+    auto body = [&](const int step, hipStream_t st) -> int {
+        const int64_t so = (int64_t)step * E;  // the step's column block of the q / k / v and activation caches
         // (w.tgt holds the embedded tokens of this step: the start tokens before the loop, then written by the previous step's beam kernel)
-        const int Tk = dyn ? T : step + 1;  // dyn: capacity (grid / LDS); the kernels stop at *dyn + 1
+        const int Tk = step + 1;  // the self-attention's key history 0 .. step
         if (rows_path) {
             // few rows (one page .. a group of pages): every Linear on the one-wave-per-block planar GEMM (pgemm_rows.h) — the LayerNorms,
             // the attention kernels and the ReLU / GELU epilogues hand over bf16 planes, the residual stream and the K / V caches stay
@@ -198,22 +159,22 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 float *kc = w.qkv + (int64_t)(l * 3 + 1) * R * TE;
                 float *vc = w.qkv + (int64_t)(l * 3 + 2) * R * TE;
                 if (ln_fused) {
-                    if (pgemm_ln(ly.qkv, w.tgt, E, ly.ln1_w, ly.ln1_b, R, qc + so, TE, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE, dyn, E)) return 1;
+                    if (pgemm_ln(ly.qkv, w.tgt, E, ly.ln1_w, ly.ln1_b, R, qc + so, TE, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE)) return 1;
                 } else {
                     if (ocrk_layernorm(w.tgt, E, ly.ln1_w, ly.ln1_b, nullptr, 0, R, E, 1e-5f, st, &nrm_pl)) return 1;
-                    if (pgemm(ly.qkv, w.nrm_p, Rp, R, qc + so, TE, MIT_ACT_NONE, nullptr, 0, nullptr, 0, st, E, (int64_t)R * TE, dyn, E)) return 1;
+                    if (pgemm(ly.qkv, w.nrm_p, Rp, R, qc + so, TE, MIT_ACT_NONE, nullptr, 0, nullptr, 0, st, E, (int64_t)R * TE)) return 1;
                 }
-                OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1, E};
-                ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, nullptr, 0, 0, nullptr, R, 1, Tk, 1, st, 4, 80, dyn, &xs, &att_pl);
+                OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1};
+                ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, nullptr, 0, 0, nullptr, R, 1, Tk, 1, st, 4, 80, &xs, &att_pl);
                 if (pgemm(ly.out, w.att_p, Rp, R, w.tgt, E, MIT_ACT_NONE, w.tgt, E, nullptr, 0, st)) return 1;
                 const float *mk = a->mem_k + (int64_t)l * N * L * E;
                 const float *mv = a->mem_v + (int64_t)l * N * L * E;
-                OcrAttXpos xc{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 0, 0};
+                OcrAttXpos xc{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 0};
                 // norm2 + the q projection inside the cross-attention kernel where that form exists (a page or a few; else two launches)
                 bool q_inside = false;
                 if (q2_fused && ly.q2.bias && ly.q2.N == E) {
                     const OcrAttQProj qp{w.tgt, E, ly.ln2_w, ly.ln2_b, 1e-5f, ly.q2.w_split, ly.q2.ldw, ly.q2.scale, ly.q2.bias};
-                    q_inside = ocrk_cross_attention_qproj(qp, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, a->mem_len, R, L, st, dyn, &xc, &att_pl);
+                    q_inside = ocrk_cross_attention_qproj(qp, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, a->mem_len, R, L, st, &xc, &att_pl);
                 }
                 if (!q_inside) {
                     if (ln_fused) {
@@ -222,7 +183,7 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                         if (ocrk_layernorm(w.tgt, E, ly.ln2_w, ly.ln2_b, nullptr, 0, R, E, 1e-5f, st, &nrm_pl)) return 1;
                         if (pgemm(ly.q2, w.nrm_p, Rp, R, w.q2, E, MIT_ACT_NONE, nullptr, 0, nullptr, 0, st)) return 1;
                     }
-                    ocrk_attention(w.q2, E, E, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, nullptr, 0, 0, a->mem_len, R, 1, L, 5, st, 4, 80, dyn, &xc, &att_pl);
+                    ocrk_attention(w.q2, E, E, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, nullptr, 0, 0, a->mem_len, R, 1, L, 5, st, 4, 80, &xc, &att_pl);
                 }
                 if (pgemm(ly.out2, w.att_p, Rp, R, w.tgt, E, MIT_ACT_NONE, w.tgt, E, nullptr, 0, st)) return 1;
                 if (ln_fused) {
@@ -232,9 +193,9 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                     if (pgemm(ly.ff1, w.nrm_p, Rp, R, nullptr, 0, MIT_ACT_RELU, nullptr, 0, w.ffh_p, Rp, st)) return 1;
                 }
                 if (l < 4) {
-                    if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.tgt, E, MIT_ACT_NONE, w.tgt, E, nullptr, 0, st, 0, 0, nullptr, 0, ff2_splitk)) return 1;
+                    if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.tgt, E, MIT_ACT_NONE, w.tgt, E, nullptr, 0, st, 0, 0, ff2_splitk)) return 1;
                 } else {  // last layer: the step's output into the activation cache (:570), and as planes for the prediction head
-                    if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.decoded + so, TE, MIT_ACT_NONE, w.tgt, E, w.dec_p, Rp, st, 0, 0, dyn, E, ff2_splitk)) return 1;
+                    if (pgemm(ly.ff2, w.ffh_p, Rp, R, w.decoded + so, TE, MIT_ACT_NONE, w.tgt, E, w.dec_p, Rp, st, 0, 0, ff2_splitk)) return 1;
                 }
             }
             if (pgemm(dec->pred1, w.dec_p, Rp, R, nullptr, 0, MIT_ACT_GELU, nullptr, 0, w.p1_p, Rp, st)) return 1;
@@ -247,18 +208,18 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 float *vc = w.qkv + (int64_t)(l * 3 + 2) * R * TE;
                 // self attention (:565)
                 if (ocrk_layernorm(w.tgt, E, ly.ln1_w, ly.ln1_b, w.nrm, E, R, E, 1e-5f, st)) return 1;
-                if (gemm(ly.qkv, w.nrm, E, qc + so, TE, R, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE, dyn, 0, E)) return 1;
+                if (gemm(ly.qkv, w.nrm, E, qc + so, TE, R, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE)) return 1;
                 // (the XPOS rotation of the step's query and of the key history 0 .. step happens inside the attention kernel)
-                OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1, E};
-                ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, w.att, E, E, nullptr, R, 1, Tk, 1, st, 4, 80, dyn, &xs);
+                OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1};
+                ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, w.att, E, E, nullptr, R, 1, Tk, 1, st, 4, 80, &xs);
                 if (gemm(ly.out, w.att, E, w.tgt, E, R, MIT_ACT_NONE, w.tgt, E, st)) return 1;
                 // cross attention (:567)
                 if (ocrk_layernorm(w.tgt, E, ly.ln2_w, ly.ln2_b, w.nrm, E, R, E, 1e-5f, st)) return 1;
                 if (gemm(ly.q2, w.nrm, E, w.q2, E, R, MIT_ACT_NONE, nullptr, 0, st)) return 1;
                 const float *mk = a->mem_k + (int64_t)l * N * L * E;
                 const float *mv = a->mem_v + (int64_t)l * N * L * E;
-                OcrAttXpos xc{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 0, 0};
-                ocrk_attention(w.q2, E, E, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, w.att, E, E, a->mem_len, R, 1, L, 5, st, 4, 80, dyn, &xc);
+                OcrAttXpos xc{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 0};
+                ocrk_attention(w.q2, E, E, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, w.att, E, E, a->mem_len, R, 1, L, 5, st, 4, 80, &xc);
                 if (gemm(ly.out2, w.att, E, w.tgt, E, R, MIT_ACT_NONE, w.tgt, E, st)) return 1;
                 // feed forward (:568)
                 if (ocrk_layernorm(w.tgt, E, ly.ln3_w, ly.ln3_b, w.nrm, E, R, E, 1e-5f, st)) return 1;
@@ -266,21 +227,17 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 if (l < 4) {
                     if (gemm(ly.ff2, w.ffh, FF, w.tgt, E, R, MIT_ACT_NONE, w.tgt, E, st)) return 1;
                 } else {  // last layer writes the step's output straight into the activation cache (:570)
-                    if (gemm(ly.ff2, w.ffh, FF, w.decoded + so, TE, R, MIT_ACT_NONE, w.tgt, E, st, 0, 0, dyn, 0, E)) return 1;
+                    if (gemm(ly.ff2, w.ffh, FF, w.decoded + so, TE, R, MIT_ACT_NONE, w.tgt, E, st)) return 1;
                 }
             }
-            if (gemm(dec->pred1, w.decoded + so, TE, w.p1, E, R, MIT_ACT_GELU, nullptr, 0, st, 0, 0, dyn, E, 0)) return 1;
+            if (gemm(dec->pred1, w.decoded + so, TE, w.p1, E, R, MIT_ACT_GELU, nullptr, 0, st)) return 1;
             if (gemm(dec->pred, w.p1, E, w.logits, Dp, R, MIT_ACT_NONE, nullptr, 0, st)) return 1;
         }
         if (a->trace_logits)
             MIT_CHECK_HIP(hipMemcpy2DAsync(a->trace_logits + (int64_t)step * R * D, (size_t)D * 4, w.logits, (size_t)Dp * 4,
                                            (size_t)D * 4, R, hipMemcpyDeviceToDevice, st));
         ocrk_logsoftmax_top5(w.logits, Dp, R, D, a->suppress_eos ? a->end_tok : -1, w.vals, w.idx, nullptr, st);
-        if (dyn) {
-            ocrk_beam_dyn(w.vals, w.idx, hist[0], hist[1], hist_ld, logp[0], logp[1], w.done, a->res_row, a->res_len, a->res_prob, a->res_tok,
-                          w.done_count, N, dyn, a->start_tok, a->end_tok, a->max_finished, st, dec->embd, w.tgt, E);
-            ocrk_step_advance(w.dstep, st);
-        } else if (step == 0) {
+        if (step == 0) {
             ocrk_beam_init(w.vals, w.idx, hist[cur], hist_ld, logp[cur], N, a->start_tok, st, dec->embd, w.tgt, E);
         } else {
             ocrk_beam_step(w.vals, w.idx, hist[cur], hist[cur ^ 1], hist_ld, logp[cur], logp[cur ^ 1], w.done, a->res_row,
@@ -294,38 +251,8 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
         return 0;
     };
 
-    // Graph replay is OPT-IN (graph_mode = 1).  Measured on one page (32 lines, R = 160 rows, 32 steps): 50.2 ms
-    // with the graph, 50.6 ms launch by launch — the loop is bound by its kernels' own latency (a 64 x 64 GEMM tile of K = 320 takes 12 us
-    // for 20 dependent K-steps whatever launches it; rocprofv3: 46.5 ms of kernel time per call), not by the launches.  Never while
-    // tracing (per-step copies at host offsets) or probing (events around every launch).
-    const bool use_graph = a->graph_mode == 1 && !a->trace_logits && !a->trace_hist && !mit_probe_on() && T >= 4;
-    hipGraphExec_t exec = nullptr;
-    if (use_graph) {
-        reap_graphs();
-        static thread_local hipStream_t cap = nullptr;
-        if (!cap) MIT_CHECK_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-        MIT_CHECK_HIP(hipMemsetAsync(w.dstep, 0, 4, s));
-        hipGraph_t graph = nullptr;
-        MIT_CHECK_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeRelaxed));
-        const int rc = body(0, w.dstep, cap);
-        const hipError_t ce = hipStreamEndCapture(cap, &graph);
-        if (rc || ce != hipSuccess || !graph) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc ? rc : mit_set_error("mit_ocr48_decode: stream capture of a decode step failed: %s", hipGetErrorString(ce));
-        }
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            return mit_set_error("mit_ocr48_decode: hipGraphInstantiate failed: %s", hipGetErrorString(ie));
-        }
-        g_pending.push_back({exec, graph, nullptr});
-    }
     for (int step = 0; step < T; ++step) {
-        if (use_graph) {
-            MIT_CHECK_HIP(hipGraphLaunch(exec, s));
-        } else if (body(step, nullptr, s)) {
-            return 1;
-        }
+        if (body(step, s)) return 1;
         steps = step + 1;
         if (!a->suppress_eos && step >= 1 && (step % 4 == 3) && step + 1 < T) {  // early exit (:765-766) without a per-step sync;
             // with EOS suppressed no hypothesis can finish, so the loop stays fully asynchronous
@@ -334,13 +261,6 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
             MIT_CHECK_HIP(hipStreamSynchronize(s));
             if (dc >= N) break;
         }
-    }
-    if (use_graph) {  // the graph stays alive until its launches have run: an event marks that point, the next call reaps it
-        cur = steps <= 1 ? 0 : ((steps - 1) & 1);  // the buffer the last executed step wrote (step 0 and 1 -> hist[0] -> hist[1] ...)
-        hipEvent_t ev = nullptr;
-        MIT_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        MIT_CHECK_HIP(hipEventRecord(ev, s));
-        g_pending.back().done = ev;
     }
     ocrk_beam_finalize(hist[cur], hist_ld, logp[cur], w.done, a->res_row, a->res_len, a->res_prob, a->res_tok, N, steps + 1, s);
     // colour heads over every beam row's activation cache (:789-799); the caller gathers rows res_row[n]

@@ -395,27 +395,10 @@ __global__ void layernorm_kernel(const float *__restrict__ in, int64_t in_rs, co
 
 // ---- XPOS rotation (xpos_relative_position.py:36-39,54-71) on [R, T, heads*80] ----
 // position index i = i0 + t selects the sin/cos row, p = p0 + t the scale row (centred positions).
-// dstep (optional, the decoder's device-resident step counter — see ocr_decoder.hip): mode 1 = "the query of this step": the input row
-// starts step * dyn_in floats further, i0 = step, p0 = step + minpos; mode 2 = "the key history": rows t <= step only, p0 = minpos;
-// minpos = -((step + 2) / 2), the centred origin of the positions 0 .. step (python -(step + 1) // 2).
 __global__ void xpos_rotate_kernel(const float *__restrict__ in, int64_t in_rs, int64_t in_ts, float *__restrict__ out,
                                    int64_t out_rs, int64_t out_ts, int R, int T, int i0, int p0, int downscale,
                                    const float *__restrict__ cosT, const float *__restrict__ sinT,
-                                   const float *__restrict__ scaleT, const float *__restrict__ iscaleT, int pmax,
-                                   const int *__restrict__ dstep, int dyn_mode, int64_t dyn_in) {
-    int t_end = T;
-    if (dstep) {
-        const int step = *dstep;
-        const int minpos = -((step + 2) / 2);
-        if (dyn_mode == 1) {
-            in += (int64_t)step * dyn_in;
-            i0 = step;
-            p0 = step + minpos;
-        } else {
-            t_end = step + 1;
-            p0 = minpos;
-        }
-    }
+                                   const float *__restrict__ scaleT, const float *__restrict__ iscaleT, int pmax) {
     // one thread per (r, t, pair j of 160 pairs = 4 heads x 40)
     const int64_t total = (int64_t)R * T * 160;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -425,7 +408,6 @@ __global__ void xpos_rotate_kernel(const float *__restrict__ in, int64_t in_rs, 
         const int64_t rt = i / 160;
         const int t = (int)(rt % T);
         const int r = (int)(rt / T);
-        if (t >= t_end) continue;
         const int j = pair % 40;
         const int ii = i0 + t, pp = p0 + t + pmax;
         const float sc = downscale ? iscaleT[pp * 40 + j] : scaleT[pp * 40 + j];
@@ -444,10 +426,8 @@ __global__ void xpos_rotate_kernel(const float *__restrict__ in, int64_t in_rs, 
 __global__ void attention_kernel(const float *__restrict__ Q, int64_t q_rs, int64_t q_ts, const float *__restrict__ K,
                                  int64_t k_rs, int64_t k_ts, const float *__restrict__ V, int64_t v_rs, int64_t v_ts,
                                  float *__restrict__ O, int64_t o_rs, int64_t o_ts, const int *__restrict__ klen, int Tk,
-                                 int kv_div, int HD, const int *__restrict__ dstep, OcrAttXpos xp, OcrPlanes opl) {
-    // dstep without folded rotation / with rotated keys: the decoder's self-attention over the tokens 0 .. step (LDS is sized for the longest history)
-    if (dstep && (!xp.cos_t || xp.rot_k)) Tk = *dstep + 1;
-    const int step = dstep ? *dstep : xp.step;
+                                 int kv_div, int HD, OcrAttXpos xp, OcrPlanes opl) {
+    const int step = xp.step;
     const int minpos = -((step + 2) / 2);
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [HD] q + [Tk] weights
     float *qs = lds;
@@ -458,7 +438,6 @@ __global__ void attention_kernel(const float *__restrict__ Q, int64_t q_rs, int6
     const float *q = Q + (int64_t)r * q_rs + (int64_t)tq * q_ts + h * HD;
     const int HP = HD / 2;
     if (xp.cos_t) {  // the query of position `step`, rotated on the way into LDS (xpos_rotate_kernel's expression, scale up)
-        if (dstep) q += (int64_t)step * xp.q_dyn;
         const int pp = step + minpos + xp.pmax;
         for (int j = lane; j < HP; j += 64) {
             const float sc = xp.scale_t[pp * HP + j];
@@ -563,22 +542,21 @@ template <int heads, int HD>   // compile-time: the staging loops divide by E / 
 // (argument order: what the first batch of loads needs comes first — twelve dwords are preloaded into SGPRs with the wave, build.py;
 // the token stride of K and V is E, checked by the launcher)
 __global__ __launch_bounds__(256) void attention_self_kernel(const float *__restrict__ K, int64_t k_rs, const float *__restrict__ V, int64_t v_rs,
-                                                             const float *__restrict__ Q, int64_t q_rs, int TkCap, const int *__restrict__ dstep,
+                                                             const float *__restrict__ Q, int64_t q_rs, int Tk,
                                                              float *__restrict__ O, int64_t o_rs, OcrAttXpos xp, OcrPlanes opl) {
     constexpr int64_t k_ts = (int64_t)heads * HD, v_ts = k_ts;
     static_assert(heads * 64 == 256 && HD % 8 == 0, "one wave per head");
-    const int Tk = dstep ? *dstep + 1 : TkCap;
-    const int step = dstep ? *dstep : xp.step;
+    const int step = xp.step;
     const int minpos = -((step + 2) / 2);
     constexpr int E = heads * HD, KP = E + 4, HP = HD / 2, TP = HP + SELF_TP_PAD;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *qs_all = lds;                      // [heads][HD]
-    float *ws_all = qs_all + E;               // [heads][TkCap]
-    float *ks = ws_all + heads * TkCap;       // [TkCap][KP]   keys, then values   (E + heads * TkCap is a multiple of 4: 16-byte aligned rows)
-    float *tc = ks + TkCap * KP;              // [TkCap][TP]   cos * iscale of (key t, pair j)
-    float *tsn = tc + TkCap * TP;             // [TkCap][TP]   sin * iscale
+    float *ws_all = qs_all + E;               // [heads][Tk]
+    float *ks = ws_all + heads * Tk;       // [Tk][KP]   keys, then values   (E + heads * Tk is a multiple of 4: 16-byte aligned rows)
+    float *tc = ks + Tk * KP;              // [Tk][TP]   cos * iscale of (key t, pair j)
+    float *tsn = tc + Tk * TP;             // [Tk][TP]   sin * iscale
     const int tid = threadIdx.x, lane = tid & 63, h = tid >> 6, r = blockIdx.x;
-    float *qs = qs_all + h * HD, *ws = ws_all + h * TkCap;
+    float *qs = qs_all + h * HD, *ws = ws_all + h * Tk;
     constexpr int E4 = E >> 2;
     const int n4 = Tk * E4;
     // ---- every global load of the kernel is requested here, in one batch: the key history, the value history (it waits in registers
@@ -615,7 +593,7 @@ __global__ __launch_bounds__(256) void attention_self_kernel(const float *__rest
     const int jq = lane < HP ? lane : 0;
     const int pp = step + minpos + xp.pmax;
     float q_sc = xp.scale_t[pp * HP + jq], q_c = xp.cos_t[step * HP + jq], q_s = xp.sin_t[step * HP + jq];
-    float2 q_x = *reinterpret_cast<const float2 *>(Q + (int64_t)r * q_rs + h * HD + (dstep ? (int64_t)step * xp.q_dyn : 0) + 2 * jq);
+    float2 q_x = *reinterpret_cast<const float2 *>(Q + (int64_t)r * q_rs + h * HD + 2 * jq);
     // rotation factors of the raw key history: entries i = t * HP + j of the tables
     constexpr int TT = 6;   // entries per thread held in registers (Tk * HP <= 256 * TT: Tk <= 38 at HP = 40); past it: a plain loop
     float fc[TT], fs[TT], fi[TT];
@@ -754,7 +732,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
                                                                           const float *__restrict__ V, int64_t v_rs, int64_t v_ts,
                                                                           float *__restrict__ O, int64_t o_rs,
                                                                           const int *__restrict__ klen, int Tk,
-                                                                          const int *__restrict__ dstep, OcrAttXpos xp, OcrPlanes opl, OcrAttQProj qp) {
+                                                                          OcrAttXpos xp, OcrPlanes opl, OcrAttQProj qp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int KP = HD + 4;                // 16-byte aligned rows; lane t reads row t as float4s (pitch 84: conflict-free per 16 lanes)
     constexpr int HD4 = HD / 4;
@@ -791,7 +769,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) fw[d][pl] = __builtin_amdgcn_raw_buffer_load_b128(rw, w_off, pl * w_plane + (unsigned int)kstep * w_step, 0);
         };
-        const int step = dstep ? *dstep : xp.step;
+        const int step = xp.step;
         constexpr int HP = HD / 2;
         const int pp = step + -((step + 2) / 2) + xp.pmax;
         // what the epilogue needs from global memory — the Linear's scale / bias and the rotation's table entries of this lane's columns —
@@ -885,15 +863,14 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
             }
         }
     } else if (xp.cos_t) {  // the beams' queries of position `step`, rotated on the way into LDS (xpos_rotate_kernel's expression, scale up)
-        const int step = dstep ? *dstep : xp.step;
+        const int step = xp.step;
         constexpr int HP = HD / 2;
         const int pp = step + -((step + 2) / 2) + xp.pmax;
-        const int64_t qo = dstep ? (int64_t)step * xp.q_dyn : 0;
         for (int i = tid; i < G * HP; i += ATT_THREADS) {
             const int g = i / HP, j = i - g * HP;
             const float sc = xp.scale_t[pp * HP + j];
             const float c = xp.cos_t[step * HP + j] * sc, sn = xp.sin_t[step * HP + j] * sc;
-            const float2 x = *reinterpret_cast<const float2 *>(Q + qo + (int64_t)(r0 + g) * q_rs + h * HD + 2 * j);
+            const float2 x = *reinterpret_cast<const float2 *>(Q + (int64_t)(r0 + g) * q_rs + h * HD + 2 * j);
             qs[g * HD + 2 * j] = x.x * c + (-x.y) * sn;
             qs[g * HD + 2 * j + 1] = x.y * c + x.x * sn;
         }
@@ -1080,14 +1057,8 @@ __global__ __launch_bounds__(ATT_THREADS) void attention_shared_kv_kernel(const 
 }
 
 // ---- embedding rows: out[r] = E[tok[r]] ----
-// dstep (optional): the token of step s is column s of the history buffer the previous step wrote — tok for s <= 1 and odd s, tok1 else
-// (the two buffers alternate, see beam_dyn_kernel)
 __global__ void embed_kernel(const int *__restrict__ tok, int64_t tok_stride, const float *__restrict__ E,
-                             float *__restrict__ out, int R, int D, const int *__restrict__ tok1, const int *__restrict__ dstep) {
-    if (dstep) {
-        const int step = *dstep;
-        tok = ((step == 0 || !((step - 1) & 1)) ? tok : tok1) + step;
-    }
+                             float *__restrict__ out, int R, int D) {
     const int64_t total = (int64_t)R * (D / 4);
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -1285,8 +1256,8 @@ __device__ __forceinline__ void beam_embed_rows(const BeamNextEmbed &next, const
 }
 
 // step 0 (:693-699): beam j of a sample takes the j-th best token of its (identical) row.
-__device__ __forceinline__ void beam_init_body(const float *__restrict__ vals, const int *__restrict__ idx, int *__restrict__ hist,
-                                               int hist_ld, float *__restrict__ logp, int N, int start_tok, const BeamNextEmbed next) {
+__global__ __launch_bounds__(64) void beam_init_kernel(const float *__restrict__ vals, const int *__restrict__ idx, int *__restrict__ hist,
+                                                       int hist_ld, float *__restrict__ logp, int N, int start_tok, BeamNextEmbed next) {
     const int n = blockIdx.x, lane = threadIdx.x;
     if (n >= N) return;
     int tok[5];
@@ -1301,18 +1272,13 @@ __device__ __forceinline__ void beam_init_body(const float *__restrict__ vals, c
     beam_embed_rows(next, n, tok, lane);
 }
 
-__global__ __launch_bounds__(64) void beam_init_kernel(const float *__restrict__ vals, const int *__restrict__ idx, int *__restrict__ hist,
-                                                       int hist_ld, float *__restrict__ logp, int N, int start_tok, BeamNextEmbed next) {
-    beam_init_body(vals, idx, hist, hist_ld, logp, N, start_tok, next);
-}
-
 // steps >= 1 (:716-771). hist_in/out [R][hist_ld]: tokens 0..step valid on input, 0..step+1 on output.
-__device__ __forceinline__ void beam_step_body(const float *__restrict__ vals, const int *__restrict__ idx,
-                                               const int *__restrict__ hist_in, int *__restrict__ hist_out, int hist_ld,
-                                               const float *__restrict__ logp_in, float *__restrict__ logp_out, int *__restrict__ done,
-                                               int *__restrict__ res_row, int *__restrict__ res_len, float *__restrict__ res_prob,
-                                               int *__restrict__ res_tok, int *__restrict__ done_count, int N, int step, int end_tok,
-                                               int max_finished, const BeamNextEmbed next) {
+__global__ __launch_bounds__(64) void beam_step_kernel(const float *__restrict__ vals, const int *__restrict__ idx,
+                                 const int *__restrict__ hist_in, int *__restrict__ hist_out, int hist_ld,
+                                 const float *__restrict__ logp_in, float *__restrict__ logp_out, int *__restrict__ done,
+                                 int *__restrict__ res_row, int *__restrict__ res_len, float *__restrict__ res_prob,
+                                 int *__restrict__ res_tok, int *__restrict__ done_count, int N, int step, int end_tok,
+                                 int max_finished, BeamNextEmbed next) {
     const int n = blockIdx.x, lane = threadIdx.x;
     if (n >= N) return;
     const bool was_done = done[n] != 0;   // (every lane reads it before lane 0 of this wave — its only writer — may set it)
@@ -1372,37 +1338,6 @@ __device__ __forceinline__ void beam_step_body(const float *__restrict__ vals, c
     beam_embed_rows(next, n, tok, lane);
 }
 
-__global__ __launch_bounds__(64) void beam_step_kernel(const float *__restrict__ vals, const int *__restrict__ idx,
-                                 const int *__restrict__ hist_in, int *__restrict__ hist_out, int hist_ld,
-                                 const float *__restrict__ logp_in, float *__restrict__ logp_out, int *__restrict__ done,
-                                 int *__restrict__ res_row, int *__restrict__ res_len, float *__restrict__ res_prob,
-                                 int *__restrict__ res_tok, int *__restrict__ done_count, int N, int step, int end_tok,
-                                 int max_finished, BeamNextEmbed next) {
-    beam_step_body(vals, idx, hist_in, hist_out, hist_ld, logp_in, logp_out, done, res_row, res_len, res_prob, res_tok, done_count, N, step,
-                   end_tok, max_finished, next);
-}
-
-// The same bookkeeping with the step read from device memory (one launch sequence serves every step, so it can be replayed from a
-// hipGraph): step 0 initialises buffer 0; step s >= 1 reads buffer (s - 1) & 1 and writes buffer s & 1.
-__global__ __launch_bounds__(64) void beam_dyn_kernel(const float *__restrict__ vals, const int *__restrict__ idx, int *__restrict__ hist0, int *__restrict__ hist1,
-                                int hist_ld, float *__restrict__ logp0, float *__restrict__ logp1, int *__restrict__ done,
-                                int *__restrict__ res_row, int *__restrict__ res_len, float *__restrict__ res_prob, int *__restrict__ res_tok,
-                                int *__restrict__ done_count, int N, const int *__restrict__ dstep, int start_tok, int end_tok, int max_finished,
-                                BeamNextEmbed next) {
-    const int step = *dstep;
-    if (step == 0) {
-        beam_init_body(vals, idx, hist0, hist_ld, logp0, N, start_tok, next);
-        return;
-    }
-    const bool odd_in = ((step - 1) & 1) != 0;
-    beam_step_body(vals, idx, odd_in ? hist1 : hist0, odd_in ? hist0 : hist1, hist_ld, odd_in ? logp1 : logp0, odd_in ? logp0 : logp1, done,
-                   res_row, res_len, res_prob, res_tok, done_count, N, step, end_tok, max_finished, next);
-}
-
-__global__ void step_advance_kernel(int *__restrict__ dstep) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *dstep += 1;
-}
-
 // fallback (:774-784): samples that never finished take the first row of their beam.
 __global__ void beam_finalize_kernel(const int *__restrict__ hist, int hist_ld, const float *__restrict__ logp,
                                      int *__restrict__ done, int *__restrict__ res_row, int *__restrict__ res_len,
@@ -1439,12 +1374,11 @@ int ocrk_layernorm(const float *in, int64_t in_rs, const float *w, const float *
 }
 
 void ocrk_xpos_rotate(const float *in, int64_t in_rs, int64_t in_ts, float *out, int64_t out_rs, int64_t out_ts, int R, int T,
-                      int i0, int p0, int downscale, const MitXposTables &tb, hipStream_t s, const int *dstep, int dyn_mode,
-                      int64_t dyn_in) {
+                      int i0, int p0, int downscale, const MitXposTables &tb, hipStream_t s) {
     const int64_t total = (int64_t)R * T * 160;
     MitProbeScope probe("xpos_rotate_kernel", s, 8.0 * (double)R * T * 320);
     hipLaunchKernelGGL(xpos_rotate_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, in, in_rs, in_ts, out, out_rs, out_ts, R,
-                       T, i0, p0, downscale, tb.cos_t, tb.sin_t, tb.scale_t, tb.iscale_t, tb.pmax, dstep, dyn_mode, dyn_in);
+                       T, i0, p0, downscale, tb.cos_t, tb.sin_t, tb.scale_t, tb.iscale_t, tb.pmax);
 }
 
 // ---- the same attention for ALL query positions of a row (the encoder's self-attention: Tq = Tk = the line's memory length): one
@@ -1709,12 +1643,11 @@ extern "C" int mit_attention_self_rows_set(int on) {
 
 void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, int64_t k_rs, int64_t k_ts, const float *V,
                     int64_t v_rs, int64_t v_ts, float *O, int64_t o_rs, int64_t o_ts, const int *klen, int R, int Tq, int Tk,
-                    int kv_div, hipStream_t s, int heads, int head_dim, const int *dstep, const OcrAttXpos *xpos, const OcrPlanes *o_planes) {
+                    int kv_div, hipStream_t s, int heads, int head_dim, const OcrAttXpos *xpos, const OcrPlanes *o_planes) {
     OcrAttXpos xp{};
     if (xpos) xp = *xpos;
     const OcrPlanes opl = (o_planes && Tq == 1) ? *o_planes : OcrPlanes{nullptr, 0, 0};
-    // (the shared-K/V form never shortens Tk by the step counter: with a step counter it is only used for the rotated query)
-    if ((!dstep || (xp.cos_t && !xp.rot_k)) && Tq == 1 && kv_div == 5 && R % kv_div == 0 && R / kv_div <= 65535 && head_dim == 80) {  // the 48px decoder's cross-attention: 5 beams, 4 x 80
+    if (Tq == 1 && kv_div == 5 && R % kv_div == 0 && R / kv_div <= 65535 && head_dim == 80) {  // the 48px decoder's cross-attention: 5 beams, 4 x 80
         // algorithmic bytes: K and V of each line read once for its kv_div beams (+ q in, o out); FLOPs 4 Tk d per query row and head
         const double bytes = 4.0 * heads * head_dim * ((double)(R / kv_div) * 2.0 * Tk + 2.0 * R), flops = 4.0 * (double)R * heads * Tk * head_dim;
         auto lds_bytes = [&](const int kchunk) { return ((size_t)kv_div * head_dim + (size_t)kchunk * (head_dim + 4) + (size_t)kv_div * Tk) * sizeof(float); };
@@ -1722,17 +1655,17 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
         if ((int64_t)heads * (R / kv_div) <= ATT_LATENCY_MAX_WGS && ATT_KCHUNK_L * (head_dim / 4) <= ATT_STAGE_L * ATT_THREADS && lds_bytes(ATT_KCHUNK_L) <= 64 * 1024) {
             MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops);
             hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK_L, ATT_STAGE_L, 80, 5>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes(ATT_KCHUNK_L), s, Q, q_rs,
-                               K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, dstep, xp, opl, OcrAttQProj{});
+                               K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, xp, opl, OcrAttQProj{});
             return;
         }
         if (ATT_KCHUNK * (head_dim / 4) <= ATT_STAGE * ATT_THREADS && lds_bytes(ATT_KCHUNK) <= 64 * 1024) {
             MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops);
             hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK, ATT_STAGE, 80, 5>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes(ATT_KCHUNK), s, Q, q_rs, K,
-                               k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, dstep, xp, opl, OcrAttQProj{});
+                               k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, xp, opl, OcrAttQProj{});
             return;
         }
     }
-    if (!dstep && !xp.cos_t && !opl.p && kv_div == 1 && Tq >= 2 * ATTR_GQ && R <= 65535 && Tq <= 65535 * 32 && head_dim <= 128 && ((q_rs | q_ts | k_rs | k_ts | v_rs | v_ts) & 3) == 0) {
+    if (!xp.cos_t && !opl.p && kv_div == 1 && Tq >= 2 * ATTR_GQ && R <= 65535 && Tq <= 65535 * 32 && head_dim <= 128 && ((q_rs | q_ts | k_rs | k_ts | v_rs | v_ts) & 3) == 0) {
         const size_t sm = ((size_t)Tk * (head_dim + 4) + (size_t)(ATTR_THREADS / 64) * ATTR_GQ * (head_dim + Tk)) * sizeof(float);
         if (sm <= 150 * 1024 && head_dim % 8 == 0) {
             // algorithmic bytes: q, k, v read once and o written once per row; FLOPs 4 Tk d per query and head
@@ -1752,7 +1685,7 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
             // the decoder's self-attention: the row's key history staged once for its four heads (bitwise attention_kernel's results)
             MitProbeScope probe("attention_self_kernel", s, 4.0 * heads * head_dim * ((double)R * 2.0 * Tk + 2.0 * (double)R),
                                 4.0 * (double)R * heads * Tk * head_dim);
-            hipLaunchKernelGGL((attention_self_kernel<4, 80>), dim3(R), dim3(256), sm, s, K, k_rs, V, v_rs, Q, q_rs, Tk, dstep, O, o_rs, xp, opl);
+            hipLaunchKernelGGL((attention_self_kernel<4, 80>), dim3(R), dim3(256), sm, s, K, k_rs, V, v_rs, Q, q_rs, Tk, O, o_rs, xp, opl);
             return;
         }
     }
@@ -1760,13 +1693,13 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
     MitProbeScope probe("attention_kernel", s, 4.0 * heads * head_dim * ((double)(R / kv_div) * 2.0 * Tk + 2.0 * (double)R * Tq),
                         4.0 * (double)R * Tq * heads * Tk * head_dim);
     hipLaunchKernelGGL(attention_kernel, dim3(Tq, heads, R), dim3(64), smem, s, Q, q_rs, q_ts, K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs,
-                       o_ts, klen, Tk, kv_div, head_dim, dstep, xp, opl);   // dstep: Tk = the LDS capacity, the kernel attends to *dstep + 1 keys
+                       o_ts, klen, Tk, kv_div, head_dim, xp, opl);
 }
 
 // The decoder's cross-attention with its q projection inside (QF form above).  Returns false — nothing launched — when the problem is
 // not the few-row case the form exists for (the caller then runs the Linear and ocrk_attention).
 bool ocrk_cross_attention_qproj(const OcrAttQProj &qp, const float *K, int64_t k_rs, int64_t k_ts, const float *V, int64_t v_rs, int64_t v_ts,
-                                const int *klen, int R, int Tk, hipStream_t s, const int *dstep, const OcrAttXpos *xpos, const OcrPlanes *o_planes) {
+                                const int *klen, int R, int Tk, hipStream_t s, const OcrAttXpos *xpos, const OcrPlanes *o_planes) {
     constexpr int heads = 4, head_dim = 80, kv_div = 5;
     OcrAttXpos xp{};
     if (xpos) xp = *xpos;
@@ -1779,23 +1712,13 @@ bool ocrk_cross_attention_qproj(const OcrAttQProj &qp, const float *K, int64_t k
     const double bytes = 4.0 * heads * head_dim * ((double)(R / kv_div) * 2.0 * Tk + 2.0 * R), flops = 4.0 * (double)R * heads * Tk * head_dim;
     MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops + 2.0 * R * 320.0 * 320.0);
     hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK_L, ATT_STAGE_L, 80, 5, true>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes, s, nullptr, 0,
-                       K, k_rs, k_ts, V, v_rs, v_ts, nullptr, 0, klen, Tk, dstep, xp, *o_planes, qp);
+                       K, k_rs, k_ts, V, v_rs, v_ts, nullptr, 0, klen, Tk, xp, *o_planes, qp);
     return true;
 }
 
-void ocrk_embed(const int *tok, int64_t tok_stride, const float *E, float *out, int R, int D, hipStream_t s, const int *tok1,
-                const int *dstep) {
-    hipLaunchKernelGGL(embed_kernel, dim3(grid_for((int64_t)R * D / 4, 256)), dim3(256), 0, s, tok, tok_stride, E, out, R, D, tok1, dstep);
+void ocrk_embed(const int *tok, int64_t tok_stride, const float *E, float *out, int R, int D, hipStream_t s) {
+    hipLaunchKernelGGL(embed_kernel, dim3(grid_for((int64_t)R * D / 4, 256)), dim3(256), 0, s, tok, tok_stride, E, out, R, D);
 }
-
-void ocrk_beam_dyn(const float *vals, const int *idx, int *hist0, int *hist1, int hist_ld, float *logp0, float *logp1, int *done,
-                   int *res_row, int *res_len, float *res_prob, int *res_tok, int *done_count, int N, const int *dstep, int start_tok,
-                   int end_tok, int max_finished, hipStream_t s, const float *next_E, float *next_out, int next_D) {
-    hipLaunchKernelGGL(beam_dyn_kernel, dim3(N), dim3(64), 0, s, vals, idx, hist0, hist1, hist_ld, logp0, logp1, done, res_row,
-                       res_len, res_prob, res_tok, done_count, N, dstep, start_tok, end_tok, max_finished, BeamNextEmbed{next_E, next_out, next_D});
-}
-
-void ocrk_step_advance(int *dstep, hipStream_t s) { hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(64), 0, s, dstep); }
 
 void ocrk_logsoftmax_top5(const float *logits, int64_t ld, int R, int D, int suppress_tok, float *vals, int *idx,
                           float *logp_out, hipStream_t s) {

@@ -13,13 +13,10 @@ namespace ocrlin {
 inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 // C[M x N] = act((A[M x K] @ W) * scale + bias) + post, rows of A / C / post strided.
-// dyn / a_dyn / c_dyn: device-resident step counter and the per-step strides of A and C (MitConvGemm.dyn), for the graph-replayed steps.
 inline int gemm(const MitLinear &lin, const float *A, int64_t lda, float *Cp, int64_t ldc, int M, int act, const float *post,
-                int64_t ldpost, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr,
-                int64_t a_dyn = 0, int64_t c_dyn = 0) {
+                int64_t ldpost, hipStream_t s, int nsplit = 0, int64_t nhi = 0) {
     MitConvGemm d;
     memset(&d, 0, sizeof(d));
-    d.dyn = dyn; d.a_dyn = a_dyn; d.c_dyn = c_dyn;
     d.a = A;
     d.a_xs = lda;
     d.NB = 1; d.Hi = 1; d.Wi = M; d.Ho = 1; d.Wo = M; d.sy = 1; d.sx = 1;
@@ -38,11 +35,10 @@ inline int gemm(const MitLinear &lin, const float *A, int64_t lda, float *Cp, in
     return mit_conv_gemm(&d, s);
 }
 
-// The same Linear on planar activations (pgemm_rows.h), one wave per 32 x 32 output block: C fp32 (optional, with the column split / step
-// offset of gemm()) and / or planes.  splitk: the K = 2048 Linear with K cut across four waves.
+// The same Linear on planar activations (pgemm_rows.h), one wave per 32 x 32 output block: C fp32 (optional, with the column split
+// of gemm()) and / or planes.  splitk: the K = 2048 Linear with K cut across four waves.
 inline int pgemm(const MitLinear &lin, const uint16_t *a_planes, int64_t lda, int M, float *Cp, int64_t ldc, int act, const float *post,
-                 int64_t ldpost, uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr,
-                 int64_t c_dyn = 0, int splitk = 0) {
+                 int64_t ldpost, uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0, int splitk = 0) {
     MitPGemm d;
     memset(&d, 0, sizeof(d));
     d.a_planes = a_planes; d.lda = lda;
@@ -54,7 +50,7 @@ inline int pgemm(const MitLinear &lin, const uint16_t *a_planes, int64_t lda, in
     d.nprod = 0;  // the GEMM mode of the moment
     PgRowsExt x;
     memset(&x, 0, sizeof(x));
-    x.nsplit = nsplit; x.nhi = nhi; x.dyn = dyn; x.c_dyn = c_dyn; x.splitk = splitk;
+    x.nsplit = nsplit; x.nhi = nhi; x.splitk = splitk;
     if (Cp) x.also_planes = c_planes, x.also_ld = ld_cp;
     else d.c_planes = c_planes, d.ld_cp = ld_cp;
     return mit_pgemm_rows(d, x, s);
@@ -62,7 +58,7 @@ inline int pgemm(const MitLinear &lin, const uint16_t *a_planes, int64_t lda, in
 
 // The same with A = LayerNorm(x) computed by the GEMM's own waves (pgemm_rows_ln.hip; K == 320): bit for bit ocrk_layernorm + pgemm.
 inline int pgemm_ln(const MitLinear &lin, const float *xin, int64_t ldx, const float *ln_w, const float *ln_b, int M, float *Cp, int64_t ldc, int act,
-                    uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0, const int *dyn = nullptr, int64_t c_dyn = 0) {
+                    uint16_t *c_planes, int64_t ld_cp, hipStream_t s, int nsplit = 0, int64_t nhi = 0) {
     MitPGemm d;
     memset(&d, 0, sizeof(d));
     d.w_planes = lin.w_split; d.ldw = lin.ldw;
@@ -72,7 +68,7 @@ inline int pgemm_ln(const MitLinear &lin, const float *xin, int64_t ldx, const f
     d.nprod = 0;
     PgRowsExt x;
     memset(&x, 0, sizeof(x));
-    x.nsplit = nsplit; x.nhi = nhi; x.dyn = dyn; x.c_dyn = c_dyn;
+    x.nsplit = nsplit; x.nhi = nhi;
     if (Cp) x.also_planes = c_planes, x.also_ld = ld_cp;
     else d.c_planes = c_planes, d.ld_cp = ld_cp;
     const PgRowsLn ln{xin, ldx, ln_w, ln_b, 1e-5f};

@@ -574,7 +574,7 @@ __global__ __launch_bounds__(256) void join_planes_kernel(const u32x4 *__restric
 // holds whole cells (eight consecutive columns of one row): 16-byte fp32 stores and / or a split into planes.  Per element the pair
 // order, the k order and the epilogue arithmetic of the other tiles: bit-identical results.
 // Decoder extras (PgRowsExt; zero-initialised = none): the three-way column split of the q | k | v projection (MitTensorMap::nsplit),
-// the device-resident step counter (the output row of the step), both output kinds at once.
+// both output kinds at once.
 
 // KTS: K / 16 as a compile-time constant (the decoder's K = 320 and 2048): the k loop fully unrolled, so that hipcc counts the loads in
 // flight exactly — at the header of a run-time loop it waits for vmcnt(0), which empties the prefetch ring once per D steps (KTS = 0).
@@ -823,7 +823,7 @@ int mit_pgemm_rows(const MitPGemm &d, const PgRowsExt &x, hipStream_t s) {
     uint16_t *planes = p.c_planes ? p.c_planes : x.also_planes;
     if (!p.c && !planes) return mit_set_error("mit_pgemm_rows: no output");
     if (p.c_planes && x.also_planes) return mit_set_error("mit_pgemm_rows: two planar outputs");
-    if ((p.N & 3) || (planes && (p.N & 7)) || (p.c && (p.ldc & 3)) || (x.nsplit & 7) || (x.nhi & 3) || (x.c_dyn & 3) || (p.post && (p.ld_post & 3)) || (p.pre && (p.ld_pre & 3)))
+    if ((p.N & 3) || (planes && (p.N & 7)) || (p.c && (p.ldc & 3)) || (x.nsplit & 7) || (x.nhi & 3) || (p.post && (p.ld_post & 3)) || (p.pre && (p.ld_pre & 3)))
         return mit_set_error("mit_pgemm_rows: N / strides must keep 16-byte cells whole");
     // the operand part of pg_check: the kernel addresses the three planes through 32-bit buffer offsets and moves 16-byte pieces
     if ((int64_t)3 * (p.K >> 3) * p.lda * 16 > 0xffffffffLL || (int64_t)3 * (p.K >> 3) * p.ldw * 16 > 0xffffffffLL)

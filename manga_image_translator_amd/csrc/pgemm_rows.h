@@ -8,8 +8,6 @@
 struct PgRowsExt {
     int nsplit;             // != 0 (multiple of 8): output column n lives at (n / nsplit) * nhi + n % nsplit (the q | k | v projection)
     int64_t nhi;
-    const int *dyn;         // device step counter: the fp32 output starts *dyn * c_dyn floats further
-    int64_t c_dyn;
     uint16_t *also_planes;  // planar copy of the result beside the fp32 output (N % 8 == 0)
     int64_t also_ld;
     int splitk;             // != 0 and K == 2048: four waves sum a quarter of K each (fixed order; not the k-sequential rounding)

@@ -24,7 +24,7 @@ __device__ __forceinline__ void pg_rows_epilogue(const MitPGemm &p, const PgRows
     const int m = m0 + li;
     const int act = p.act & 0xff;
     const bool post_first = (p.act & MIT_ACT_POST_FIRST) != 0;
-    float *cbase = p.c ? p.c + (int64_t)z * p.c_zs + (x.dyn ? (int64_t)(*x.dyn) * x.c_dyn : 0) : nullptr;
+    float *cbase = p.c ? p.c + (int64_t)z * p.c_zs : nullptr;
     u32x4 *pl_out = p.c_planes ? reinterpret_cast<u32x4 *>(p.c_planes + (int64_t)z * p.cp_zs) : reinterpret_cast<u32x4 *>(x.also_planes);
     const int64_t pl_ld = p.c_planes ? p.ld_cp : x.also_ld;
     const int64_t pl_plane = (int64_t)(p.N >> 3) * pl_ld;

@@ -127,7 +127,7 @@ int mit_pgemm_rows_ln(const MitPGemm &d, const PgRowsExt &x, const PgRowsLn &ln,
     uint16_t *planes = p.c_planes ? p.c_planes : x.also_planes;
     if (!p.c && !planes) return mit_set_error("mit_pgemm_rows_ln: no output");
     if (p.c_planes && x.also_planes) return mit_set_error("mit_pgemm_rows_ln: two planar outputs");
-    if ((p.N & 3) || (planes && (p.N & 7)) || (p.ldc & 3) || (p.ld_post & 3) || (ln.ldx & 3) || (x.nsplit & 7) || (x.nhi & 3) || (x.c_dyn & 3))
+    if ((p.N & 3) || (planes && (p.N & 7)) || (p.ldc & 3) || (p.ld_post & 3) || (ln.ldx & 3) || (x.nsplit & 7) || (x.nhi & 3))
         return mit_set_error("mit_pgemm_rows_ln: N / strides must keep 16-byte cells whole");
     if ((uint64_t)3 * (LN_K / 8) * (uint64_t)p.ldw * 16u >= (1ull << 32)) return mit_set_error("mit_pgemm_rows_ln: W planes exceed 4 GB");
     auto al16 = [](const void *q) { return ((uintptr_t)q & 15) == 0; };

@@ -69,9 +69,6 @@ def _refused():
     d = desc(**{**base, "Cin": 4})  # the row-lookup epilogue on a launch that takes the generic kernel
     d.lut_rows, d.lut1, d.lut2, d.lut_ld = 4096, 4096, 4096, 64
     out.append((d, -1))
-    d = desc(**{**base, "Cin": 64, "N": 4})  # the device-side step offset on the N <= 4 kernel
-    d.dyn = 4096
-    out.append((d, -1))
     return out
 
 

@@ -333,36 +333,10 @@ def test_dwconv_ragged_rows_equals_per_row_kernel(cuda, k, C_, H, shapes):
 
 
 @pytest.mark.parametrize("widths,T,suppress", [([50, 77, 120, 121, 64, 200], 14, True), ([90, 33], 9, False), ([40 + 5 * i for i in range(40)], 6, True)])
-def test_graph_replayed_decode_is_bit_identical(cuda, ocr_setup, widths, T, suppress):
-    """mit_ocr48_decode with its steps replayed from a hipGraph (every step-dependent argument read from a device-resident counter)
-    against the classic launch-by-launch loop: the same kernels on the same operands, so every result tensor must be identical —
-    with EOS suppressed and with the early-exit polling, for one chunk and for a pooled decode of 40 lines."""
-    sd, D, eng = ocr_setup
-    crops = _crops(widths, seed=11)
-    mks, mvs, lens = [], [], []
-    for indices, ws, region in eng.make_chunks(crops):
-        mk, mv, kl, L = eng.encode(torch.from_numpy(region).to(cuda), ws)
-        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
-    Lmax = max(m.shape[2] for m in mks)
-    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
-    mem_k, mem_v, klen = torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
-    outs = []
-    for graph in (False, True, True):
-        o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, graph=graph)
-        torch.cuda.synchronize()
-        outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
-    for o in outs[1:]:
-        assert o["steps_run"] == outs[0]["steps_run"]
-        for k in ("tokens", "length", "prob", "colors"):
-            assert torch.equal(o[k], outs[0][k]), k
-
-
-@pytest.mark.parametrize("widths,T,suppress", [([50, 77, 120, 121, 64, 200], 14, True), ([90, 33], 9, False), ([40 + 5 * i for i in range(40)], 6, True)])
 def test_few_row_decode_equals_the_tiled_form(cuda, ocr_setup, widths, T, suppress):
     """The few-row form of a decode step (mit_ocr48_decode_rows_max_set: every Linear one wave per 32 x 32 block on bf16-plane
     activations, LayerNorm / attention kernels producing the planes) against the tiled form the full batches take: the plane split,
-    the MFMA pair order and the epilogue arithmetic are the same, so tokens, lengths, probabilities and colours must be identical —
-    launch by launch and replayed from a graph."""
+    the MFMA pair order and the epilogue arithmetic are the same, so tokens, lengths, probabilities and colours must be identical."""
     from manga_image_translator_amd import lib as L
 
     sd, D, eng = ocr_setup
@@ -382,9 +356,9 @@ def test_few_row_decode_equals_the_tiled_form(cuda, ocr_setup, widths, T, suppre
     prev_sk = os.environ.get("MIT_OCR_FF2_SPLITK")
     os.environ["MIT_OCR_FF2_SPLITK"] = "0"   # the one-chain FFN kernel: the k-sequential sum of the tiles (the K-cut form has its own test)
     try:
-        for rows_max, graph in ((0, False), (prev, False), (prev, True)):
+        for rows_max in (0, prev):
             lib.mit_ocr48_decode_rows_max_set(rows_max)
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, graph=graph)
+            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
             torch.cuda.synchronize()
             outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
     finally:
@@ -513,7 +487,7 @@ def test_register_form_of_logsoftmax_top5_is_bitwise_the_loop_form(cuda, R, D, s
 def test_layernorm_inside_the_few_row_gemm_is_bit_identical(cuda, ocr_setup, widths, T, suppress):
     """pgemm_rows_ln_kernel (the decoder's norm1 / norm2 / norm3 computed by the waves of the Linear that consumes them, same butterfly
     as layernorm_kernel) against the two-launch form (MIT_OCR_LN_FUSED=0) and against the tiled form of full batches: every result
-    tensor identical, launch by launch and replayed from a graph; 6, 2 and 40 lines = 30, 10 and 200 rows (ragged last row block)."""
+    tensor identical; 6, 2 and 40 lines = 30, 10 and 200 rows (ragged last row block)."""
     import os
     from manga_image_translator_amd import lib as L
 
@@ -533,10 +507,10 @@ def test_layernorm_inside_the_few_row_gemm_is_bit_identical(cuda, ocr_setup, wid
     os.environ["MIT_OCR_FF2_SPLITK"] = "0"
     outs = []
     try:
-        for fused, rows_max, graph in (("0", prev_rows, False), ("1", prev_rows, False), ("1", prev_rows, True), ("1", 0, False)):
+        for fused, rows_max in (("0", prev_rows), ("1", prev_rows), ("1", 0)):
             os.environ["MIT_OCR_LN_FUSED"] = fused
             lib.mit_ocr48_decode_rows_max_set(rows_max)
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, graph=graph)
+            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
             torch.cuda.synchronize()
             outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
     finally:
@@ -592,7 +566,7 @@ def test_k_cut_ffn_linear_of_the_few_row_decode(cuda, ocr_setup, widths, T, supp
 def test_q_projection_inside_the_cross_attention_is_bit_identical(cuda, ocr_setup, widths, T, suppress):
     """attention_shared_kv_kernel<..., QF> (norm2 and multihead_attn's q projection computed inside the decoder's cross-attention kernel:
     one wave normalises the line's five beams with layernorm_kernel's butterfly, three waves run pgemm_rows_kernel's K loop on the head's
-    columns) against the separate launches (MIT_OCR_Q2_FUSED=0): every result tensor identical, launch by launch and from a graph."""
+    columns) against the separate launches (MIT_OCR_Q2_FUSED=0): every result tensor identical."""
     import os
 
     sd, D, eng = ocr_setup
@@ -607,9 +581,9 @@ def test_q_projection_inside_the_cross_attention_is_bit_identical(cuda, ocr_setu
     prev = os.environ.get("MIT_OCR_Q2_FUSED")
     outs = []
     try:
-        for q2, graph in (("0", False), ("1", False), ("1", True)):
+        for q2 in ("0", "1"):
             os.environ["MIT_OCR_Q2_FUSED"] = q2
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, graph=graph)
+            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
             torch.cuda.synchronize()
             outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
     finally:
