@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 20
+#define MIT_ABI_VERSION 21
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -127,7 +127,20 @@ typedef struct MitConvGemm {
      * mit_conv_gemm_cfg runs with nprod = 0 as well, like the test-only 3-pair tile: the tile decides; nprod = 1 with a tile that
      * is not a p1 tile is refused.) */
     int32_t nprod;
-    int32_t _pad1;
+    /* optional: compute only a device-side list of live 8 x 8 blocks of the (nb, oy, ox) output grid (LaMa's decoder tail, whose result
+     * is read only under the mask).  An image has ceil(Ho / 8) * ceil(Wo / 8) blocks in raster order (edge blocks are clipped); block
+     * b of image i has the id i * blocks_per_image + b.  live_blocks holds the ids of the live blocks of the whole batch, ascending;
+     * live_start[i] is the index in live_blocks of image i's first entry and live_start[NB] the total (NB + 1 entries, live_start[0]
+     * need not be 0).  Row r of the launch is then position r & 63 (row-major in the block) of block live_blocks[live_start[0] + (r >> 6)];
+     * rows past 64 * (live_start[NB] - live_start[0]) and positions of an edge block outside Ho x Wo are dead rows: gathered as zeros
+     * and never stored, like the rows m >= M of a dense launch.  The host launches the dense grid and reads nothing back: a workgroup
+     * loads the count and returns when its tile lies past the live tiles (the XCD-contiguous tile order is formed over the live tiles).
+     * A batch that is cut into runs of whole images moves live_start and live_img0 (the batch index of the run's first image) along
+     * with the operands, so every run finds its own segment.  Live rows get the bits of the dense launch.  NULL = the dense launch,
+     * unchanged.  Implemented by the fast (fp32 MFMA) and split tiles for Z == 1 without lut_rows; any other tile refuses it. */
+    int32_t live_img0;
+    const int32_t *live_blocks;
+    const int32_t *live_start;
 } MitConvGemm;
 
 const char *mit_last_error(void);
@@ -247,10 +260,27 @@ int mit_join_planes(const uint16_t *planes_dev, int64_t ld, int R, int K, float 
  * goes global -> LDS by global_load_lds_dwordx4 (no staging registers, 4 workgroups per CU; reflect padding only); a NEGATIVE
  * in_planestride (-stride) says every plane stores its images parity-major, [2 (y & 1)][2 (x & 1)][H / 2][W / 2][4] — the layout in
  * which the stride-2 transposed convolution that produces them writes consecutive pixels per launch.  Same bits in every layout.
+ * live_cells (optional, device): a byte per 8-row x 32-column cell of the output, [B][ceil(H / 8)][ceil(W / 32)].  A workgroup whose tile
+ * (16 x 64 in the packed kernels, 8 x 32 in the plain one) covers only zero cells issues no load or LDS-DMA request and stores nothing;
+ * every other tile computes what it computes without the map.  NULL = every tile.
  * Replaces ReflectionPad2d(3) + Conv2d(64, 3, 7) + sigmoid at the end of FFCResNetGenerator (inpainting_lama_mpe.py:597-600). */
 int mit_conv_small_cout(const float *in_dev, int64_t in_pixstride, int64_t in_planestride, const float *w4_dev, const float *w_pairs_dev, const float *bias_dev, float *out_dev,
                         int64_t out_pixstride, int B, int H, int W, int Cin, int Cout, int k, int pad_mode, int act,
-                        float act_alpha, void *stream);
+                        float act_alpha, const uint8_t *live_cells, void *stream);
+
+/* Which parts of LaMa's decoder tail a composite reads (lama_post takes the prediction only where mask >= 127): from mask [B][H][W] u8
+ * (H, W multiples of 8), on `stream`, with no allocation, synchronisation or copy to the host,
+ *   cells                the live-cell map of mit_conv_small_cout, [B][H / 8][ceil(W / 32)] bytes;
+ *   listL / startL       the live-block list of the L-th transposed convolution (L = 0: output H/4, 1: H/2, 2: H) as MitConvGemm takes
+ *                        it (live_blocks / live_start) for that layer's parity sub-grid [B][H >> (3 - L)][W >> (3 - L)] — one list for
+ *                        its four parity launches; listL holds up to B * ceil(h / 8) * ceil(w / 8) ids, startL B + 1 entries.
+ * A block is live when one of its positions has an output, in one of the 2 x 2 parities, that a needed position of the next layer reads:
+ * need(H) = dilate(mask >= 127, 3) for the 7x7 window; need(input) = dilate(pool2x2_any(need(output)), 1) per transposed convolution
+ * (k3 s2 p1 op1: input i feeds outputs 2i-1, 2i, 2i+1).  Lists are in block-raster order, image after image.
+ * work: mit_lama_tail_need_work(B, H, W) bytes of scratch, 16-byte aligned.  Nothing in the reference corresponds to it. */
+int64_t mit_lama_tail_need_work(int B, int H, int W);
+int mit_lama_tail_need(const uint8_t *mask_dev, int B, int H, int W, uint8_t *cells_dev, int32_t *list0_dev, int32_t *start0_dev, int32_t *list1_dev,
+                       int32_t *start1_dev, int32_t *list2_dev, int32_t *start2_dev, uint8_t *work_dev, void *stream);
 
 /* The ConvNeXt block's pointwise pair as ONE launch (round 5): out = post + scale2 * (W2 . gelu(W1 . x + b1)) + bias2 per row, i.e.
  * pwconv1 -> GELU -> pwconv2 -> gamma -> + input of ConvNeXtBlock.forward (manga_translator/ocr/model_48px.py:203-214), in the

@@ -242,6 +242,11 @@ bool vec_epilogue_ok(const MitConvGemm &p) {
     return !(reinterpret_cast<uintptr_t>(p.scale) & 15) && !(reinterpret_cast<uintptr_t>(p.bias) & 15);
 }
 
+// rows of a launch that carries a live-block list: every 8 x 8 block of every image whole (edge blocks are clipped in the kernel), so
+// that the dense grid covers the case "every block live"
+int64_t list_rows(const MitConvGemm &p) { return (int64_t)p.NB * ((p.Ho + 7) / 8) * ((p.Wo + 7) / 8) * 64; }
+int64_t rows_of(const MitConvGemm &p) { return p.live_blocks ? list_rows(p) : (int64_t)p.NB * p.Ho * p.Wo; }
+
 // ---- validate -> plan -> launch ----
 // stage 1: the descriptor by itself, whatever tile it takes.  p = *d with MIT_ACT_VEC_OK set where the float4 epilogue applies.
 int validate(const MitConvGemm *d, MitConvGemm &p) {
@@ -273,6 +278,16 @@ int validate(const MitConvGemm *d, MitConvGemm &p) {
         if (!p.lut1 || !p.lut2 || p.lut_ld < p.N) return mit_set_error("mit_conv_gemm: lut_rows needs lut1, lut2 and lut_ld >= N");
         if (p.Z != 1) return mit_set_error("mit_conv_gemm: the row-lookup epilogue is for Z == 1 launches");
         if (p.lut_ld > 0x7fff) return mit_set_error("mit_conv_gemm: lut_ld too large (row offsets are 16-bit row x lut_ld in 32 bits)");
+    }
+    if (p.live_blocks || p.live_start) {  // the live-block list: both arrays, one slice, rows decoded per block (no per-row table)
+        if (!p.live_blocks || !p.live_start) return mit_set_error("mit_conv_gemm: a live-block list needs live_blocks and live_start");
+        if ((reinterpret_cast<uintptr_t>(p.live_blocks) | reinterpret_cast<uintptr_t>(p.live_start)) & 3) return mit_set_error("mit_conv_gemm: live_blocks / live_start must be 4-byte aligned");
+        if (p.Z != 1) return mit_set_error("mit_conv_gemm: a live-block list is for Z == 1 launches");
+        if (p.lut_rows) return mit_set_error("mit_conv_gemm: a live-block list together with lut_rows is not implemented");
+        if (p.live_img0 < 0) return mit_set_error("mit_conv_gemm: live_img0 must be >= 0 (got %d)", p.live_img0);
+        if (list_rows(p) > 0x7fffffffLL) return mit_set_error("mit_conv_gemm: M too large");
+    } else if (p.live_img0 != 0) {
+        return mit_set_error("mit_conv_gemm: live_img0 without a live-block list");
     }
     if (p.Z > 65535) return mit_set_error("mit_conv_gemm: Z too large");
     if (p.nprod != 0 && p.nprod != 1) return mit_set_error("mit_conv_gemm: nprod must be 0 (the GEMM mode) or 1 (one bf16 product) (got %d)", p.nprod);
@@ -309,12 +324,13 @@ MitConvGemm run_of(const MitConvGemm &p, int b0, int nb) {
     if (p.pre.base) r.pre.base += (int64_t)b0 * p.pre.bs;
     if (p.post.base) r.post.base += (int64_t)b0 * p.post.bs;
     if (p.lut_rows) r.lut_rows += (int64_t)b0 * p.Ho * p.Wo;
+    if (p.live_blocks) r.live_start += b0, r.live_img0 += b0;  // the run's segment of the list: [live_start[b0], live_start[b0 + nb])
     return r;
 }
 
 // stage 2b: the tile of one run (cfg < 0: the automatic choice) and what that tile refuses
 int plan_run(const MitConvGemm &p, int cfg, int *tile) {
-    const int64_t M = (int64_t)p.NB * p.Ho * p.Wo;
+    const int64_t M = rows_of(p);
     if (p.nprod == 1) {  // (per run: a batch past 2^31 elements is eligible run by run)
         if (!split_eligible(p, 16))
             return mit_set_error("mit_conv_gemm: nprod = 1 needs the split tiles' preconditions (Cin %% 16 == 0, <= %d taps, 32-bit element offsets, 16-byte aligned w_split with w_zs1 == 0 and Kw %% 8 == 0): there is no fp32 fallback for a requested precision", FAST_MAX_TAPS);
@@ -331,6 +347,8 @@ int plan_run(const MitConvGemm &p, int cfg, int *tile) {
         if (p.post.base) return mit_set_error("mit_conv_gemm: lut_rows together with a post residual is not implemented");
         if ((p.act & 0xff) != MIT_ACT_NONE && (p.act & 0xff) != MIT_ACT_RELU) return mit_set_error("mit_conv_gemm: lut_rows is implemented for act none / relu");
     }
+    if (p.live_blocks && !fast && !split)  // no dense fallback: the caller's dead positions hold no defined value
+        return mit_set_error("mit_conv_gemm: a live-block list needs a fast or split tile (Cin %% 16 == 0, <= %d taps, N > 4); this launch takes %s", FAST_MAX_TAPS, c.name);
     if (gemv && (!gemv_eligible(p, c.lanes_per_row()) || p.N > c.BN))
         return mit_set_error("mit_conv_gemm: cfg %s needs N <= %d, Z == 1, unsplit maps and Cin %% %d == 0", c.name, c.BN, 4 * c.lanes_per_row());
     if (split && !split_eligible(p, c.BK))
@@ -345,7 +363,7 @@ int plan_run(const MitConvGemm &p, int cfg, int *tile) {
 // stage 3: one planned run, inside the probe while it is enabled
 int launch_run(const MitConvGemm &p, int cfg, hipStream_t hs) {
     const CfgEntry &c = kCfgs[cfg];
-    const int M = p.NB * p.Ho * p.Wo;
+    const int M = (int)rows_of(p);
     const int MT = (M + c.BM - 1) / c.BM;
     const int NT = (p.N + c.BN - 1) / c.BN;
     const int Ktot = p.ntaps * p.Cin;
@@ -364,6 +382,15 @@ int launch_run(const MitConvGemm &p, int cfg, hipStream_t hs) {
         MIT_CHECK_HIP(hipEventRecord(r.start, hs));
         c.launch(p, M, MT, NT, KT, hs);
         MIT_CHECK_HIP(hipEventRecord(r.stop, hs));
+        if (p.live_blocks) {  // credit the live rows, not M: the count is read back behind the launch (probe only — a synchronising copy)
+            int32_t s0 = 0, s1 = 0;
+            MIT_CHECK_HIP(hipEventSynchronize(r.stop));
+            MIT_CHECK_HIP(hipMemcpy(&s0, p.live_start, sizeof(s0), hipMemcpyDeviceToHost));
+            MIT_CHECK_HIP(hipMemcpy(&s1, p.live_start + p.NB, sizeof(s1), hipMemcpyDeviceToHost));
+            r.M = (s1 - s0) * 64;
+            r.exec_flops = 2.0 * (double)r.M * p.N * Ktot * p.Z;
+            r.alg_flops = r.exec_flops;
+        }
         g_probe.push_back(r);
     } else {
         c.launch(p, M, MT, NT, KT, hs);

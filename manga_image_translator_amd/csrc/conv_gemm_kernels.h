@@ -72,6 +72,40 @@ __device__ __forceinline__ float apply_act(float v, float alpha) {
     return v;
 }
 
+// ---- output row m -> (nb, oy, ox): the one decode behind every gather table and the epilogue's RowOff -------------------------
+// Dense launch: m = (nb * Ho + oy) * Wo + ox; rows m >= M are dead.  With MitConvGemm.live_blocks the rows are those of the listed
+// 8 x 8 blocks: row m is position m & 63 (row-major) of the (m >> 6)-th live block of this run; rows past the live blocks and positions
+// of a clipped edge block outside Ho x Wo are dead.  A dead row gathers zeros and stores nothing.  Called outside the K loops only.
+__device__ __forceinline__ bool decode_row(const MitConvGemm &p, const int m, const int M, const int HoWo, int &nb, int &oy, int &ox) {
+    if (p.live_blocks == nullptr) {
+        if (m >= M) return false;
+        nb = m / HoWo;
+        const int rem = m - nb * HoWo;
+        oy = rem / p.Wo;
+        ox = rem - oy * p.Wo;
+        return true;
+    }
+    const int s0 = p.live_start[0];
+    const int blk = m >> 6;
+    if (m >= M || blk >= p.live_start[p.NB] - s0) return false;
+    const int bw = (p.Wo + 7) >> 3, bpi = ((p.Ho + 7) >> 3) * bw;
+    const int id = p.live_blocks[s0 + blk] - p.live_img0 * bpi;  // block index inside this run
+    nb = id / bpi;
+    const int rem = id - nb * bpi;
+    const int by = rem / bw;
+    oy = by * 8 + ((m & 63) >> 3);
+    ox = (rem - by * bw) * 8 + (m & 7);
+    return oy < p.Ho && ox < p.Wo;
+}
+// workgroups of a launch: MT * NT, or with a live-block list the tiles that hold live rows — the caller returns when blockIdx.x is
+// past them and forms its XCD-contiguous tile order over this count, so the live tiles spread over all XCDs
+template <int BM>
+__device__ __forceinline__ int live_workgroups(const MitConvGemm &p, const int MT, const int NT) {
+    if (p.live_blocks == nullptr) return MT * NT;
+    const int live = p.live_start[p.NB] - p.live_start[0];  // wave-uniform: scalar loads
+    return ((live * 64 + BM - 1) / BM) * NT;
+}
+
 // ---- epilogue shared by both kernels: row offsets computed once per row, shared through LDS ----
 // The activation (and whether a residual joins) is a compile-time parameter of the store loop and dispatched once per
 // wave: a per-element switch costs more than the stores on the small-K layers.
@@ -181,11 +215,8 @@ __device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM]
     for (int r = tid; r < BM; r += NTHR) {
         const int m = m0 + r;
         RowOff ro = {-1, 0, 0};
-        if (m < M) {
-            const int nb = m / HoWo;
-            const int rem = m - nb * HoWo;
-            const int oy = rem / p.Wo;
-            const int ox = rem - oy * p.Wo;
+        int nb, oy, ox;
+        if (decode_row(p, m, M, HoWo, nb, oy, ox)) {
             ro.c = z1 * p.c.zs1 + z0 * p.c.zs0 + (int64_t)nb * p.c.bs + (int64_t)oy * p.c.ys + (int64_t)ox * p.c.xs;
             ro.pre = z1 * p.pre.zs1 + z0 * p.pre.zs0 + (int64_t)nb * p.pre.bs + (int64_t)oy * p.pre.ys +
                      (int64_t)ox * p.pre.xs;
@@ -297,11 +328,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, con
 #pragma unroll
     for (int i = 0; i < A_ITERS; ++i) {
         const int m = m0 + am + i * A_MSTEP;
-        if (m < M) {
-            const int nb = m / HoWo;
-            const int rem = m - nb * HoWo;
-            const int oy = rem / p.Wo;
-            const int ox = rem - oy * p.Wo;
+        int nb, oy, ox;
+        if (decode_row(p, m, M, HoWo, nb, oy, ox)) {
             a_rowbase[i] = (int64_t)nb * p.a_bs;
             a_iy0[i] = oy * p.sy;
             a_ix0[i] = ox * p.sx;
@@ -468,8 +496,9 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     const int li = lane & 31;
     const int lh = lane >> 5;
 
-    const int nwg = MT * NT;
+    const int nwg = live_workgroups<BM>(p, MT, NT);
     int bid = blockIdx.x;
+    if (bid >= nwg) return;  // (only with a live-block list: the tiles past the live rows)
     {
         const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
@@ -488,11 +517,8 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
         const int t = idx / BM, r = idx - t * BM;
         const int m = m0 + r;
         int off = -1;
-        if (m < M) {
-            const int nb = m / HoWo;
-            const int rem = m - nb * HoWo;
-            const int oy = rem / p.Wo;
-            const int ox = rem - oy * p.Wo;
+        int nb, oy, ox;
+        if (decode_row(p, m, M, HoWo, nb, oy, ox)) {
             int iy = oy * p.sy + p.tap_dy[t];
             int ix = ox * p.sx + p.tap_dx[t];
             bool ok = true;

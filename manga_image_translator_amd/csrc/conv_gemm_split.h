@@ -87,7 +87,8 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     const int li = lane & 31;
     const int lh = lane >> 5;
 
-    const int nwg = MT * NT;
+    const int nwg = live_workgroups<BM>(p, MT, NT);
+    if ((int)blockIdx.x >= nwg) return;  // (only with a live-block list: the tiles past the live rows)
     int cur_tile;  // block id -> position in the XCD-contiguous order: consecutive tiles (n fastest) share the A panel
     {
         const int v = blockIdx.x, xcd = v & 7, q = nwg >> 3, r = nwg & 7;
@@ -128,11 +129,8 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
             const int tp = idx / BM, r = idx - tp * BM;
             const int m = m0 + r;
             int off = -1;
-            if (m < M) {
-                const int nb = m / HoWo;
-                const int rem = m - nb * HoWo;
-                const int oy = rem / p.Wo;
-                const int ox = rem - oy * p.Wo;
+            int nb, oy, ox;
+            if (decode_row(p, m, M, HoWo, nb, oy, ox)) {
                 int iy = oy * p.sy + p.tap_dy[tp];
                 int ix = ox * p.sx + p.tap_dx[tp];
                 bool ok = true;

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <vector>
 #include "../../include/mit_hip.h"
 #include "common.h"
 
@@ -43,19 +44,37 @@ __device__ __forceinline__ float act_fn(float v, int act, float alpha) {
     }
 }
 
+// The optional live-cell map (a byte per 8-row x 32-column cell of the output, [B][ceil(H / 8)][ceil(W / 32)]): does the TH_ x TW_ tile
+// at (y0, x0) of image b cover a non-zero cell?  Workgroup-uniform (scalar loads); a dead tile returns before its first load.
+template <int TH_, int TW_>
+__device__ __forceinline__ bool tile_live(const uint8_t *__restrict__ cells, const int b, const int y0, const int x0, const int H, const int W) {
+    if (cells == nullptr) return true;
+    const int ch = (H + 7) >> 3, cw = (W + 31) >> 5, cy0 = y0 >> 3, cx0 = x0 >> 5;
+    bool live = false;
+#pragma unroll
+    for (int dy = 0; dy < TH_ / 8; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < TW_ / 32; ++dx)
+            if (cy0 + dy < ch && cx0 + dx < cw) live = live || cells[((int64_t)b * ch + cy0 + dy) * cw + cx0 + dx] != 0;
+    return live;
+}
+
 template <int K>
 __global__ __launch_bounds__(256) void conv_small_cout_kernel(const float *__restrict__ in, int64_t in_pix, const f32x4 *__restrict__ w4,
                                                                const float *__restrict__ bias, float *__restrict__ out,
                                                                int64_t out_pix, int H, int W, int Cin, int Cout, int reflect,
-                                                               int act, float alpha) {
+                                                               int act, float alpha, const uint8_t *__restrict__ cells) {
     constexpr int R = K / 2;
     constexpr int HW_ = TW + 2 * R, HH_ = TH + 2 * R;
     __shared__ f32x4 tile[CCH / 4][HH_][HW_];
     const int tx = threadIdx.x & (TW - 1), ty = threadIdx.x / TW;
     const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH, b = blockIdx.z;
+    // a dead tile runs no channel slice (no load, no barrier) and stores nothing; as a loop bound rather than an early return, which
+    // cost the K = 5 form an SGPR spill slot in scratch memory
+    const bool live = tile_live<TH, TW>(cells, b, y0, x0, H, W);
     const float *ib = in + (int64_t)b * H * W * in_pix;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int c0 = 0; c0 < Cin; c0 += CCH) {
+    for (int c0 = 0; c0 < (live ? Cin : 0); c0 += CCH) {
         __syncthreads();
         for (int i = threadIdx.x; i < (CCH / 4) * HH_ * HW_; i += 256) {
             const int q = i % (CCH / 4);
@@ -96,9 +115,11 @@ __global__ __launch_bounds__(256) void conv_small_cout_kernel(const float *__res
         }
     }
     const int x = x0 + tx, y = y0 + ty;
-    if (x < W && y < H) {
+    if (x < W && y < H && live) {
         float *o = out + (((int64_t)b * H + y) * W + x) * out_pix;
-        for (int n = 0; n < Cout; ++n) o[n] = act_fn(acc[n] + (bias ? bias[n] : 0.f), act, alpha);
+#pragma unroll
+        for (int n = 0; n < 4; ++n)  // (constant indices into acc: a run-time one sent the accumulator through scratch memory)
+            if (n < Cout) o[n] = act_fn(acc[n] + (bias ? bias[n] : 0.f), act, alpha);
     }
 }
 
@@ -111,7 +132,7 @@ __global__ __launch_bounds__(256) void conv_small_cout3_kernel(const float *__re
                                                                 const f32x2 *__restrict__ wq /* [taps][Cin / 4][4 out (3 used)][2 channel pairs] */,
                                                                 const float *__restrict__ bias, float *__restrict__ out,
                                                                 int64_t out_pix, int H, int W, int Cin, int Cout, int reflect,
-                                                                int act, float alpha) {
+                                                                int act, float alpha, const uint8_t *__restrict__ cells) {
     // Packed operands are CHANNEL pairs: an accumulator pair holds (sum over even channels, sum over odd channels) of one output, a
     // pixel's channels (c, c + 1) are adjacent in the NHWC input and so are a kernel tap's weights for them in wq — every operand of
     // every v_pk_fma_f32 is a naturally aligned register pair (VGPR pair from one ds_read_b128, SGPR pair from one scalar load), no
@@ -123,6 +144,7 @@ __global__ __launch_bounds__(256) void conv_small_cout3_kernel(const float *__re
     __shared__ f32x4 tile[TR][HW_];      // [row][even pixels | odd pixels] = the 4 channels of the current slice
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int x0 = blockIdx.x * TW3, y0 = blockIdx.y * TH3, b = blockIdx.z;
+    if (!tile_live<TH3, TW3>(cells, b, y0, x0, H, W)) return;
     const float *ib = in + (int64_t)b * H * W * in_pix;
     f32x2 acc[2][2][3];                  // [row r: y, y + 8][column j: x, x + 1][output channel]
 #pragma unroll
@@ -222,7 +244,8 @@ typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 template <int K>
 __global__ __launch_bounds__(256, 4) void conv_small_cout3_dma_kernel(const float *__restrict__ in, int64_t in_plane /* floats between 4-channel planes */,
                                                                       const f32x2 *__restrict__ wq, const float *__restrict__ bias, float *__restrict__ out,
-                                                                      int64_t out_pix, int H, int W, int Cin, int Cout, int act, float alpha, int parity_major) {
+                                                                      int64_t out_pix, int H, int W, int Cin, int Cout, int act, float alpha, int parity_major,
+                                                                      const uint8_t *__restrict__ cells) {
     constexpr int R = K / 2;
     constexpr int TR = TH3 + 2 * R, HW_ = TW3 + 2 * R, HALF = HW_ / 2;
     constexpr int CELLS = TR * HW_, PIECES = (CELLS + 63) / 64, PPW = (PIECES + 3) / 4, BUF_CELLS = PPW * 4 * 64;
@@ -230,6 +253,7 @@ __global__ __launch_bounds__(256, 4) void conv_small_cout3_dma_kernel(const floa
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x0 = blockIdx.x * TW3, y0 = blockIdx.y * TH3, b = blockIdx.z;
+    if (!tile_live<TH3, TW3>(cells, b, y0, x0, H, W)) return;
     int src_off[PPW];  // this lane's source pixel of each of its wave's pieces (floats into a plane's image of batch entry b)
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
@@ -305,7 +329,7 @@ __global__ __launch_bounds__(256, 4) void conv_small_cout3_dma_kernel(const floa
 
 extern "C" int mit_conv_small_cout(const float *in_dev, int64_t in_pixstride, int64_t in_planestride, const float *w4_dev, const float *w_pairs_dev, const float *bias_dev,
                                    float *out_dev, int64_t out_pixstride, int B, int H, int W, int Cin, int Cout, int k,
-                                   int pad_mode, int act, float act_alpha, void *stream) {
+                                   int pad_mode, int act, float act_alpha, const uint8_t *live_cells, void *stream) {
     if (!in_dev || !w4_dev || !out_dev) return mit_set_error("mit_conv_small_cout: null pointer");
     if (Cout < 1 || Cout > 4) return mit_set_error("mit_conv_small_cout: 1 <= Cout <= 4 required (got %d)", Cout);
     if (Cin <= 0 || (Cin % CCH)) return mit_set_error("mit_conv_small_cout: Cin must be a multiple of %d (got %d)", CCH, Cin);
@@ -325,9 +349,28 @@ extern "C" int mit_conv_small_cout(const float *in_dev, int64_t in_pixstride, in
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const f32x4 *w4 = reinterpret_cast<const f32x4 *>(w4_dev);
     const int refl = pad_mode == MIT_PAD_REFLECT;
-    // VALU-bound: algorithmic FLOPs 2 k^2 Cin Cout per pixel; bytes: input read once + Cout outputs written
+    // VALU-bound: algorithmic FLOPs 2 k^2 Cin Cout per pixel; bytes: input read once + Cout outputs written — of the pixels of the live
+    // tiles when a cell map is given (counted on the host from a copy of the map: a synchronising read, only while the probe is on)
+    double live_px = (double)B * H * W;
+    if (live_cells && mit_probe_on()) {
+        const bool packed = Cout <= 3 && w_pairs_dev;
+        const int th = packed ? TH3 : TH, tw = packed ? TW3 : TW, ch = mit_div_up(H, 8), cw = mit_div_up(W, 32);
+        std::vector<uint8_t> host((size_t)B * ch * cw);
+        MIT_CHECK_HIP(hipStreamSynchronize(s));
+        MIT_CHECK_HIP(hipMemcpy(host.data(), live_cells, host.size(), hipMemcpyDeviceToHost));
+        int64_t tiles = 0;
+        for (int b = 0; b < B; ++b)
+            for (int y0 = 0; y0 < H; y0 += th)
+                for (int x0 = 0; x0 < W; x0 += tw) {
+                    bool live = false;
+                    for (int cy = y0 / 8; cy < ch && cy < (y0 + th) / 8; ++cy)
+                        for (int cx = x0 / 32; cx < cw && cx < (x0 + tw) / 32; ++cx) live = live || host[((size_t)b * ch + cy) * cw + cx] != 0;
+                    tiles += live;
+                }
+        live_px = (double)tiles * th * tw;
+    }
     MitProbeScope probe(Cout <= 3 && w_pairs_dev ? (k == 7 ? "conv_small_cout3_kernel<7>" : k == 5 ? "conv_small_cout3_kernel<5>" : "conv_small_cout3_kernel<3>")
-                                                                    : (k == 7 ? "conv_small_cout_kernel<7>" : k == 5 ? "conv_small_cout_kernel<5>" : "conv_small_cout_kernel<3>"), s, 4.0 * (double)B * H * W * (Cin + Cout), 2.0 * k * k * (double)Cin * Cout * (double)B * H * W);
+                                                                    : (k == 7 ? "conv_small_cout_kernel<7>" : k == 5 ? "conv_small_cout_kernel<5>" : "conv_small_cout_kernel<3>"), s, 4.0 * live_px * (Cin + Cout), 2.0 * k * k * (double)Cin * Cout * live_px);
     // Cout <= 3: the packed-FMA kernel (2.7x fewer VALU instructions).  With 4-channel slices loaded straight from HBM it fetched
     // every 128-byte input line 8 times and was slower than the plain kernel (25 vs 17.7 ms per 16 pages); staging 16-channel groups
     // in registers brought it to 15.9 ms (same-box A/B).
@@ -337,27 +380,27 @@ extern "C" int mit_conv_small_cout(const float *in_dev, int64_t in_pixstride, in
         if (Cin & 3) return mit_set_error("mit_conv_small_cout: Cin %% 4");
         if (planes4) {
             switch (k) {
-                case 3: hipLaunchKernelGGL(conv_small_cout3_dma_kernel<3>, grid3, block, 0, s, in_dev, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, act, act_alpha, parity_major); break;
-                case 5: hipLaunchKernelGGL(conv_small_cout3_dma_kernel<5>, grid3, block, 0, s, in_dev, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, act, act_alpha, parity_major); break;
-                case 7: hipLaunchKernelGGL(conv_small_cout3_dma_kernel<7>, grid3, block, 0, s, in_dev, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, act, act_alpha, parity_major); break;
+                case 3: hipLaunchKernelGGL(conv_small_cout3_dma_kernel<3>, grid3, block, 0, s, in_dev, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, act, act_alpha, parity_major, live_cells); break;
+                case 5: hipLaunchKernelGGL(conv_small_cout3_dma_kernel<5>, grid3, block, 0, s, in_dev, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, act, act_alpha, parity_major, live_cells); break;
+                case 7: hipLaunchKernelGGL(conv_small_cout3_dma_kernel<7>, grid3, block, 0, s, in_dev, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, act, act_alpha, parity_major, live_cells); break;
                 default: return mit_set_error("mit_conv_small_cout: k must be 3, 5 or 7 (got %d)", k);
             }
             MIT_CHECK_LAUNCH("mit_conv_small_cout");
             return 0;
         }
         switch (k) {
-            case 3: hipLaunchKernelGGL(conv_small_cout3_kernel<3>, grid3, block, 0, s, in_dev, in_pixstride, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha); break;
-            case 5: hipLaunchKernelGGL(conv_small_cout3_kernel<5>, grid3, block, 0, s, in_dev, in_pixstride, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha); break;
-            case 7: hipLaunchKernelGGL(conv_small_cout3_kernel<7>, grid3, block, 0, s, in_dev, in_pixstride, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha); break;
+            case 3: hipLaunchKernelGGL(conv_small_cout3_kernel<3>, grid3, block, 0, s, in_dev, in_pixstride, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha, live_cells); break;
+            case 5: hipLaunchKernelGGL(conv_small_cout3_kernel<5>, grid3, block, 0, s, in_dev, in_pixstride, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha, live_cells); break;
+            case 7: hipLaunchKernelGGL(conv_small_cout3_kernel<7>, grid3, block, 0, s, in_dev, in_pixstride, in_planestride, wp, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha, live_cells); break;
             default: return mit_set_error("mit_conv_small_cout: k must be 3, 5 or 7 (got %d)", k);
         }
         MIT_CHECK_LAUNCH("mit_conv_small_cout");
         return 0;
     }
     switch (k) {
-        case 3: hipLaunchKernelGGL(conv_small_cout_kernel<3>, grid, block, 0, s, in_dev, in_pixstride, w4, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha); break;
-        case 5: hipLaunchKernelGGL(conv_small_cout_kernel<5>, grid, block, 0, s, in_dev, in_pixstride, w4, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha); break;
-        case 7: hipLaunchKernelGGL(conv_small_cout_kernel<7>, grid, block, 0, s, in_dev, in_pixstride, w4, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha); break;
+        case 3: hipLaunchKernelGGL(conv_small_cout_kernel<3>, grid, block, 0, s, in_dev, in_pixstride, w4, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha, live_cells); break;
+        case 5: hipLaunchKernelGGL(conv_small_cout_kernel<5>, grid, block, 0, s, in_dev, in_pixstride, w4, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha, live_cells); break;
+        case 7: hipLaunchKernelGGL(conv_small_cout_kernel<7>, grid, block, 0, s, in_dev, in_pixstride, w4, bias_dev, out_dev, out_pixstride, H, W, Cin, Cout, refl, act, act_alpha, live_cells); break;
         default: return mit_set_error("mit_conv_small_cout: k must be 3, 5 or 7 (got %d)", k);
     }
     MIT_CHECK_LAUNCH("mit_conv_small_cout");

@@ -217,13 +217,52 @@ class _FFC:
         return self._direct
 
 
+def _dilate(m: np.ndarray, r: int) -> np.ndarray:
+    p = np.pad(m, ((0, 0), (r, r), (r, r)))
+    H, W = m.shape[1:]
+    return np.any([p[:, dy:dy + H, dx:dx + W] for dy in range(2 * r + 1) for dx in range(2 * r + 1)], axis=0)
+
+
+def _pool2(m: np.ndarray) -> np.ndarray:
+    m = np.pad(m, ((0, 0), (0, m.shape[1] % 2), (0, m.shape[2] % 2)))
+    return m[:, 0::2, 0::2] | m[:, 0::2, 1::2] | m[:, 1::2, 0::2] | m[:, 1::2, 1::2]
+
+
+def _blocks_any(m: np.ndarray, bh: int, bw: int) -> np.ndarray:
+    B, H, W = m.shape
+    p = np.pad(m, ((0, 0), (0, -H % bh), (0, -W % bw)))
+    return p.reshape(B, p.shape[1] // bh, bh, p.shape[2] // bw, bw).any(axis=(2, 4))
+
+
+def tail_need_numpy(mask: np.ndarray) -> dict:
+    """What mit_lama_tail_need computes, in numpy (tests): from mask u8 [B, H, W] (H, W multiples of 8) the output convolution's
+    ``cells`` [B, H / 8, ceil(W / 32)], and per up-convolution L (0: output H/4 .. 2: output H) the need map ``sub[L]`` of its parity
+    sub-grid, ``need_out[L]`` (the positions of its output that are read), ``blocks[L]`` (live 8 x 8 blocks [B, bh, bw]), ``list[L]``
+    (their ids b * bh * bw + block, ascending) and ``start[L]`` (per-image prefix, B + 1 entries)."""
+    need = np.asarray(mask) >= 127
+    out = dict(cells=_blocks_any(need, 8, 32).astype(np.uint8), sub={}, need_out={}, blocks={}, list={}, start={})
+    need = _dilate(need, 3)                      # the 7x7 window
+    for L in (2, 1, 0):
+        out["need_out"][L] = need
+        sub = _pool2(need)                       # a sub-grid position is wanted when one of its 2 x 2 output parities is
+        blk = _blocks_any(sub, 8, 8)
+        out["sub"][L], out["blocks"][L] = sub, blk
+        out["list"][L] = np.flatnonzero(blk.reshape(-1)).astype(np.int32)
+        out["start"][L] = np.concatenate([[0], np.cumsum(blk.reshape(blk.shape[0], -1).sum(1))]).astype(np.int32)
+        need = _dilate(sub, 1)                   # input i feeds outputs 2i-1, 2i, 2i+1: a superset of the inputs that are read
+    return out
+
+
 class LamaEngine(ops.Engine):
     """Batched LaMa generator. ``forward(img_u8[B,H,W,3], mask_u8[B,H,W]) -> u8 [B,H,W,3]`` (device tensors)."""
 
     def __init__(self, gen_sd: Dict[str, torch.Tensor], mpe_sd: Optional[Dict[str, torch.Tensor]] = None,
                  n_blocks: int = 9, device="cuda", fft_h: bool = True, winograd: bool = True, fft_w: bool = True,
-                 row_packed_stem: bool = True):
+                 row_packed_stem: bool = True, masked_tail: bool = True):
         super().__init__(device)
+        # True: a composite computes the decoder tail (the three up-convolutions and the 7x7 output convolution) only where the mask
+        # lets the prediction through (mit_lama_tail_need); False: the dense tail, for A/B comparison
+        self.masked_tail = masked_tail
         self.winograd = winograd  # False: the FFC blocks' 3x3 convolutions in direct (9-tap) form, for A/B comparison
         self.fft_h = fft_h  # False: keep the H-axis transform on the dense DFT GEMM (for A/B comparison)
         self.fft_w = fft_w  # False: keep the W-axis transform on the dense DFT GEMM (for A/B comparison)
@@ -443,6 +482,22 @@ class LamaEngine(ops.Engine):
         ffc.st_out(t2, out=out[..., LOCAL_C:], pre=P, post=res_g, nprod=nprod)
         self._dbg_put("s2_out_global", out[..., LOCAL_C:])  # conv2(x + fu(x)) + convl2g -> bn_g -> relu (+ id_g)
 
+    def _tail_need(self, mask_u8: torch.Tensor):
+        """([(blocks, start)] of ups[0..2], cells) for this batch's masks: device tensors from the workspace, filled on the current stream."""
+        B, H, W = mask_u8.shape
+        lib = _lib.load()
+        cells = self._buf("need_cells", B, H // 8, (W + 31) // 32, dtype=torch.uint8)
+        work = self._buf("need_work", int(lib.mit_lama_tail_need_work(B, H, W)), dtype=torch.uint8)
+        live = []
+        for L in range(3):
+            h, w = H >> (3 - L), W >> (3 - L)
+            live.append((self._buf(f"need_list{L}", B * ((h + 7) // 8) * ((w + 7) // 8), dtype=torch.int32),
+                         self._buf(f"need_start{L}", B + 1, dtype=torch.int32)))
+        _lib.check(lib.mit_lama_tail_need(mask_u8.data_ptr(), B, H, W, cells.data_ptr(), live[0][0].data_ptr(), live[0][1].data_ptr(),
+                                          live[1][0].data_ptr(), live[1][1].data_ptr(), live[2][0].data_ptr(), live[2][1].data_ptr(),
+                                          work.data_ptr(), C.c_void_p(ops.current_stream())), "mit_lama_tail_need")
+        return live, cells
+
     # -- full generator ------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, taps: Optional[dict] = None, composite: bool = True,
@@ -522,21 +577,28 @@ class LamaEngine(ops.Engine):
             self._ffc(c2, T, X, X, nprod)  # in place: each element reads its own residual before it is overwritten
             if taps is not None:
                 taps[f"block{i}"] = X.clone()
+        # The tail is local, and a composite takes the prediction only where mask >= 127 (lama_post): compute the blocks that such a
+        # pixel reads, nothing else.  Dead positions of u1 / u2 / u3 / pred keep whatever the buffers held (stale encoder values) and
+        # are read only for outputs that nobody reads.  With taps or the debug store the tail stays dense: they show whole tensors.
+        live = [None, None, None]
+        cells = None
+        if self.masked_tail and composite and taps is None and self._dbg is None:
+            live, cells = self._tail_need(mask_u8)
         u1 = self._buf("d2", B, H // 4, W // 4, 256)
-        self.ups[0](X, out=u1, nprod=nprod)
+        self.ups[0](X, out=u1, nprod=nprod, live=live[0])
         u2 = self._buf("d1", B, H // 2, W // 2, 128)
-        self.ups[1](u1, out=u2, nprod=nprod)
+        self.ups[1](u1, out=u2, nprod=nprod, live=live[1])
         pred = self._buf("pred", B, H, W, 3)
         if self.planar_tail:   # the last up-convolution writes 64 / P planes of P channels, the 7x7 output convolution reads them slice by slice
             P = self.planar_tail
             pm = P == 4 and H % 2 == 0 and W % 2 == 0   # 4-channel planes as four dense parity sub-images: both sides move consecutive pixels
             u3 = self._buf("full64", 64 // P, B, H, W, P)
-            self.ups[2](u2, out=u3, planes=64 // P, parity_major=pm, nprod=nprod)
-            self.out_conv(u3, out=pred, parity_major=pm)
+            self.ups[2](u2, out=u3, planes=64 // P, parity_major=pm, nprod=nprod, live=live[2])
+            self.out_conv(u3, out=pred, parity_major=pm, cells=cells)
         else:                  # planar_tail = 0: NHWC between the two (tests) — same values, other addresses
             u3 = self._buf("full64", B, H, W, 64)
-            self.ups[2](u2, out=u3, nprod=nprod)
-            self.out_conv(u3, out=pred)
+            self.ups[2](u2, out=u3, nprod=nprod, live=live[2])
+            self.out_conv(u3, out=pred, cells=cells)
         if taps is not None:
             taps["pred"] = pred.clone()
         out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=self.device)

@@ -9,7 +9,7 @@ import ctypes as C
 from pathlib import Path
 
 MIT_MAX_TAPS = 64
-MIT_ABI_VERSION = 20
+MIT_ABI_VERSION = 21
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SILU, ACT_SIGMOID, ACT_GELU = range(6)
 ACT_POST_FIRST = 0x100
@@ -74,7 +74,9 @@ class MitConvGemm(C.Structure):
         ("lut2", C.c_void_p),
         ("lut_ld", C.c_int64),
         ("nprod", C.c_int32),   # 0 = follow the GEMM mode; 1 = the one-product bf16 tiles (include/mit_hip.h)
-        ("_pad1", C.c_int32),
+        ("live_img0", C.c_int32),    # the live-block list (include/mit_hip.h): batch index of the launch's first image
+        ("live_blocks", C.c_void_p),  # int32 ids of the live 8 x 8 output blocks of the batch, ascending; NULL = dense
+        ("live_start", C.c_void_p),   # int32 [NB + 1]: each image's first entry in live_blocks, then the total
     ]
 
 
@@ -194,7 +196,9 @@ SYMBOLS = {
     "mit_gemm_mode_get": (C.c_int, []),
     "mit_gemm_split_min_tiles": (C.c_int64, [C.c_int64]),
     "mit_conv_small_cout": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "mit_lama_tail_need_work": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mit_lama_tail_need": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 9),
     "mit_convnext_mlp_supported": (C.c_int, [C.c_int]),
     "mit_convnext_mlp": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),

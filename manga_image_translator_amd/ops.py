@@ -142,9 +142,11 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
                    pre: Optional[MitTensorMap] = None, post: Optional[MitTensorMap] = None,
                    scale: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
                    alpha: float = 0.0, Z: int = 1, zdiv: int = 1, a_zs: Tuple[int, int] = (0, 0),
-                   w_zs: Tuple[int, int] = (0, 0), nprod: int = 0) -> MitConvGemm:
+                   w_zs: Tuple[int, int] = (0, 0), nprod: int = 0,
+                   live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> MitConvGemm:
     """Fill a ``MitConvGemm`` descriptor. Pure host logic (usable without a GPU).  ``nprod`` = 1: the one-product bf16 tiles for this
-    launch (MitConvGemm.nprod; the weight must carry planes: ``ensure_split``)."""
+    launch (MitConvGemm.nprod; the weight must carry planes: ``ensure_split``).  ``live`` = (blocks, start): int32 device tensors, the
+    list of live 8 x 8 output blocks and its per-image prefix (MitConvGemm.live_blocks / live_start) — only they are computed."""
     if len(taps) == 0 or len(taps) > MIT_MAX_TAPS:
         raise ValueError(f"ntaps {len(taps)} out of range")
     d = MitConvGemm()
@@ -171,6 +173,11 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
     d.bias = _ptr(bias)
     d.act, d.act_alpha = act, alpha
     d.nprod = int(nprod)
+    if live is not None:
+        blocks, start = live
+        if blocks.dtype != torch.int32 or start.dtype != torch.int32 or start.numel() < NB + 1:
+            raise ValueError("conv_gemm_desc: live = (int32 block ids, int32 [NB + 1] prefix)")
+        d.live_blocks, d.live_start = blocks.data_ptr(), start.data_ptr()
     return d
 
 
@@ -561,8 +568,10 @@ class ConvSmallCout:
         self.w_pairs = (w4.reshape(kh * kw, Cin // 4, 4, 4).permute(0, 1, 3, 2).to(device).contiguous() if Cout <= 3 else None)
         self.bias = None if bias is None else bias.detach().to(torch.float32).to(device).contiguous()
 
-    def __call__(self, x: torch.Tensor, out: torch.Tensor, parity_major: bool = False) -> torch.Tensor:
-        """``parity_major``: the P = 4 planes hold each image as four dense sub-images [2][2][H / 2][W / 2][4] (what
+    def __call__(self, x: torch.Tensor, out: torch.Tensor, parity_major: bool = False, cells: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``cells``: u8 [B, ceil(H / 8), ceil(W / 32)] (device) — only tiles that cover a non-zero 8 x 32 cell are computed, the rest of
+        ``out`` is left as it is.
+        ``parity_major``: the P = 4 planes hold each image as four dense sub-images [2][2][H / 2][W / 2][4] (what
         ``ConvTranspose2d(..., planes=, parity_major=True)`` writes).
         ``x``: [B,H,W,C] NHWC, or the same activations as planes [C / P, B, H, W, P], P = 16 or 4 (contiguous; what
         ``ConvTranspose2d(..., planes=)`` writes) — the packed kernel then loads whole lines per channel group (P = 16) or takes each
@@ -590,9 +599,11 @@ class ConvSmallCout:
         lib = _lib.load()
         if parity_major and not plane:
             raise ValueError("ConvSmallCout: parity_major without planar input")
+        if cells is not None and (cells.dtype != torch.uint8 or tuple(cells.shape) != (B, (H + 7) // 8, (W + 31) // 32) or not cells.is_contiguous()):
+            raise ValueError(f"ConvSmallCout: cells must be contiguous u8 [{B}, {(H + 7) // 8}, {(W + 31) // 32}]")
         _lib.check(lib.mit_conv_small_cout(x.data_ptr(), x.stride(2), -plane if parity_major else plane, self.w4.data_ptr(), _ptr(self.w_pairs), _ptr(self.bias), out.data_ptr(),
                                            out.stride(2), B, H, W, self.Cin, self.Cout, self.k, self.pad_mode, self.act,
-                                           self.alpha, C.c_void_p(current_stream())), "mit_conv_small_cout")
+                                           self.alpha, _ptr(cells), C.c_void_p(current_stream())), "mit_conv_small_cout")
         return out
 
 
@@ -692,8 +703,11 @@ class ConvTranspose2d:
     def out_hw(self, H: int, W: int) -> Tuple[int, int]:
         return ((H - 1) * self.s - 2 * self.p + self.k[0] + self.op, (W - 1) * self.s - 2 * self.p + self.k[1] + self.op)
 
-    def descs(self, x: torch.Tensor, out: torch.Tensor, planes: int = 0, parity_major: bool = False, nprod: int = 0) -> List[MitConvGemm]:
-        """``planes`` = P > 0: ``out`` is [P, B, Ho, Wo, Cout / P] (contiguous) and every launch writes through a column-split map
+    def descs(self, x: torch.Tensor, out: torch.Tensor, planes: int = 0, parity_major: bool = False, nprod: int = 0,
+              live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> List[MitConvGemm]:
+        """``live`` = (blocks, start): one list of live 8 x 8 blocks of the parity sub-grid, shared by the parity launches (a block is
+        listed when any of its parities is wanted): only those blocks of ``out`` are written.  All classes must have the same sub-grid.
+        ``planes`` = P > 0: ``out`` is [P, B, Ho, Wo, Cout / P] (contiguous) and every launch writes through a column-split map
         (MitTensorMap.nsplit = Cout / P): channel group g of a pixel goes to plane g.  The consumer that reads channel groups (the 7x7
         output convolution) then finds each group in whole lines."""
         split = nhi = 0
@@ -715,6 +729,8 @@ class ConvTranspose2d:
         ds = []
         for py, px, pk in self.sub:
             ov = out[:, py::self.s, px::self.s]
+            if live is not None and (ov.shape[1] * self.s != Ho or ov.shape[2] * self.s != Wo):
+                raise ValueError("ConvTranspose2d: a live-block list needs an output size that is a multiple of the stride")
             if ov.shape[1] == 0 or ov.shape[2] == 0:
                 continue
             if nprod:
@@ -727,15 +743,15 @@ class ConvTranspose2d:
                 a=x, NB=B, Hi=H, Wi=W, Cin=self.Cin, a_strides=(x.stride(0), x.stride(1), x.stride(2)),
                 Ho=ov.shape[1], Wo=ov.shape[2], sy=1, sx=1, taps=pk.taps, pad_mode=PAD_ZERO, w=pk.w, ldw=pk.Np,
                 Kw=pk.Kp, Nw=pk.Np, N=self.Cout, c=tensor_map(ov, nsplit=split, nhi=nhi), scale=self.scale, bias=self.bias, act=self.act,
-                alpha=self.alpha, nprod=nprod))
+                alpha=self.alpha, nprod=nprod, live=live))
         return ds
 
     def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, cfg: int = -1, planes: int = 0, parity_major: bool = False,
-                 nprod: int = 0) -> torch.Tensor:
+                 nprod: int = 0, live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
         if out is None:
             Ho, Wo = self.out_hw(x.shape[1], x.shape[2])
             out = (torch.empty(planes, x.shape[0], Ho, Wo, self.Cout // planes, dtype=torch.float32, device=x.device) if planes else
                    torch.empty(x.shape[0], Ho, Wo, self.Cout, dtype=torch.float32, device=x.device))
-        for d in self.descs(x, out, planes, parity_major, nprod):
+        for d in self.descs(x, out, planes, parity_major, nprod, live):
             launch_conv_gemm(d, cfg)
         return out
