@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 21
+#define MIT_ABI_VERSION 22
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -141,6 +141,22 @@ typedef struct MitConvGemm {
     int32_t live_img0;
     const int32_t *live_blocks;
     const int32_t *live_start;
+    /* optional: the ``pre`` operand taken from the 36 Winograd F(4x4, 3x3) products of a 3x3 convolution over the same output grid,
+     * wino_m [36][T][wino_n] (T = NB * wino_th * wino_tw tiles of 4 x 4 outputs, image-major raster; what the Z = 36 launch of
+     * WinogradConv3x3 writes), wino_zs floats between two of the 36 slices:
+     *     epilogue(v) = act( (v + (A^T m A)[oy & 3][ox & 3]) * scale[n] + bias[n] ) + post[..]
+     * with m the 6 x 6 products of tile (oy >> 2, ox >> 2) and column n — the value mit_wino43_output (no scale, bias or activation)
+     * would have stored at (nb, oy, ox, n), computed by the same expression sequence, so the result has the bits of that launch
+     * followed by this one with its output as ``pre``; the staging tensor and its launch disappear.  Needs the 8 x 8 block row order
+     * (live_blocks / live_start: list every block for a dense layer), under which the 16 rows a lane holds of one accumulator block are
+     * one whole tile; one tap with sy == sx == 1, pre.base == NULL, no column-split map, N % 4 == 0, wino_n == N,
+     * wino_th == ceil(Ho / 4), wino_tw == ceil(Wo / 4), wino_zs >= T * wino_n — anything else is refused.  A batch cut into runs moves
+     * wino_m along with the operands.  NULL = off.  Replaces nothing of the reference by itself (convl2g(x_l) joins conv2's output in
+     * FFC.forward, inpainting_lama_mpe.py:365-368). */
+    const float *wino_m;
+    int64_t wino_zs;
+    int32_t wino_n, wino_th, wino_tw;
+    int32_t _pad_wino;
 } MitConvGemm;
 
 const char *mit_last_error(void);
@@ -198,8 +214,8 @@ int64_t mit_gemm_split_min_tiles(int64_t n);
 
 /* ---- planar operands: the plain GEMMs of the split-bf16 mode with activations that ARRIVE split ---------------------------------
  * In mit_conv_gemm's split tiles the activations are split into their three bf16 planes by VALU work inside the K loop, once per
- * output-column tile.  When the producer of an activation tensor writes the planes itself (mit_split_planes, the planar forms of
- * mit_dwconv_nhwc_ragged_rows / mit_wino43_input, or mit_pgemm's own planar epilogue) a plain GEMM (1x1 convolution, nn.Linear, the 36
+ * output-column tile.  When the producer of an activation tensor writes the planes itself (mit_split_planes, or mit_pgemm's own
+ * planar epilogue) a plain GEMM (1x1 convolution, nn.Linear, the 36
  * Winograd products) needs no VALU work in its K loop at all: both operands go global -> LDS by the LDS-DMA (global_load_lds_dwordx4)
  * in the cell layout the bf16 MFMA consumes, a ring of stages keeps the loads one or two K-tiles ahead behind counted vmcnt waits, and
  * a workgroup walks several output tiles so that the next tile's loads are in flight during an epilogue.
@@ -322,7 +338,8 @@ typedef struct MitProfStat {
 int mit_prof_enable(int on); /* clears the records; on != 0 starts recording */
 int mit_prof_tag_next(double alg_flops);
 int mit_prof_read(MitProfStat *stats, int max_cfgs, int *n_cfgs);
-/* One CSV line per recorded launch (tile, M, N, K, taps, Z, act, ms, executed / algorithmic FLOPs): the per-layer view behind
+/* One CSV line per recorded launch (tile, M, N, K, taps, Z, act, ms, executed / algorithmic FLOPs, bytes of the Winograd
+ * pre-operand its epilogue read — MitConvGemm.wino_m, 0 without one): the per-layer view behind
  * bench.py's per-tile totals (scripts/ocr_layers.py).  Call before mit_prof_enable() clears the records. */
 int mit_prof_dump(const char *path);
 /* The same probe for the kernels that are NOT mit_conv_gemm (the HBM-bound transforms / FFTs / element-wise passes, the VALU

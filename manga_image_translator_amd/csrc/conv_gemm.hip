@@ -151,6 +151,7 @@ struct ProbeRec {
     int cfg;
     double exec_flops, alg_flops;
     int M, N, K, ntaps, Z, act;
+    double wino_bytes;  // the Winograd pre-operand read by the epilogue (MitConvGemm.wino_m): 36 products per tile and column
 };
 std::mutex g_probe_mu;
 bool g_probe_on = false;
@@ -181,15 +182,15 @@ extern "C" int mit_prof_dump(const char *path) {
     std::lock_guard<std::mutex> lk(g_probe_mu);
     FILE *f = fopen(path, "w");
     if (!f) return mit_set_error("mit_prof_dump: cannot open %s", path);
-    fprintf(f, "tile,M,N,K,taps,Z,act,ms,exec_flops,alg_flops\n");
+    fprintf(f, "tile,M,N,K,taps,Z,act,ms,exec_flops,alg_flops,wino_bytes\n");
     for (auto &r : g_probe) {
         float ms = 0.f;
         if (hipEventSynchronize(r.stop) != hipSuccess || hipEventElapsedTime(&ms, r.start, r.stop) != hipSuccess) {
             fclose(f);
             return mit_set_error("mit_prof_dump: event query failed");
         }
-        fprintf(f, "%s,%d,%d,%d,%d,%d,%d,%.6f,%.0f,%.0f\n", kCfgs[r.cfg].name, r.M, r.N, r.K, r.ntaps, r.Z, r.act, ms, r.exec_flops,
-                r.alg_flops);
+        fprintf(f, "%s,%d,%d,%d,%d,%d,%d,%.6f,%.0f,%.0f,%.0f\n", kCfgs[r.cfg].name, r.M, r.N, r.K, r.ntaps, r.Z, r.act, ms, r.exec_flops,
+                r.alg_flops, r.wino_bytes);
     }
     fclose(f);
     return 0;
@@ -289,6 +290,17 @@ int validate(const MitConvGemm *d, MitConvGemm &p) {
     } else if (p.live_img0 != 0) {
         return mit_set_error("mit_conv_gemm: live_img0 without a live-block list");
     }
+    if (p.wino_m) {  // the Winograd pre-operand (wino_pre_add): a lane's 16 rows of an accumulator block must be one 4 x 4 tile
+        if (!p.live_blocks) return mit_set_error("mit_conv_gemm: wino_m needs the 8 x 8 block row order (live_blocks / live_start; list every block for a dense layer)");
+        if (p.ntaps != 1 || p.sy != 1 || p.sx != 1) return mit_set_error("mit_conv_gemm: wino_m is for one tap with stride 1 (got %d taps, stride %d x %d)", p.ntaps, p.sy, p.sx);
+        if (p.pre.base) return mit_set_error("mit_conv_gemm: wino_m together with a pre operand is not implemented");
+        if (p.c.nsplit || (p.post.base && p.post.nsplit)) return mit_set_error("mit_conv_gemm: wino_m with a column-split map is not implemented");
+        if ((p.N & 3) || p.wino_n != p.N) return mit_set_error("mit_conv_gemm: wino_m needs N %% 4 == 0 and wino_n == N (N=%d wino_n=%d)", p.N, p.wino_n);
+        if (p.wino_th != (p.Ho + 3) / 4 || p.wino_tw != (p.Wo + 3) / 4)
+            return mit_set_error("mit_conv_gemm: wino_th x wino_tw must be ceil(Ho / 4) x ceil(Wo / 4) (got %d x %d for %d x %d)", p.wino_th, p.wino_tw, p.Ho, p.Wo);
+        if (p.wino_zs < (int64_t)p.NB * p.wino_th * p.wino_tw * p.wino_n) return mit_set_error("mit_conv_gemm: wino_zs is shorter than one slice of tiles (NB * wino_th * wino_tw * wino_n)");
+        if (reinterpret_cast<uintptr_t>(p.wino_m) & 3) return mit_set_error("mit_conv_gemm: wino_m must be 4-byte aligned");
+    }
     if (p.Z > 65535) return mit_set_error("mit_conv_gemm: Z too large");
     if (p.nprod != 0 && p.nprod != 1) return mit_set_error("mit_conv_gemm: nprod must be 0 (the GEMM mode) or 1 (one bf16 product) (got %d)", p.nprod);
     if (p.nprod == 1 && !p.w_split) return mit_set_error("mit_conv_gemm: nprod = 1 needs w_split (mit_gemm_split_pack): there is no fp32 fallback for a requested precision");
@@ -324,6 +336,7 @@ MitConvGemm run_of(const MitConvGemm &p, int b0, int nb) {
     if (p.pre.base) r.pre.base += (int64_t)b0 * p.pre.bs;
     if (p.post.base) r.post.base += (int64_t)b0 * p.post.bs;
     if (p.lut_rows) r.lut_rows += (int64_t)b0 * p.Ho * p.Wo;
+    if (p.wino_m) r.wino_m += (int64_t)b0 * p.wino_th * p.wino_tw * p.wino_n;
     if (p.live_blocks) r.live_start += b0, r.live_img0 += b0;  // the run's segment of the list: [live_start[b0], live_start[b0 + nb])
     return r;
 }
@@ -379,6 +392,7 @@ int launch_run(const MitConvGemm &p, int cfg, hipStream_t hs) {
         r.exec_flops = 2.0 * (double)M * p.N * Ktot * p.Z;
         r.alg_flops = tagged >= 0.0 ? tagged : r.exec_flops;
         r.M = M, r.N = p.N, r.K = Ktot, r.ntaps = p.ntaps, r.Z = p.Z, r.act = p.act;
+        r.wino_bytes = p.wino_m ? 4.0 * 36.0 * (double)p.NB * p.wino_th * p.wino_tw * p.wino_n : 0.0;
         MIT_CHECK_HIP(hipEventRecord(r.start, hs));
         c.launch(p, M, MT, NT, KT, hs);
         MIT_CHECK_HIP(hipEventRecord(r.stop, hs));

@@ -32,6 +32,7 @@
 #include <vector>
 #include "../../include/mit_hip.h"
 #include "common.h"
+#include "wino_at6.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -205,10 +206,55 @@ __device__ __forceinline__ void epilogue_store_vec(const MitConvGemm &p, f32x16 
     }
 }
 
-template <int BM, int TM, int TN, int SMEM_FLOATS = 0, int NTHR = 256>
+// ---- the Winograd pre-operand (MitConvGemm.wino_m): acc += A^T m A, tile by tile, ahead of the shared store loops ----------------
+// Under the 8 x 8 block row order (decode_row's list form) row m is position m & 63 of its block, and a lane holds of one 32 x 32
+// accumulator block the rows (r & 3) + 8 * (r >> 2) + 4 * lh of the block's 32-row half q: y = 4 q + (r >> 2), x = 4 lh + (r & 3) —
+// the whole 4 x 4 Winograd tile (2 by + q, 2 bx + lh), element (r >> 2, r & 3) in acc[..][r], of one output column.  So the lane loads
+// that tile's 36 products of its column (each load 128 contiguous bytes over a half-wave) and runs the passes of wino43_output_kernel
+// (wino_at6.h: same expressions, same order) in registers: no LDS, no cross-lane traffic.  The tile is there exactly when its first
+// position (r = 0) decodes to a live row: oy = 4 ty < Ho <=> ty < ceil(Ho / 4), the same along x; positions of an edge tile outside
+// Ho x Wo receive a value and stay dead rows that the store loops skip.
+template <int TM, int TN>
+__device__ __forceinline__ void wino_pre_add(const MitConvGemm &p, f32x16 (&acc)[TM][TN], const int M, const int m0, const int n0,
+                                             const int wm0, const int wn0, const int HoWo, const int tid) {
+    const int lane = tid & 63;
+    const int li = lane & 31;
+    const int lh = lane >> 5;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+        int nb, oy, ox;
+        if (!decode_row(p, m0 + wm0 + mi * 32 + 4 * lh, M, HoWo, nb, oy, ox)) continue;
+        const float *mt = p.wino_m + ((int64_t)(nb * p.wino_th + (oy >> 2)) * p.wino_tw + (ox >> 2)) * p.wino_n;
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni) {
+            const int n = n0 + wn0 + ni * 32 + li;
+            if (n >= p.N) continue;
+            const float *mp = mt + n;
+            float t[4][6];  // A^T m, column by column
+#pragma unroll
+            for (int s = 0; s < 6; ++s) {
+                float c[6];
+#pragma unroll
+                for (int r = 0; r < 6; ++r) c[r] = mp[(int64_t)(r * 6 + s) * p.wino_zs];
+                at6(c[0], c[1], c[2], c[3], c[4], c[5], t[0][s], t[1][s], t[2][s], t[3][s]);
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                float o[4];
+                at6(t[a][0], t[a][1], t[a][2], t[a][3], t[a][4], t[a][5], o[0], o[1], o[2], o[3]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[mi][ni][a * 4 + e] += o[e];
+            }
+        }
+    }
+}
+
+// WINO: the kernel takes MitConvGemm.wino_m (the fast and split tiles; the launcher refuses it on the others)
+template <int BM, int TM, int TN, int SMEM_FLOATS = 0, int NTHR = 256, bool WINO = false>
 __device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM][TN], float *smem, const int M, const int m0,
                                          const int n0, const int wm0, const int wn0, const int z1, const int z0,
                                          const int HoWo, const int tid) {
+    if (WINO && p.wino_m != nullptr) wino_pre_add<TM, TN>(p, acc, M, m0, n0, wm0, wn0, HoWo, tid);
     // tid: the caller's thread index — threadIdx.x, or the same number rebuilt after the K loop (wave index kept in an SGPR, lane from
     // mbcnt) so that no thread-index-derived register has to stay live, or be spilled to scratch, across the loop
     RowOff *rowoff = reinterpret_cast<RowOff *>(smem);  // BM entries (<= A/B staging area)
@@ -644,7 +690,7 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     // buffers, so small tiles (64 x 64) get the dwordx4 store path too
     constexpr int EPI_FLOATS = (BM * (int)sizeof(RowOff) + 15) / 16 * 4 + 4 * 32 * EPI_PITCH + BM * (int)sizeof(LutOff) / 4;
     constexpr int SMEM_F = (2 * A_TILE + 2 * B_TILE) > EPI_FLOATS ? (2 * A_TILE + 2 * B_TILE) : EPI_FLOATS;
-    epilogue<BM, TM, TN, SMEM_F>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
+    epilogue<BM, TM, TN, SMEM_F, 256, true>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
 }
 // ---- N <= 4: one output column group per row — a dot product, not a tile ------------------------------------------------
 // An MFMA tile would idle >= 28 of its 32 columns (the ctd heads' last ConvTranspose2d 64 -> 1 and 16 -> 1 ran at 2 TFLOP/s on

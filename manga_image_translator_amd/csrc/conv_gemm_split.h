@@ -353,7 +353,7 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     // 128 x 128 tile otherwise spilled eight such registers to scratch memory; see DESIGN §7 on why no kernel of this library may use
     // scratch)
     const int tid_e = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    epilogue<BM, TM, TN, SMEM_F>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
+    epilogue<BM, TM, TN, SMEM_F, 256, true>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
 }
 
 // (A one-wave-per-32x32-block form with register-streamed operands for few-row GEMMs — a page's decoder Linears, M = 160 — was built and

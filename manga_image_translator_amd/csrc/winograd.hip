@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include "../../include/mit_hip.h"
 #include "common.h"
+#include "wino_at6.h"
 
 namespace {
 
@@ -88,15 +89,7 @@ __global__ __launch_bounds__(256) void wino43_input_kernel(const float *__restri
         for (int s = 0; s < 6; ++s) *reinterpret_cast<float2 *>(vo + (int64_t)(r * 6 + s) * zstride) = d[r][s];
 }
 
-// A^T (rows): [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
-__device__ __forceinline__ void at6(const float m0, const float m1, const float m2, const float m3, const float m4, const float m5,
-                                    float &y0, float &y1, float &y2, float &y3) {
-    const float s12 = m1 + m2, d12 = m1 - m2, s34 = m3 + m4, d34 = m3 - m4;
-    y0 = (m0 + s12) + s34;
-    y1 = d12 + 2.f * d34;
-    y2 = s12 + 4.f * s34;
-    y3 = (d12 + 8.f * d34) + m5;
-}
+// (at6, the A^T pass of the output transform: wino_at6.h, shared with the GEMM epilogue that folds the transform in)
 
 __device__ __forceinline__ float wino_act(float v, int act, float alpha) {
     if (act == MIT_ACT_RELU) return v > 0.f ? v : 0.f;

@@ -258,8 +258,11 @@ class LamaEngine(ops.Engine):
 
     def __init__(self, gen_sd: Dict[str, torch.Tensor], mpe_sd: Optional[Dict[str, torch.Tensor]] = None,
                  n_blocks: int = 9, device="cuda", fft_h: bool = True, winograd: bool = True, fft_w: bool = True,
-                 row_packed_stem: bool = True, masked_tail: bool = True):
+                 row_packed_stem: bool = True, masked_tail: bool = True, fold_l2g: bool = True):
         super().__init__(device)
+        # True: convl2g's Winograd output transform runs in conv2's epilogue (MitConvGemm.wino_m: no staging tensor, one launch less per
+        # layer); False: the three-launch form, for A/B comparison.  Same bytes either way.
+        self.fold_l2g = fold_l2g
         # True: a composite computes the decoder tail (the three up-convolutions and the 7x7 output convolution) only where the mask
         # lets the prediction through (mit_lama_tail_need); False: the dense tail, for A/B comparison
         self.masked_tail = masked_tail
@@ -454,7 +457,11 @@ class LamaEngine(ops.Engine):
         x_l, x_g = x[..., :LOCAL_C], x[..., LOCAL_C:]
         res_l = None if residual is None else residual[..., :LOCAL_C]
         res_g = None if residual is None else residual[..., LOCAL_C:]
-        P = self._buf("ffc_P", B, h, w, GLOBAL_C)
+        # convl2g(x_l) joins conv2's output: as the staging tensor P (st_out's ``pre``), or — fp32 Winograd form — as the 36 products
+        # M_g that st_out's epilogue transforms itself.  The debug store shows P, so it keeps the three-launch form.
+        fold = self.fold_l2g and ffc.winograd and not nprod and self._dbg is None
+        P = None if fold else self._buf("ffc_P", B, h, w, GLOBAL_C)
+        M_g = None
         if nprod:
             to_l, l2g = ffc.direct()
             to_l(x, out=out[..., :LOCAL_C], post=res_l, nprod=nprod)
@@ -467,9 +474,13 @@ class LamaEngine(ops.Engine):
             ffc.to_l.gemm_output(V, self._buf("wino_ml", 36, T, LOCAL_C), out[..., :LOCAL_C], post=res_l)
             self._dbg_put("w2_wino_products_l", self._buf("wino_ml", 36, T, LOCAL_C))
             self._dbg_put("w3_out_local", out[..., :LOCAL_C])
-            ffc.l2g.gemm_output(V, self._buf("wino_mg", 36, T, GLOBAL_C), P)
+            if fold:
+                M_g = ffc.l2g.products(V, self._buf("wino_mg", 36, T, GLOBAL_C))
+            else:
+                ffc.l2g.gemm_output(V, self._buf("wino_mg", 36, T, GLOBAL_C), P)
             self._dbg_put("w4_wino_products_g", self._buf("wino_mg", 36, T, GLOBAL_C))
-            self._dbg_put("w5_P", P)
+            if P is not None:
+                self._dbg_put("w5_P", P)
         else:
             ffc.to_l(x, out=out[..., :LOCAL_C], post=res_l)  # convl2l(x_l) + convg2l(x_g) -> bn_l -> relu (+ id_l)
             ffc.l2g(x_l, out=P)  # convl2g(x_l), raw
@@ -479,7 +490,7 @@ class LamaEngine(ops.Engine):
         self._dbg_put("s1_st_in", t1)
         self._fourier_unit(ffc, t1, t2, nprod)
         self._dbg_put("fu5_irfft_rows_plus_t1", t2)
-        ffc.st_out(t2, out=out[..., LOCAL_C:], pre=P, post=res_g, nprod=nprod)
+        ffc.st_out(t2, out=out[..., LOCAL_C:], pre=P, wino_pre=M_g, post=res_g, nprod=nprod)
         self._dbg_put("s2_out_global", out[..., LOCAL_C:])  # conv2(x + fu(x)) + convl2g -> bn_g -> relu (+ id_g)
 
     def _tail_need(self, mask_u8: torch.Tensor):

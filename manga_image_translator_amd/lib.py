@@ -9,7 +9,7 @@ import ctypes as C
 from pathlib import Path
 
 MIT_MAX_TAPS = 64
-MIT_ABI_VERSION = 21
+MIT_ABI_VERSION = 22
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SILU, ACT_SIGMOID, ACT_GELU = range(6)
 ACT_POST_FIRST = 0x100
@@ -77,6 +77,12 @@ class MitConvGemm(C.Structure):
         ("live_img0", C.c_int32),    # the live-block list (include/mit_hip.h): batch index of the launch's first image
         ("live_blocks", C.c_void_p),  # int32 ids of the live 8 x 8 output blocks of the batch, ascending; NULL = dense
         ("live_start", C.c_void_p),   # int32 [NB + 1]: each image's first entry in live_blocks, then the total
+        ("wino_m", C.c_void_p),      # the Winograd pre-operand (include/mit_hip.h): the 36 products [36][T][wino_n]; NULL = off
+        ("wino_zs", C.c_int64),      # floats between two of the 36 slices
+        ("wino_n", C.c_int32),       # row length of wino_m (== N)
+        ("wino_th", C.c_int32),      # tiles per image, ceil(Ho / 4) x ceil(Wo / 4)
+        ("wino_tw", C.c_int32),
+        ("_pad_wino", C.c_int32),
     ]
 
 

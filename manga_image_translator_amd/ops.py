@@ -143,10 +143,12 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
                    scale: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, act: int = ACT_NONE,
                    alpha: float = 0.0, Z: int = 1, zdiv: int = 1, a_zs: Tuple[int, int] = (0, 0),
                    w_zs: Tuple[int, int] = (0, 0), nprod: int = 0,
-                   live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> MitConvGemm:
+                   live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, wino_pre: Optional[torch.Tensor] = None) -> MitConvGemm:
     """Fill a ``MitConvGemm`` descriptor. Pure host logic (usable without a GPU).  ``nprod`` = 1: the one-product bf16 tiles for this
     launch (MitConvGemm.nprod; the weight must carry planes: ``ensure_split``).  ``live`` = (blocks, start): int32 device tensors, the
-    list of live 8 x 8 output blocks and its per-image prefix (MitConvGemm.live_blocks / live_start) — only they are computed."""
+    list of live 8 x 8 output blocks and its per-image prefix (MitConvGemm.live_blocks / live_start) — only they are computed.
+    ``wino_pre``: the 36 Winograd products ``[36, T, N]`` of a 3x3 convolution over the same output grid (``WinogradConv3x3.products``),
+    whose output transform the epilogue computes where it would add ``pre`` (MitConvGemm.wino_m; needs ``live``)."""
     if len(taps) == 0 or len(taps) > MIT_MAX_TAPS:
         raise ValueError(f"ntaps {len(taps)} out of range")
     d = MitConvGemm()
@@ -178,7 +180,27 @@ def conv_gemm_desc(*, a: torch.Tensor, NB: int, Hi: int, Wi: int, Cin: int, a_st
         if blocks.dtype != torch.int32 or start.dtype != torch.int32 or start.numel() < NB + 1:
             raise ValueError("conv_gemm_desc: live = (int32 block ids, int32 [NB + 1] prefix)")
         d.live_blocks, d.live_start = blocks.data_ptr(), start.data_ptr()
+    if wino_pre is not None:
+        th, tw = (Ho + 3) // 4, (Wo + 3) // 4
+        if wino_pre.dtype != torch.float32 or tuple(wino_pre.shape) != (36, NB * th * tw, N) or wino_pre.stride(2) != 1 or wino_pre.stride(1) != N:
+            raise ValueError(f"conv_gemm_desc: wino_pre must be fp32 [36, {NB * th * tw}, {N}] with dense rows (got {tuple(wino_pre.shape)})")
+        d.wino_m, d.wino_zs, d.wino_n, d.wino_th, d.wino_tw = wino_pre.data_ptr(), wino_pre.stride(0), N, th, tw
     return d
+
+
+_FULL_BLOCKS = ShapeCache(8)
+
+
+def full_block_list(B: int, Ho: int, Wo: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(blocks, start) listing EVERY 8 x 8 block of a ``[B, Ho, Wo]`` output grid (``conv_gemm_desc(live=...)``): a dense layer in the
+    block row order, which the Winograd pre-operand needs.  Cached per shape and device (a few page shapes stay resident)."""
+    dev = torch.device(device)
+    bpi = ((Ho + 7) // 8) * ((Wo + 7) // 8)
+
+    def make():
+        return (torch.arange(B * bpi, dtype=torch.int32, device=dev), torch.arange(B + 1, dtype=torch.int32, device=dev) * bpi)
+
+    return _FULL_BLOCKS.get((B, Ho, Wo, str(dev)), make)
 
 
 def launch_conv_gemm(desc: MitConvGemm, cfg: int = -1, stream: Optional[int] = None) -> None:
@@ -433,8 +455,11 @@ class Conv2d:
         return ((H + 2 * self.py - d * (self.kh - 1) - 1) // self.sy + 1, (W + 2 * self.px - d * (self.kw - 1) - 1) // self.sx + 1)
 
     def desc(self, x: torch.Tensor, out: torch.Tensor, pre: Optional[torch.Tensor] = None,
-             post: Optional[torch.Tensor] = None, nprod: int = 0) -> MitConvGemm:
-        """``nprod`` = 1: this launch on the one-product bf16 tiles (MitConvGemm.nprod)."""
+             post: Optional[torch.Tensor] = None, nprod: int = 0, wino_pre: Optional[torch.Tensor] = None,
+             live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> MitConvGemm:
+        """``nprod`` = 1: this launch on the one-product bf16 tiles (MitConvGemm.nprod).  ``wino_pre``: the 36 Winograd products
+        ``[36, T, Cout]`` of a 3x3 convolution over the same output grid, transformed and added in the epilogue in place of ``pre``
+        (``conv_gemm_desc``); the launch then runs in 8 x 8 block order over ``live``, by default every block (``full_block_list``)."""
         _check_nhwc(x, "Conv2d input")
         if nprod:
             ensure_split(self.w)
@@ -452,14 +477,15 @@ class Conv2d:
             a=x, NB=B, Hi=H, Wi=W, Cin=self.Cin, a_strides=(x.stride(0), x.stride(1), x.stride(2)), Ho=Ho, Wo=Wo,
             sy=self.sy, sx=self.sx, taps=self.taps, pad_mode=self.pad_mode, w=self.w, ldw=self.Np, Kw=self.Kp,
             Nw=self.Np, N=self.Cout, c=tensor_map(out), pre=tensor_map(pre), post=tensor_map(post),
-            scale=self.scale, bias=self.bias, act=self.act, alpha=self.alpha, nprod=nprod)
+            scale=self.scale, bias=self.bias, act=self.act, alpha=self.alpha, nprod=nprod, wino_pre=wino_pre,
+            live=full_block_list(B, Ho, Wo, x.device) if wino_pre is not None and live is None else live)
 
     def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None,
-                 post: Optional[torch.Tensor] = None, cfg: int = -1, nprod: int = 0) -> torch.Tensor:
+                 post: Optional[torch.Tensor] = None, cfg: int = -1, nprod: int = 0, wino_pre: Optional[torch.Tensor] = None) -> torch.Tensor:
         if out is None:
             Ho, Wo = self.out_hw(x.shape[1], x.shape[2])
             out = torch.empty(x.shape[0], Ho, Wo, self.Cout, dtype=torch.float32, device=x.device)
-        launch_conv_gemm(self.desc(x, out, pre, post, nprod), cfg)
+        launch_conv_gemm(self.desc(x, out, pre, post, nprod, wino_pre), cfg)
         return out
 
 
@@ -522,6 +548,12 @@ class WinogradConv3x3:
                               pad_mode=PAD_ZERO, w=self.u, ldw=self.Np, Kw=self.Kp, Nw=self.Np, N=self.Cout, c=cm, Z=36,
                               zdiv=1 << 30, a_zs=(0, T * Cv), w_zs=(0, self.Kp * self.Np))
 
+    def products(self, v: torch.Tensor, m: torch.Tensor, cfg: int = -1) -> torch.Tensor:
+        """Only the 36 products, from a ready V into ``m`` [36, T, Cout]: for a consumer that applies the output transform itself
+        (``Conv2d(..., wino_pre=m)``).  Valid for a layer without scale, bias and activation (the transform there applies none)."""
+        launch_conv_gemm(self.gemm_desc(v, m), cfg)
+        return m
+
     def gemm_output(self, v: torch.Tensor, m: torch.Tensor, out: torch.Tensor, post: Optional[torch.Tensor] = None, cfg: int = -1):
         """36 products from a ready V (its first ``Cin`` channels) and the output transform into ``out`` [B,H,W,Cout]."""
         _check_nhwc(out, "WinogradConv3x3 output")
@@ -530,7 +562,7 @@ class WinogradConv3x3:
             raise ValueError(f"WinogradConv3x3: output {tuple(out.shape)} does not match V {tuple(v.shape)}")
         if post is not None and tuple(post.shape) != tuple(out.shape):
             raise ValueError("WinogradConv3x3: residual shape differs from the output")
-        launch_conv_gemm(self.gemm_desc(v, m), cfg)
+        self.products(v, m, cfg)
         ps = (0, 0, 0) if post is None else (post.stride(0), post.stride(1), post.stride(2))
         _lib.check(_lib.load().mit_wino43_output(m.data_ptr(), out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), _ptr(post), *ps,
                                                  _ptr(self.scale), _ptr(self.bias), B, H, W, self.Cout, self.act, self.alpha,
