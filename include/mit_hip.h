@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 22
+#define MIT_ABI_VERSION 23
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -598,6 +598,26 @@ int mit_mc2_ffd_unpack(const uint8_t *img_dev, int B, int H, int W, int Cin, con
 int mit_mc2_gen_in(const uint8_t *plane_dev, int B, int h, int w, float *out_dev, int Hp, int Wp, void *stream);
 /* Generator output (manga_colorization_v2.py:61-74): tanh(pre) * 0.5 + 0.5, crop to h x w, * 255 truncated -> u8 RGB [B,h,w,3]. */
 int mit_mc2_post(const float *pre_dev, int64_t pre_pixstride, int B, int Hp, int Wp, uint8_t *out_dev, int h, int w, void *stream);
+
+/* Text-detection stage (dbconvnext): the norms of DBNet on ConvNeXt ---------------------------
+ * Reference: manga_translator/detection/dbnet_convnext.py (DBNetConvNext :450-491).  The convolutions and both MLP layers run on
+ * mit_conv_gemm; these are the LayerNorms, which the network has where the other detectors have BatchNorm. */
+
+/* nn.LayerNorm over the last dimension of fp32 [rows, D], row strides in floats (input and output may each be a channel slice of
+ * a wider NHWC buffer: a pixel is a row).  timm's LayerNorm2d of the stem (:273), of every stage's downsample.0 (:156) and
+ * LayerNorm of the up-blocks (:103).  D % 4 == 0, D <= 1024, strides multiples of 4, 16-byte aligned operands.  Two passes
+ * (mean, then the centred second moment) in fp32; the order of the sums depends on D alone. */
+int mit_layernorm_rows(const float *in_dev, int64_t in_rowstride, const float *w_dev, const float *b_dev, float *out_dev,
+                       int64_t out_rowstride, int64_t rows, int D, float eps, void *stream);
+/* ConvNeXtBlock.forward up to the MLP for a depthwise block (:114, :119-120): out = LayerNorm_C(dwconv7x7(x) + bdw) * g + b, zero
+ * padding 3, NHWC with pixel strides in floats (x may be a slice of a concat buffer, out a slice or dense); w is [49][C] (tap-major).
+ * C in {128, 256, 512, 1024}; any B, H, W >= 1.  The channel sums are fp32 in an order that depends on C alone, so an image's result
+ * does not depend on the batch it is in.  One pass: a pixel's channels stay in one workgroup. */
+int mit_dwconv7_ln_nhwc(const float *x_dev, int64_t x_pixstride, const float *w_dev, const float *bdw_dev, const float *g_dev,
+                        const float *b_dev, float eps, float *out_dev, int64_t out_pixstride, int B, int H, int W, int C, void *stream);
+/* 1 when the one-pass kernel above is the form to use at width C — it exists for that C and was measured faster there than
+ * mit_dwconv_nhwc followed by mit_layernorm_rows (profiles/r23a_dbconvnext.json) —, else 0: the caller then runs the two launches. */
+int mit_dwconv7_ln_supported(int C);
 
 /* Text-detection stage (ctd): memory-bound pieces and NHWC helpers ---------------------------
  * Reference: manga_translator/detection/ctd.py, ctd_utils/. */

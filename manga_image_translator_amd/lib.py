@@ -9,7 +9,7 @@ import ctypes as C
 from pathlib import Path
 
 MIT_MAX_TAPS = 64
-MIT_ABI_VERSION = 22
+MIT_ABI_VERSION = 23
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SILU, ACT_SIGMOID, ACT_GELU = range(6)
 ACT_POST_FIRST = 0x100
@@ -351,6 +351,11 @@ SYMBOLS = {
                                      C.c_void_p, C.c_void_p]),
     "mit_mc2_gen_in": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "mit_mc2_post": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "mit_layernorm_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float,
+                                     C.c_void_p]),
+    "mit_dwconv7_ln_nhwc": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int64,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "mit_dwconv7_ln_supported": (C.c_int, [C.c_int]),
 }
 
 _lib = None

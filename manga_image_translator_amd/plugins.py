@@ -4,6 +4,7 @@ Each class honours the contract of its reference counterpart:
 
   HipComicTextDetector   <- ComicTextDetector   (/root/reference/manga_translator/detection/ctd.py:60-179)
   HipDefaultDetector     <- DefaultDetector     (detection/default.py:27-103)
+  HipDBConvNextDetector  <- DBConvNextDetector  (detection/dbnet_convnext.py:512-588)
   HipModel48pxOCR        <- Model48pxOCR        (ocr/model_48px.py:25-180)
   HipModel48pxCTCOCR     <- Model48pxCTCOCR     (ocr/model_48px_ctc.py:30-160)
   HipModel32pxOCR        <- Model32pxOCR        (ocr/model_32px.py:19-140)
@@ -347,6 +348,45 @@ class HipDefaultDetector(_EnginePlugin, _DetBase):
         elif pad_w > 0:
             mask_resized = mask_resized[:, :-pad_w]
         return textlines, np.clip(mask_resized * 255, 0, 255).astype(np.uint8), None
+
+
+class HipDBConvNextDetector(HipDefaultDetector):
+    """``--detector dbconvnext`` (DBNet on ConvNeXt) on the HIP engine.  ``DBConvNextDetector._infer`` (detection/dbnet_convnext.py:541-588)
+    is ``DefaultDetector._infer`` line for line, so only the network behind it differs: ``_infer`` is inherited."""
+    _KEY = _key = "dbconvnext_hip"
+    CKPT = "dbnet_convnext.ckpt"
+    _MODEL_MAPPING: Dict = {  # detection/dbnet_convnext.py:513-519: nothing to download, the file is expected beside the program
+        "model": {
+            "url": "",
+            "hash": "",
+            "file": ".",
+        },
+    }
+
+    def __init__(self, *args, **kwargs):
+        import shutil
+
+        if os.path.exists(self.CKPT):                       # :522-524: a checkpoint in the working directory moves to the model directory
+            os.makedirs(self.model_dir, exist_ok=True)
+            shutil.move(self.CKPT, self._get_file_path(self.CKPT))
+        super().__init__(*args, **kwargs)
+
+    def _check_for_malformed_model_mapping(self):
+        """The reference's mapping has an empty URL — the user supplies the file — which ModelWrapper's check (utils/inference.py:129-134)
+        refuses, so the reference's own class cannot be constructed over it.  Nothing is ever downloaded for this model: nothing to check."""
+
+    def _check_downloaded(self) -> bool:
+        return os.path.exists(self._get_file_path(self.CKPT))
+
+    async def _load(self, device: str):
+        from . import dbconvnext
+
+        dev = _gpu_device(device)
+        sd = self._weights
+        if sd is None:
+            sd = _load_dbconvnext_checkpoint(self)
+        self.engine = dbconvnext.DbconvnextEngine(sd, device=dev)
+        self.device = device
 
 
 class HipModel48pxOCR(_EnginePlugin, _OcrBase):
@@ -1038,6 +1078,17 @@ def _load_aot_checkpoint(plugin):
     return {"aot": synth.check_state_dict(sd, aot_schema.aot_generator_schema(), plugin.CKPT)}
 
 
+def _load_dbconvnext_checkpoint(plugin):
+    """dbnet_convnext.ckpt: {'model': state_dict} or a bare state_dict (detection/dbnet_convnext.py:529-530), schema-checked.  The 1x1
+    shortcut of an up-block may come without its bias (whether timm's ``create_conv2d`` gives it one depends on the timm release the
+    checkpoint was trained with; the engine takes either)."""
+    from . import dbconvnext_schema, synth
+
+    sd = _bare_state_dict(torch.load(_ckpt_path(plugin, plugin.CKPT), map_location="cpu"))
+    schema = [e for e in dbconvnext_schema.dbnet_convnext_schema() if e[0] in sd or not e[0].endswith(".shortcut.conv.bias")]
+    return synth.check_state_dict(sd, schema, plugin.CKPT)
+
+
 def _load_esrgan_checkpoint(plugin):
     """4xESRGAN.pth: a bare RRDBNet state_dict; the block count comes from its keys (esrgan_pytorch.py:526-528, infer_params :476-510)."""
     from . import esrgan_schema, synth
@@ -1080,6 +1131,7 @@ def register() -> None:
             return value
 
     for reg, enum_name, cls in ((DETECTORS, "Detector", HipComicTextDetector), (DETECTORS, "Detector", HipDefaultDetector),
+                                (DETECTORS, "Detector", HipDBConvNextDetector),
                                 (OCRS, "Ocr", HipModel48pxOCR), (OCRS, "Ocr", HipModel48pxCTCOCR),
                                 (OCRS, "Ocr", HipModel32pxOCR),
                                 (INPAINTERS, "Inpainter", HipLamaMPEInpainter), (INPAINTERS, "Inpainter", HipLamaLargeInpainter),
