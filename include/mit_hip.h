@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 23
+#define MIT_ABI_VERSION 24
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -283,6 +283,21 @@ int mit_join_planes(const uint16_t *planes_dev, int64_t ld, int R, int K, float 
 int mit_conv_small_cout(const float *in_dev, int64_t in_pixstride, int64_t in_planestride, const float *w4_dev, const float *w_pairs_dev, const float *bias_dev, float *out_dev,
                         int64_t out_pixstride, int B, int H, int W, int Cin, int Cout, int k, int pad_mode, int act,
                         float act_alpha, const uint8_t *live_cells, void *stream);
+
+/* ConvTranspose2d(Cin -> 1, stride 2) (+ scale, bias, activation) in ONE pass over the input and over a given output extent only
+ * (ABI 24; csrc/convt_cout1.hip).  Two forms, anything else is refused: k4 s2 p1 at Cin = 64 (`upconv6`, ctd_utils/basemodel.py:20) and
+ * k2 s2 p0 at Cin = 16 (the last layer of both DB branches, basemodel.py:93,96).
+ *   x:    [B][Hi][Wi][Cin] fp32 with strides x_bs / x_ys / x_xs floats (each a multiple of 4; channel stride 1), 16-byte aligned
+ *   w:    [Cin][1][k][k] as the layer holds it, 16-byte aligned;  scale / bias: one float each, or NULL (1 / 0)
+ *   out:  a one-channel map with strides out_bs / out_ys / out_xs floats; the layer's output is 2 Hi x 2 Wi, and only rows < out_h and
+ *         columns < out_w of it are computed and written (the rest of `out` is left as it is)
+ * Bit-identical to the four parity launches of mit_conv_gemm on its N <= 4 kernel (same lane partition of the channels, tap order,
+ * shuffle tree and epilogue).  A workgroup owns MIT_CONVT_COUT1_STRIP_K4 / _K2 columns of input positions. */
+#define MIT_CONVT_COUT1_STRIP_K4 16
+#define MIT_CONVT_COUT1_STRIP_K2 64
+int mit_convt_cout1(const float *x_dev, int64_t x_bs, int64_t x_ys, int64_t x_xs, int B, int Hi, int Wi, int Cin, const float *w_dev, int k,
+                    int stride, int pad, const float *scale_dev, const float *bias_dev, int act, float act_alpha, float *out_dev,
+                    int64_t out_bs, int64_t out_ys, int64_t out_xs, int out_h, int out_w, void *stream);
 
 /* Which parts of LaMa's decoder tail a composite reads (lama_post takes the prediction only where mask >= 127): from mask [B][H][W] u8
  * (H, W multiples of 8), on `stream`, with no allocation, synchronisation or copy to the host,

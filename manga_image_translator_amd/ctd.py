@@ -9,7 +9,9 @@ are not executed (and not counted in the FLOP figure).
 Layout: fp32 NHWC; every torch.cat of the reference is a pre-allocated buffer whose channel slices
 the producers write directly (C3's cat, SPPF's cat, the U-Net skips); BatchNorm / LeakyReLU /
 SiLU / ReLU / sigmoid / residual adds live in the conv epilogues; ConvTranspose2d runs as four
-sub-pixel convolutions writing strided views.
+sub-pixel convolutions writing strided views, except the three 1-channel layers at the end of the
+heads: those read their input once (``mit_convt_cout1``) and, with the DB branches' layers before
+them, compute only the un-padded part of the letterbox (``head_extents``).
 """
 from __future__ import annotations
 
@@ -45,6 +47,17 @@ def _head_conv(sd, p, k, device):
                       device=device)
 
 
+def head_extents(hv: int, wv: int, S: int = INPUT_SIZE) -> Tuple[Tuple[int, int], Tuple[int, int], Tuple[int, int]]:
+    """What the last layers of both heads have to read so that rows ``< hv`` and columns ``< wv`` of ``mask`` and ``lines`` are
+    right: -> ((rows, cols) of ``u320``, of ``db1``, of ``db0``).  The layers are local: an output index ``< n`` of a k2 s2
+    transposed convolution reads input indices ``< ceil(n / 2)``, of the k4 s2 p1 one indices ``<= ceil(n / 2)``."""
+    half = lambda n: (n + 1) // 2
+    b1 = (half(hv), half(wv))                                        # t2 (16 -> 1, k2 s2) reads db1
+    b0 = (half(b1[0]), half(b1[1]))                                  # t1 (16 -> 16, k2 s2) reads db0, which c0 writes
+    u = (min(S // 2, b1[0] + 1), min(S // 2, b1[1] + 1))             # up6 (64 -> 1, k4 s2 p1) reads u320
+    return u, b1, b0
+
+
 class _C3:
     """C3 (common.py:126-136) with n Bottlenecks (e=1.0, shortcut as given)."""
 
@@ -72,9 +85,12 @@ class CtdEngine(ops.Engine):
     """Batched text-detection network: u8 pages -> (mask u8, lines fp32) on the device."""
 
     def __init__(self, yolo_sd: Dict[str, torch.Tensor], seg_sd: Dict[str, torch.Tensor], det_sd: Dict[str, torch.Tensor],
-                 device="cuda"):
+                 device="cuda", fused_heads: bool = True):
+        """``fused_heads=False``: the 1-channel transposed convolutions as four parity launches each and the DB branches over the whole
+        letterbox square, padding included (the form before ``mit_convt_cout1``; same bits in the un-padded region)."""
         super().__init__(device)
         dev = self.device
+        self.fused_heads = bool(fused_heads)
         ymk = lambda k_s: (lambda p, k: _fused_yolo_conv(yolo_sd, p, k, k_s, dev))
         y1 = lambda p, k: _fused_yolo_conv(yolo_sd, p, k, 1, dev)
         self.y0 = _fused_yolo_conv(yolo_sd, "model.0", 6, 2, dev)
@@ -233,8 +249,14 @@ class CtdEngine(ops.Engine):
         self._up(self.up4, cat80, cat160[..., 64:], "up4")  # u160 -> cat160
         u320 = self._buf("u320", B, 512, 512, 64)
         self._up(self.up5, cat160, u320, "up5")
+        # the un-padded part of the letterbox square: with fused_heads nothing beyond it is computed by the layers below, and the
+        # rest of mask / mask_u8 / lines is stale workspace
+        hv, wv = S - dh, S - dw
         mask = self._buf("mask", B, S, S, 1)
-        self.up6(u320, out=mask)
+        if self.fused_heads:
+            self.up6.single_pass(u320, mask, hv, wv)
+        else:
+            self.up6(u320, out=mask)
         # ---- DBHead (basemodel.py:100-119) ----
         dcat80 = self._buf("dcat80", B, 128, 128, 384)  # [f80 | u80'] with DBHead's own upconv3
         _lib.check(lib.mit_copy_channels(f80.data_ptr(), 384, dcat80.data_ptr(), 384, B * 128 * 128, 128, st), "mit_copy_channels")
@@ -246,16 +268,24 @@ class CtdEngine(ops.Engine):
         lines = self._buf("lines", B, 2, S, S)
         for plane, (c0, t1, t2) in ((0, self.br_binarize), (1, self.br_thresh)):  # cat((shrink, threshold)) :119
             b0 = self._buf("db0", B, 256, 256, 16)
-            c0(dc, out=b0)
             b1 = self._buf("db1", B, 512, 512, 16)
-            t1(b0, out=b1)
-            t2(b1, out=lines[:, plane].unsqueeze(-1))
+            if self.fused_heads:
+                _, _, (h0, w0) = head_extents(hv, wv, S)
+                b0v = b0[:, :h0, :w0]
+                c0(dc, out=b0v, out_hw=(h0, w0))          # dc stays whole: the last row's / column's taps read real pixels
+                t1(b0v, out=b1[:, :2 * h0, :2 * w0])
+                t2.single_pass(b1, lines[:, plane].unsqueeze(-1), hv, wv)
+            else:
+                c0(dc, out=b0)
+                t1(b0, out=b1)
+                t2(b1, out=lines[:, plane].unsqueeze(-1))
         mask_u8 = self._buf("mask_u8", B, S, S, dtype=torch.uint8)
         _lib.check(lib.mit_map_to_u8(mask.data_ptr(), mask_u8.data_ptr(), B * S * S, 0, 0.0, st), "mit_map_to_u8")
         if taps is not None:
             taps["mask_f32"] = mask.clone()
-        self.last_mask_f32 = mask[..., 0]  # [B,S,S] view of the workspace, valid until the next forward (the tiled path averages floats)
-        return mask_u8[:, :S - dh, :S - dw], lines[:, :, :S - dh, :S - dw], (dw, dh)
+        # [B,S-dh,S-dw] view of the workspace, valid until the next forward (the tiled path averages floats; its squares have no padding)
+        self.last_mask_f32 = mask[:, :hv, :wv, 0]
+        return mask_u8[:, :hv, :wv], lines[:, :, :hv, :wv], (dw, dh)
 
     def shrink_bitmap(self, lines: torch.Tensor, thr: float = 0.3) -> torch.Tensor:
         """SegDetectorRepresenter.binarize (db_utils.py:75): pred[:, 0] > thresh, as u8 on the device."""

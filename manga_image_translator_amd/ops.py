@@ -456,8 +456,10 @@ class Conv2d:
 
     def desc(self, x: torch.Tensor, out: torch.Tensor, pre: Optional[torch.Tensor] = None,
              post: Optional[torch.Tensor] = None, nprod: int = 0, wino_pre: Optional[torch.Tensor] = None,
-             live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> MitConvGemm:
-        """``nprod`` = 1: this launch on the one-product bf16 tiles (MitConvGemm.nprod).  ``wino_pre``: the 36 Winograd products
+             live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out_hw: Optional[Tuple[int, int]] = None) -> MitConvGemm:
+        """``out_hw`` = (h, w): only the top-left h x w of the layer's output is computed and ``out`` is that view; ``x`` stays whole, so
+        the taps of the last row and column read the real neighbours, not padding.
+        ``nprod`` = 1: this launch on the one-product bf16 tiles (MitConvGemm.nprod).  ``wino_pre``: the 36 Winograd products
         ``[36, T, Cout]`` of a 3x3 convolution over the same output grid, transformed and added in the epilogue in place of ``pre``
         (``conv_gemm_desc``); the launch then runs in 8 x 8 block order over ``live``, by default every block (``full_block_list``)."""
         _check_nhwc(x, "Conv2d input")
@@ -468,6 +470,10 @@ class Conv2d:
         if Cx != self.Cin:
             raise ValueError(f"Conv2d: input has {Cx} channels, layer expects {self.Cin}")
         Ho, Wo = self.out_hw(H, W)
+        if out_hw is not None:
+            if not (0 < out_hw[0] <= Ho and 0 < out_hw[1] <= Wo):
+                raise ValueError(f"Conv2d: out_hw {tuple(out_hw)} is not inside the output {(Ho, Wo)}")
+            Ho, Wo = out_hw
         if tuple(out.shape) != (B, Ho, Wo, self.Cout):
             raise ValueError(f"Conv2d: output shape {tuple(out.shape)} != {(B, Ho, Wo, self.Cout)}")
         for t, nm in ((pre, "pre"), (post, "post")):
@@ -481,11 +487,12 @@ class Conv2d:
             live=full_block_list(B, Ho, Wo, x.device) if wino_pre is not None and live is None else live)
 
     def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, pre: Optional[torch.Tensor] = None,
-                 post: Optional[torch.Tensor] = None, cfg: int = -1, nprod: int = 0, wino_pre: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 post: Optional[torch.Tensor] = None, cfg: int = -1, nprod: int = 0, wino_pre: Optional[torch.Tensor] = None,
+                 out_hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         if out is None:
-            Ho, Wo = self.out_hw(x.shape[1], x.shape[2])
+            Ho, Wo = self.out_hw(x.shape[1], x.shape[2]) if out_hw is None else out_hw
             out = torch.empty(x.shape[0], Ho, Wo, self.Cout, dtype=torch.float32, device=x.device)
-        launch_conv_gemm(self.desc(x, out, pre, post, nprod, wino_pre), cfg)
+        launch_conv_gemm(self.desc(x, out, pre, post, nprod, wino_pre, out_hw=out_hw), cfg)
         return out
 
 
@@ -731,9 +738,31 @@ class ConvTranspose2d:
             bias_t = bias.detach().to(torch.float32)
         self.scale = None if scale is None else scale.to(device).contiguous()
         self.bias = None if bias_t is None else bias_t.to(device).contiguous()
+        # the forms mit_convt_cout1 takes (one pass over the input for all four parities): the weight as the layer holds it
+        self.one_pass = Cout == 1 and stride == 2 and output_padding == 0 and (kh, kw, padding, Cin) in ((4, 4, 1, 64), (2, 2, 0, 16))
+        self.w_raw = w.to(device).contiguous() if self.one_pass else None
 
     def out_hw(self, H: int, W: int) -> Tuple[int, int]:
         return ((H - 1) * self.s - 2 * self.p + self.k[0] + self.op, (W - 1) * self.s - 2 * self.p + self.k[1] + self.op)
+
+    def single_pass(self, x: torch.Tensor, out: torch.Tensor, out_h: Optional[int] = None, out_w: Optional[int] = None) -> torch.Tensor:
+        """The layer through ``mit_convt_cout1`` (``self.one_pass`` layers only): every input line is read once, and only rows
+        ``< out_h`` / columns ``< out_w`` of ``out`` [B, 2H, 2W, 1] (any strides) are computed and written.  Same bits as
+        ``__call__`` inside that extent."""
+        if not self.one_pass:
+            raise ValueError("ConvTranspose2d.single_pass: only Cout = 1 layers of k4 s2 p1 (Cin 64) or k2 s2 (Cin 16)")
+        _check_nhwc(x, "ConvTranspose2d input")
+        B, H, W, Cx = x.shape
+        if Cx != self.Cin or tuple(out.shape) != (B, 2 * H, 2 * W, 1):
+            raise ValueError(f"ConvTranspose2d.single_pass: bad shapes {tuple(x.shape)} -> {tuple(out.shape)}")
+        if out.dtype != torch.float32 or out.device != x.device:
+            raise ValueError("ConvTranspose2d.single_pass: fp32 output on the input's device required")
+        out_h, out_w = 2 * H if out_h is None else out_h, 2 * W if out_w is None else out_w
+        _lib.check(_lib.load().mit_convt_cout1(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), B, H, W, self.Cin, self.w_raw.data_ptr(),
+                                               self.k[0], self.s, self.p, _ptr(self.scale), _ptr(self.bias), self.act, self.alpha,
+                                               out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), out_h, out_w,
+                                               C.c_void_p(current_stream())), "mit_convt_cout1")
+        return out
 
     def descs(self, x: torch.Tensor, out: torch.Tensor, planes: int = 0, parity_major: bool = False, nprod: int = 0,
               live: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> List[MitConvGemm]:
