@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 24
+#define MIT_ABI_VERSION 25
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -402,6 +402,29 @@ int mit_bilateral_u8c3(const uint8_t *src_dev, uint8_t *dst_dev, int B, int H, i
  * original mask thresholded at 127 (inpainting_lama_mpe.py:57-61,116). */
 int mit_select_u8(const uint8_t *mask_dev, int thr, const uint8_t *a_dev, const uint8_t *b_dev, uint8_t *out_dev, int64_t npix, int C,
                   void *stream);
+
+/* Webtoon strips: det_rearrange_forward's tiling around the detector network, on the device (ABI 25) ----------------------
+ * Reference: utils/generic.py:876-997 (called from detection/ctd.py:137 and detection/default.py:60).  The plan (transpose, w, pw_num,
+ * ph_num, ph_step, p_num; patch = pw_num * w) is rearrange.plan()'s restatement of :940-975.
+ *
+ * mit_rearrange_squares — the einops rearranges of :920-924 before square_pad_resize (:849-874): u8 page [H,W,3] -> the unshrunk squares
+ * u8 [p_num, patch, patch, 3], band b = s * pw_num + j of square s cut at strip row b * ph_step:
+ *   plain plan      sq[s][r][j*w + c]  = page[b*ph_step + r][c]        (w = W, strip length H)
+ *   transposed plan sq[s][j*w + a][r]  = page[a][b*ph_step + r]        (w = H, strip length W: the wide strip's band^T)
+ * Bands >= ph_num of the last square are zero.  The INTER_LINEAR shrink to the detect size (:871-872) is mit_resize_u8 on the result. */
+int mit_rearrange_squares(const uint8_t *page_dev, int H, int W, int transpose, int w, int pw_num, int ph_num, int ph_step, int p_num,
+                          uint8_t *sq_dev, void *stream);
+/* mit_rearrange_stitch — _unrearrange (utils/generic.py:891-918): the network's output squares f32 [n, C, m, m] with element strides
+ * (sn, sc, sy, sx) (a view of an engine's workspace as it is) -> the strip's map f32 [C, hh, pw] (transposed plan: [C, pw, hh]), dense.
+ * step = int(ph_step * m / patch), pw = int(m / pw_num), hh = int(pw / w * h) and starts_dev (int32 [ph_num], non-decreasing: band p
+ * starts at int(round(rel_step[p] * hh)), :904) come from the host.  Per element (c, y along the strip, x across it), in float32:
+ *   v = 0;  for p = 0 .. ph_num-1:   t = starts[p]
+ *     if t <= y < min(t + m, hh):        v = v + src[p / pw_num][c][y - t][(p % pw_num) * pw + x]     (transposed plan: [..x][y - t])
+ *     if p > 0 and t <= y < t + m - step: v = v * 0.5f                                                    (:909-911, the running average)
+ * which is the reference's band-by-band accumulation restated per element: bit-identical.  ops = 1 also writes dst_u8_dev (same shape):
+ * (uint8)(v * 255.0f), truncating — postprocess_mask of the ctd detector (detection/ctd.py:41-44).  ops = 0: dst_u8_dev may be NULL. */
+int mit_rearrange_stitch(const float *src_dev, int n, int C, int m, int64_t sn, int64_t sc, int64_t sy, int64_t sx, int transpose, int pw_num,
+                         int ph_num, int step, int pw, int hh, const int *starts_dev, float *dst_dev, uint8_t *dst_u8_dev, int ops, void *stream);
 
 /* ctd detector: refine_mask on the GPU ------------------------------------------------------------
  * Reference: manga_translator/detection/ctd_utils/textmask.py:158-174 (refine_mask; :29-132 its helpers), called from

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ctd, hostglue, imgproc, lama, mask_refinement as MR, ocr48, textline_merge as TM
+from . import ctd, hostglue, imgproc, lama, mask_refinement as MR, ocr48, rearrange, textline_merge as TM
 from .textline import Quadrilateral
 
 BOX_THRESH = 0.6          # ctd.py:157-159
@@ -81,6 +81,8 @@ _STAGE_OF = {"detect+boxes+refine_mask": "det", "ocr": "ocr", "textline_merge+ma
 class CoupledPageEngine:
     """Owns the stage engines of one GPU and a host thread pool."""
 
+    takes_strips = True   # detect() has det_rearrange_forward's branch: a batch of equal webtoon strips is one coupled run (serve.py)
+
     def __init__(self, weights: Dict[str, Dict[str, torch.Tensor]], dictionary: Sequence[str], device="cuda", lama_blocks: int = 9,
                  ctd_mb: int = 16, lama_mb: int = 16, host_workers: int = 16, mask_workers: int = 4, side_stream: Optional[bool] = None):
         self.device = torch.device(device)
@@ -128,19 +130,27 @@ class CoupledPageEngine:
     # ---- stage 1: detector network + boxes (host pool) + mask resize + refine_mask ------------------------------------------
     @torch.no_grad()
     def detect(self, pages_u8: torch.Tensor, inject=None):
-        """-> (textlines per page, refined mask u8 [B,H,W] on the device): ComicTextDetector._infer (ctd.py:129-179) for a batch."""
+        """-> (textlines per page, refined mask u8 [B,H,W] on the device): ComicTextDetector._infer (ctd.py:129-179) for a batch.
+
+        Webtoon strips (``rearrange.plan(H, W, 1024)`` is not None) take det_rearrange_forward's branch (ctd.py:137) like the plugin
+        does, on the device: see ``_detect_strips``.  ``inject`` on a strip holds maps of the STITCHED geometry: ``prob`` f32
+        [B, hh, pw] and ``mask`` u8 [B, hh, pw] ([B, pw, hh] for a wide strip), ``(step, pw, hh, _) = rearrange.stitch_geometry(plan, 1024)``."""
         B, H, W, _ = pages_u8.shape
         mask_full = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
         keep = []
-        for i in range(0, B, self.ctd_mb):
-            j = min(B, i + self.ctd_mb)
-            mask_u8, lines, _ = self.ctd.forward(pages_u8[i:j])
-            if inject is not None:   # benchmark stand-in for trained weights: the maps a trained head would emit REPLACE the random-init
-                lines[:, 0] = inject["prob"][i:j]     # network's (its sigmoid output hovers around 0.5 everywhere: one page-sized blob);
-                mask_u8 = inject["mask"][i:j]         # the network has run in full by now, its cost is in the measurement
-            # SegDetectorRepresenter (db_utils.py:40-216) where the map is (csrc/ctd_boxes.hip): enqueued behind the network, collected below
-            keep.append((i, j, hostglue.boxes_from_bitmap_gpu_launch(lines[:, 0], 0.3, W, H, unclip_ratio=1.5, min_sside=2.0)))
-            mask_full[i:j] = imgproc.resize_u8(mask_u8.contiguous(), (W, H))      # cv2.resize(mask, (w, h), INTER_LINEAR) (ctd.py:162)
+        pl = rearrange.plan(H, W, ctd.INPUT_SIZE)
+        if pl is not None:
+            keep.append((0, B, self._detect_strips(pages_u8, pl, inject, mask_full)))
+        else:
+            for i in range(0, B, self.ctd_mb):
+                j = min(B, i + self.ctd_mb)
+                mask_u8, lines, _ = self.ctd.forward(pages_u8[i:j])
+                if inject is not None:   # benchmark stand-in for trained weights: the maps a trained head would emit REPLACE the random-init
+                    lines[:, 0] = inject["prob"][i:j]     # network's (its sigmoid output hovers around 0.5 everywhere: one page-sized blob);
+                    mask_u8 = inject["mask"][i:j]         # the network has run in full by now, its cost is in the measurement
+                # SegDetectorRepresenter (db_utils.py:40-216) where the map is (csrc/ctd_boxes.hip): enqueued behind the network, collected below
+                keep.append((i, j, hostglue.boxes_from_bitmap_gpu_launch(lines[:, 0], 0.3, W, H, unclip_ratio=1.5, min_sside=2.0)))
+                mask_full[i:j] = imgproc.resize_u8(mask_u8.contiguous(), (W, H))      # cv2.resize(mask, (w, h), INTER_LINEAR) (ctd.py:162)
         textlines = [None] * B
         for i, j, h in keep:
             for b, (boxes, scores) in zip(range(i, j), hostglue.boxes_from_bitmap_gpu_collect(h)):
@@ -162,6 +172,33 @@ class CoupledPageEngine:
         # for the whole queue): no table keyed by address that a failed stage could leave behind for an unrelated tensor to inherit
         refined.mit_ready_event = torch.cuda.current_stream().record_event()
         return textlines, refined
+
+    def _detect_strips(self, pages_u8: torch.Tensor, pl, inject, mask_full: torch.Tensor):
+        """The network part of ``detect`` for a batch of equal webtoon strips, det_rearrange_forward (utils/generic.py:876-997) on the
+        device: the squares of all pages (``rearrange.squares_gpu``) go through the network in micro-batches of ``ctd_mb`` — more than the
+        reference's four at a time, which changes nothing because the engine's results do not depend on the batch size — each page's
+        maps are stitched (``rearrange.stitch_gpu``), the box extraction is enqueued on the stitched maps and the stitched u8 mask is
+        resized into ``mask_full``.  -> the handle of the enqueued box extraction."""
+        B, H, W, _ = pages_u8.shape
+        S = ctd.INPUT_SIZE
+        sq = torch.cat([rearrange.squares_gpu(pages_u8[b], pl, S) for b in range(B)])
+        n = sq.shape[0]
+        lines_sq = torch.empty(n, 2, S, S, dtype=torch.float32, device=self.device)    # the engine's outputs are workspace views that
+        mask_sq = torch.empty(n, S, S, dtype=torch.float32, device=self.device)        # the next micro-batch overwrites
+        for i in range(0, n, self.ctd_mb):
+            _, lines, _ = self.ctd.forward(sq[i:i + self.ctd_mb])
+            lines_sq[i:i + self.ctd_mb] = lines
+            mask_sq[i:i + self.ctd_mb] = self.ctd.last_mask_f32
+        prob, mask_u8 = [], []
+        for b in range(B):
+            prob.append(rearrange.stitch_gpu(lines_sq[b * pl.p_num:(b + 1) * pl.p_num], pl)[0, 0])
+            mask_u8.append(rearrange.stitch_gpu(mask_sq[b * pl.p_num:(b + 1) * pl.p_num], pl, u8=True)[1][0, 0])   # postprocess_mask (ctd.py:155)
+        prob, mask_u8 = torch.stack(prob), torch.stack(mask_u8)
+        if inject is not None:   # see detect: the stand-in for trained weights, here at the stitched size
+            prob, mask_u8 = inject["prob"], inject["mask"]
+        h = hostglue.boxes_from_bitmap_gpu_launch(prob, 0.3, W, H, unclip_ratio=1.5, min_sside=2.0)
+        mask_full[:] = imgproc.resize_u8(mask_u8.contiguous(), (W, H))
+        return h
 
     # ---- stage 2: OCR ---------------------------------------------------------------------------------------------------
     @torch.no_grad()

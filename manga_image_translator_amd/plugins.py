@@ -230,7 +230,17 @@ class HipComicTextDetector(_EnginePlugin, _DetBase):
         from . import hostglue, imgproc, rearrange
 
         S = self.input_size[0]
-        if rearrange.plan(im_h, im_w, S) is not None:    # webtoon strip: det_rearrange_forward (ctd.py:137, generic.py:876-997)
+        strip = rearrange.plan(im_h, im_w, S) is not None    # webtoon strip: det_rearrange_forward (ctd.py:137, generic.py:876-997)
+        if strip and self._boxes is None and self._refine is None and torch.device(self.engine.device).type == "cuda":
+            # nothing injected: bands, squares, network, stitch and postprocess_mask (:155) stay on the device (csrc/rearrange.hip); the
+            # stitched maps then go the whole page's way below, so only the boxes and the final mask cross PCIe
+            def net(squares):  # det_batch_forward_ctd (ctd.py:106-127): at S x S the engine's letterbox is the identity
+                _, sq_lines, _ = self.engine.forward(squares)
+                return sq_lines, self.engine.last_mask_f32
+
+            lines, (_, mask_u8) = rearrange.forward_gpu(page[0], net, S, mask_u8=True)
+            mask_u8, lines_map = mask_u8[0], None
+        elif strip:
             lines_map, mask_f = rearrange.forward(image, self._tiles_forward, S)
             mask_u8 = torch.from_numpy((mask_f.squeeze() * 255).astype(np.uint8)).to(self.engine.device)[None]  # postprocess_mask (:155)
         else:
@@ -239,7 +249,7 @@ class HipComicTextDetector(_EnginePlugin, _DetBase):
         if self._refine is None:                         # cv2.resize(mask, (w, h), INTER_LINEAR) (:162) on the GPU as well
             mask_full = imgproc.resize_u8(mask_u8[:1].contiguous(), (im_w, im_h))[0]
         # SegDetectorRepresenter(thresh=0.3) (:102,156): on the GPU where the map already is (csrc/ctd_boxes.hip: only the boxes cross
-        # PCIe); an injected extractor, or a rearranged strip whose stitched map was assembled on the host, takes the numpy map
+        # PCIe); an injected extractor, or a rearranged strip whose stitched map was assembled on the host (see above), takes the numpy map
         if self._boxes is None and lines_map is None and lines.is_cuda:   # (a map that lives on the host — an injected stand-in engine,
             # tests/boundary_checks.py — goes to the host routine as well)
             boxes, scores = hostglue.ctd_boxes_gpu(lines, im_h, im_w)[0]
@@ -306,7 +316,18 @@ class HipDefaultDetector(_EnginePlugin, _DetBase):
 
         boxes_fn = self._boxes or _native_dbnet_boxes
         resize2x = self._resize2x or (lambda m: _resize2x_f32(m))
-        if rearrange.plan(image.shape[0], image.shape[1], detect_size) is not None:  # webtoon strip (default.py:60, generic.py:876-997)
+        strip = rearrange.plan(image.shape[0], image.shape[1], detect_size) is not None  # webtoon strip (default.py:60, generic.py:876-997)
+        if strip and self._boxes is None and self._pre is None and torch.device(self.engine.device).type == "cuda":
+            # nothing injected: bands, squares, network and stitch on the device (csrc/rearrange.hip), the boxes extracted where the
+            # stitched map is; the stitched float mask comes down once for the host x2 resize below
+            from . import hostglue
+
+            db, mask4 = rearrange.forward_gpu(self._page_on_device(image)[0], self.engine.forward, detect_size)
+            mask = mask4[0, 0].cpu().numpy()
+            h, w = image.shape[:2]
+            ratio, pad_w, pad_h = 1.0, 0, 0
+            boxes_fn = lambda d, hh, ww, tt, bt, ur: hostglue.dbnet_boxes_gpu(d, hh, ww, tt, bt, ur)[0]   # noqa: E731
+        elif strip:
             def tiles(squares):  # det_batch_forward_default (:15-25): x / 127.5 - 1 happens inside the engine
                 t = torch.from_numpy(np.ascontiguousarray(squares)).to(self.engine.device)
                 if t.shape[1] != detect_size:

@@ -11,6 +11,10 @@ This module re-derives that geometry once (``plan``) and applies it in two vecto
 stitch (accumulate, halve the overlap of every band after the first) is kept in float32 numpy in the reference's order, so the
 stitched maps are bit-identical to the reference's for the same network output (tests/golden/rearrange.npz pins that against the
 reference function itself, with a deterministic stand-in for the network).
+
+``squares_gpu`` / ``stitch_gpu`` / ``forward_gpu`` are the same two passes with the page and the maps on the device
+(csrc/rearrange.hip): the plan and the band starts still come from here, the stitch replays the same accumulation per output element
+and gives the same bits (tests/test_rearrange_gpu.py).
 """
 from __future__ import annotations
 
@@ -85,15 +89,23 @@ def squares(img: np.ndarray, pl: Plan, tgt_size: int, resize: Optional[Callable[
     return np.stack(out), int(pad_size)
 
 
+def stitch_geometry(pl: Plan, psize: int) -> Tuple[int, int, int, List[int]]:
+    """(step, pw, hh, starts) of the stitched map for network output squares of side ``psize`` (generic.py:892-895,904): the band
+    pitch and the band width in map pixels, the map's length along the strip, and the row every band starts at.  ``stitch`` and
+    ``stitch_gpu`` both take their geometry from here (``round`` is Python's, so the starts are computed on the host for both)."""
+    step = int(pl.ph_step * psize / pl.patch)
+    pw = int(psize / pl.pw_num)
+    hh = int(pw / pl.w * pl.h)
+    return step, pw, hh, [int(round(pl.rel_steps[p] * hh)) for p in range(pl.ph_num)]
+
+
 def stitch(maps: Sequence[np.ndarray], pl: Plan, channel: int) -> np.ndarray:
     """Network output squares [c, s, s] (already cropped of the padding) -> the strip's map [1, c, H', W'] (float32).
 
     Every band is added at its relative position; from the second band on, the rows it shares with its predecessor (the first
     ``s - step`` rows of the band) are halved after the add — the reference's running average (generic.py:897-916)."""
     psize = maps[0].shape[-1]
-    step = int(pl.ph_step * psize / pl.patch)
-    pw = int(psize / pl.pw_num)
-    hh = int(pw / pl.w * pl.h)
+    step, pw, hh, starts = stitch_geometry(pl, psize)
     tgt = np.zeros((channel, hh, pw), dtype=np.float32)
     last = len(maps) * pl.pw_num - pl.pad_num - 1
     done = False
@@ -104,7 +116,7 @@ def stitch(maps: Sequence[np.ndarray], pl: Plan, channel: int) -> np.ndarray:
             p = np.transpose(p, (0, 2, 1))
         for jj in range(pl.pw_num):
             pidx = ii * pl.pw_num + jj
-            t = int(round(pl.rel_steps[pidx] * hh))
+            t = starts[pidx]
             b = min(t + psize, hh)
             tgt[..., t:b, :] += p[..., :b - t, jj * pw:(jj + 1) * pw]
             if pidx > 0:
@@ -136,3 +148,88 @@ def forward(img: np.ndarray, batch_forward: Callable[[np.ndarray], Tuple[np.ndar
             dbs.append(d)
             masks.append(m)
     return stitch(dbs, pl, 2), stitch(masks, pl, 1)
+
+
+# ---- the same tiling with the page and the maps on the device (csrc/rearrange.hip) ---------------------------------------------
+
+def squares_gpu(page_dev, pl: Plan, tgt_size: int):
+    """``squares`` on the device: u8 page [H,W,3] (device) -> u8 [p_num, tgt, tgt, 3]: the band gather (``mit_rearrange_squares``) and
+    square_pad_resize's INTER_LINEAR shrink (``imgproc.resize_u8``).  Every plan of ``plan()`` has ``patch > tgt_size`` (for
+    w <= tgt, patch = floor(2 tgt / w) w > 2 tgt - w >= tgt; else patch = 2 w > 2 tgt), so the padding branch of square_pad_resize
+    does not exist here: a plan with ``patch <= tgt_size`` is refused."""
+    import ctypes as C
+
+    import torch
+
+    from . import imgproc, lib as _lib, ops
+
+    if pl.patch <= tgt_size:
+        raise ValueError(f"squares_gpu: squares of side {pl.patch} would be padded to {tgt_size}; plan() makes no such plan (use squares)")
+    if page_dev.dtype != torch.uint8 or page_dev.dim() != 3 or page_dev.shape[2] != 3 or not page_dev.is_cuda:
+        raise ValueError(f"squares_gpu expects a uint8 device page [H,W,3], got {page_dev.dtype} {tuple(page_dev.shape)} on {page_dev.device}")
+    H, W = int(page_dev.shape[0]), int(page_dev.shape[1])
+    if (pl.h, pl.w) != ((W, H) if pl.transpose else (H, W)):
+        raise ValueError(f"squares_gpu: the plan is for a {pl.h} x {pl.w} strip, the page is {H} x {W}")
+    page_dev = page_dev.contiguous()
+    sq = torch.empty(pl.p_num, pl.patch, pl.patch, 3, dtype=torch.uint8, device=page_dev.device)
+    _lib.check(_lib.load().mit_rearrange_squares(page_dev.data_ptr(), H, W, int(pl.transpose), pl.w, pl.pw_num, pl.ph_num, pl.ph_step, pl.p_num,
+                                                 sq.data_ptr(), C.c_void_p(ops.current_stream())), "mit_rearrange_squares")
+    return imgproc.resize_u8(sq, (tgt_size, tgt_size))
+
+
+def stitch_gpu(maps_dev, pl: Plan, u8: bool = False):
+    """``stitch`` on the device (``mit_rearrange_stitch``): the network's output squares f32 [n, C, m, m] (or [n, m, m]: one channel),
+    any strides — an engine's workspace view as it is — -> the strip's map f32 [1, C, H', W'], bit-identical to ``stitch``.  With
+    ``u8`` it returns ``(map, (map * 255).astype(uint8))``: the second is ctd's postprocess_mask (ctd.py:41-44) of the stitched mask."""
+    import ctypes as C
+
+    import torch
+
+    from . import lib as _lib, ops
+
+    if maps_dev.dim() == 3:
+        maps_dev = maps_dev[:, None]
+    if maps_dev.dtype != torch.float32 or maps_dev.dim() != 4 or maps_dev.shape[2] != maps_dev.shape[3] or not maps_dev.is_cuda:
+        raise ValueError(f"stitch_gpu expects float32 device squares [n,C,m,m], got {maps_dev.dtype} {tuple(maps_dev.shape)} on {maps_dev.device}")
+    n, ch, m, _ = (int(v) for v in maps_dev.shape)
+    if n != pl.p_num:
+        raise ValueError(f"stitch_gpu: {n} squares for a plan of {pl.p_num}")
+    step, pw, hh, starts = stitch_geometry(pl, m)
+    if any(b < a for a, b in zip(starts, starts[1:])) or starts[0] < 0:
+        raise ValueError("stitch_gpu: band starts must not decrease")
+    dev = maps_dev.device
+    starts_dev = torch.tensor(starts, dtype=torch.int32).to(dev)
+    shape = (1, ch, pw, hh) if pl.transpose else (1, ch, hh, pw)
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    out_u8 = torch.empty(shape, dtype=torch.uint8, device=dev) if u8 else None
+    sn, sc, sy, sx = (int(v) for v in maps_dev.stride())
+    _lib.check(_lib.load().mit_rearrange_stitch(maps_dev.data_ptr(), n, ch, m, sn, sc, sy, sx, int(pl.transpose), pl.pw_num, pl.ph_num, step, pw,
+                                                hh, starts_dev.data_ptr(), out.data_ptr(), out_u8.data_ptr() if u8 else None, int(u8),
+                                                C.c_void_p(ops.current_stream())), "mit_rearrange_stitch")
+    return (out, out_u8) if u8 else out
+
+
+def forward_gpu(page_dev, batch_forward_dev: Callable, tgt_size: int, max_batch_size: int = 4, mask_u8: bool = False):
+    """``forward`` with the page on the device: -> (db [1,2,H',W'], mask [1,1,H'',W'']) device tensors, or (None, None) when the page
+    needs no tiling.  ``batch_forward_dev(u8 [n<=max_batch_size, tgt, tgt, 3] device) -> (db [n,2,m,m], mask [n,1,m',m'] or [n,m',m'])``
+    float32 device tensors of any strides; they may be views of a workspace that the next call overwrites (a strip of more than
+    ``max_batch_size`` squares collects them in a buffer of its own, a smaller one stitches the views as they are).  ``mask_u8``: the
+    mask comes back as ``(mask, mask_u8)`` (``stitch_gpu(..., u8=True)``)."""
+    import torch
+
+    pl = plan(int(page_dev.shape[0]), int(page_dev.shape[1]), tgt_size)
+    if pl is None:
+        return None, None
+    sq = squares_gpu(page_dev, pl, tgt_size)
+    if pl.p_num <= max_batch_size:
+        db, mask = batch_forward_dev(sq)
+    else:
+        db = mask = None
+        for i in range(0, pl.p_num, max_batch_size):
+            d, m = batch_forward_dev(sq[i:i + max_batch_size])
+            if db is None:
+                db = torch.empty((pl.p_num,) + tuple(d.shape[1:]), dtype=d.dtype, device=d.device)
+                mask = torch.empty((pl.p_num,) + tuple(m.shape[1:]), dtype=m.dtype, device=m.device)
+            db[i:i + max_batch_size] = d
+            mask[i:i + max_batch_size] = m
+    return stitch_gpu(db, pl), stitch_gpu(mask, pl, u8=mask_u8)

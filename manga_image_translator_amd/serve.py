@@ -256,8 +256,8 @@ class DenseStages:
             return "not HxWx3"
         if self._upscale_options(cfg)[0]:
             return "upscale"
-        if rearrange.plan(page.shape[0], page.shape[1], 1024) is not None:
-            return "webtoon strip (rearranged detection)"
+        if rearrange.plan(page.shape[0], page.shape[1], 1024) is not None and not getattr(self._coupled_engine(), "takes_strips", False):
+            return "webtoon strip (rearranged detection)"      # (the engine is asked only when the page is a strip)
         if int(_as_dict(cfg.get("ocr", {})).get("ignore_bubble", 0)):
             return "ocr.ignore_bubble is not implemented by the coupled engine"
         return None
@@ -283,8 +283,9 @@ class DenseStages:
         ``batch_size`` > 1 the pages of equal size are grouped, up to ``batch_size`` per group; each group is uploaded once and goes
         through ONE ``CoupledPageEngine.run`` on the engines the loaded plugins own.  Results come back in request order, each the
         dict ``translate`` returns for that page with ``config`` and its ``config["per_page"][i]`` overlay.  A page alone in its size
-        group, a webtoon strip and a request option the coupled engine does not implement take the page loop (``translate``), as
-        every page does with ``batch_size <= 1``; ``last_batch_plan`` and the ``pages_batched`` / ``pages_looped`` counters of
+        group and a request option the coupled engine does not implement take the page loop (``translate``), as every page does
+        with ``batch_size <= 1``; webtoon strips of equal size batch like any other page when the coupled engine has the
+        rearranged detection (``takes_strips``, which ``CoupledPageEngine`` sets), else they take the loop as well; ``last_batch_plan`` and the ``pages_batched`` / ``pages_looped`` counters of
         ``device_info`` say which way the pages went."""
         import torch
 
