@@ -529,9 +529,8 @@ def pack_chunks(region_imgs: List[np.ndarray], max_chunk_size: int = 16, *, heig
         yield indices, widths, region
 
 
-# numpy mirror of the C struct MitWarpLine (include/mit_hip.h): 9 doubles + 10 int32 = 112 bytes
-WARP_LINE_DTYPE = np.dtype([("minv", "<f8", (9,)), ("page", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("cw", "<i4"), ("ch", "<i4"),
-                            ("dw", "<i4"), ("dh", "<i4"), ("vertical", "<i4"), ("out_row", "<i4"), ("_pad", "<i4")])
+# numpy records of the C struct MitWarpLine (include/mit_hip.h): 9 doubles + 10 int32 = 112 bytes
+WARP_LINE_DTYPE = np.dtype(_lib.MitWarpLine)
 
 
 def warp_plans(quads: Sequence[Quadrilateral], directions: Sequence[str], im_h: int, im_w: int, textheight: int = 48) -> np.ndarray:

@@ -1,6 +1,7 @@
-"""The C-ABI library: loads, exports every function include/mit_hip.h declares, and the ctypes mirror of every struct
-has the C compiler's size and field offsets (gcc compiles a probe against the real header).  No compute calls: those
-are the ``-m gpu`` tests."""
+"""The C-ABI library: loads and exports every function include/mit_hip.h declares; the ctypes binding lib.py derives from that header
+(cheader.py) has every declared function, the C compiler's size and field offsets for every struct (gcc compiles a probe against the
+real header) and the literal prototypes pinned below; the header reader refuses what it cannot read.  No compute calls: those are the
+``-m gpu`` tests."""
 import ctypes as C
 import os
 import re
@@ -81,12 +82,13 @@ def test_pgemm_argument_checks_without_gpu():
 
 
 def test_ctypes_structs_match_c_layout(tmp_path):
+    """Every struct the header declares, not a hand-kept list: size and every field offset as gcc lays them out."""
     from manga_image_translator_amd import lib
 
-    structs = {"MitTensorMap": lib.MitTensorMap, "MitConvGemm": lib.MitConvGemm, "MitXposTables": lib.MitXposTables,
-               "MitLinear": lib.MitLinear, "MitOcrDecoderLayer": lib.MitOcrDecoderLayer, "MitOcr48Decoder": lib.MitOcr48Decoder,
-               "MitOcr48DecodeArgs": lib.MitOcr48DecodeArgs, "MitProfStat": lib.MitProfStat, "MitWarpLine": lib.MitWarpLine,
-               "MitDilateJob": lib.MitDilateJob, "MitMaskRun": lib.MitMaskRun, "MitPGemm": lib.MitPGemm}
+    structs = lib.STRUCTS
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert set(structs) == set(re.findall(r"typedef\s+struct\s+(\w+)", src)) and len(structs) >= 19
+    assert all(getattr(lib, name) is st for name, st in structs.items())
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void) {"]
     for name, st in structs.items():
         lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
@@ -102,6 +104,88 @@ def test_ctypes_structs_match_c_layout(tmp_path):
         assert int(out[name]) == C.sizeof(st), name
         for fname, *_ in st._fields_:
             assert int(out[f"{name}.{fname}"]) == getattr(st, fname).offset, f"{name}.{fname}"
+
+
+def test_prototype_pins():
+    """Literal prototypes of entries that exercise each rule of the header reader: a wrong scalar width (int for int64_t) would
+    truncate a stride silently."""
+    from manga_image_translator_amd import lib
+
+    P, I, Q, F, D, S = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_char_p
+    assert lib.SYMBOLS["mit_last_error"] == (S, [])
+    assert lib.SYMBOLS["mit_device_name"] == (I, [I, S, I])
+    assert lib.SYMBOLS["mit_lama_tail_need_work"] == (Q, [I, I, I])
+    assert lib.SYMBOLS["mit_convt_cout1"] == (I, [P, Q, Q, Q, I, I, I, I, P, I, I, I, P, P, I, F, P, Q, Q, Q, I, I, P])
+    assert lib.SYMBOLS["mit_mask_assign_lines"] == (I, [P, I, I, P, P, P, I, I, D, P, Q, P, Q, P, P, P])
+    assert lib.SYMBOLS["mit_ocr32_decode"] == (I, [P, P, P])
+    assert lib.SYMBOLS["mit_prof_enable"] == (I, [I])
+    assert (lib.MIT_ABI_VERSION, lib.MIT_MAX_TAPS, lib.MIT_CONVT_COUT1_STRIP_K4, lib.MIT_CONVT_COUT1_STRIP_K2) == (25, 64, 16, 64)
+    assert (lib.ACT_NONE, lib.ACT_RELU, lib.ACT_LEAKY, lib.ACT_SILU, lib.ACT_SIGMOID, lib.ACT_GELU) == tuple(range(6))
+    assert (lib.ACT_POST_FIRST, lib.PAD_ZERO, lib.PAD_REFLECT) == (0x100, 0, 1)
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int mit_f(size_t n);", "size_t"),                                    # an unknown type
+    ("typedef struct S { foo_t *p; } S;", "foo_t"),                       # ... also behind a pointer
+    ("int mit_f(void (*cb)(int), int n);", "mit_f"),                       # a function-pointer parameter
+    ("typedef struct S { int a : 3; } S;", "a : 3"),                       # a bit-field
+    ("typedef union U { int a; float b; } U;", "typedef union U"),         # a union
+    ("typedef struct S { union { int a; float b; } u; } S;", "struct S"),  # ... also inside a struct
+    ("int mit_f(int, float x);", "int"),                                   # an unnamed parameter
+    ("typedef struct S { int a[N]; } S;", "N"),                            # an extent that is no #define
+    ("enum E { A, B };", "A"),                                             # an enumerator without a value
+    ("#define MIT_F(x) (x)", "MIT_F"),                                     # a function-like macro
+    ("int mit_f(int n)", "mit_f"),                                         # a declaration that never ends
+    ("int mit_ok(int n);", "mit_ok"),                                      # a second prototype of one name
+    ("int mit_f(int n[4]);", "mit_f"),                                     # an array parameter
+])
+def test_header_reader_refuses_what_it_cannot_read(text, named):
+    from manga_image_translator_amd import cheader
+
+    with pytest.raises(cheader.HeaderError, match=re.escape(named)):
+        cheader.parse("/* c */ int mit_ok(void);\n" + text)
+
+
+def test_header_reader_on_a_synthetic_header():
+    from manga_image_translator_amd import cheader
+
+    consts, structs, funcs, enums = cheader.parse("""
+        #ifndef X_H
+        #define X_H
+        #include <stdint.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define N 3 /* extent */
+        #define MASK 0x10
+        enum E { E_A = 0, E_B = 7 };
+        typedef struct In { int8_t tag; double ms, a, b; } In;  /* several declarators on a line */
+        typedef struct Out {
+            char name[5];
+            const float *w, *b;
+            int16_t taps[N];   /* sized by a #define */
+            In rows[2];        /* an array of nested structs */
+            In one;
+            int32_t n, _pad;
+        } Out;
+        const char *mit_name(void);
+        int64_t mit_run(const Out *o, char *buf, uint64_t *sums, float alpha,
+                        void *stream);
+        void mit_reset(void);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """)
+    assert consts == {"N": 3, "MASK": 16} and enums == {"E_A": 0, "E_B": 7}
+    In, Out = structs["In"], structs["Out"]
+    assert [f[0] for f in In._fields_] == ["tag", "ms", "a", "b"] and C.sizeof(In) == 32 and In.ms.offset == 8 and In.b.offset == 24
+    assert [(n, getattr(Out, n).offset, getattr(Out, n).size) for n, _ in Out._fields_] == [
+        ("name", 0, 5), ("w", 8, 8), ("b", 16, 8), ("taps", 24, 6), ("rows", 32, 64), ("one", 96, 32), ("n", 128, 4), ("_pad", 132, 4)]
+    assert C.sizeof(Out) == 136
+    assert dict(Out._fields_)["w"] is C.c_void_p and dict(Out._fields_)["rows"] is In * 2 and dict(Out._fields_)["taps"] is C.c_int16 * 3
+    assert funcs == {"mit_name": (C.c_char_p, []), "mit_reset": (None, []),
+                     "mit_run": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_float, C.c_void_p])}
 
 
 def test_stale_library_is_refused(tmp_path, monkeypatch):

@@ -9,10 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from manga_image_translator_amd import lib as L
+
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.0
-STRIP = {4: 16, 2: 64}      # MIT_CONVT_COUT1_STRIP_K4 / _K2 (include/mit_hip.h): input positions per workgroup along a row
+STRIP = {4: L.MIT_CONVT_COUT1_STRIP_K4, 2: L.MIT_CONVT_COUT1_STRIP_K2}    # input positions per workgroup along a row (include/mit_hip.h)
 ROWS = {4: 16, 2: 8}        # rows of input positions a workgroup walks (csrc/convt_cout1.hip)
 
 

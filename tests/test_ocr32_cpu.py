@@ -1,10 +1,9 @@
 """The 32px OCR without a GPU: the CPU oracle against the fixture written from the reference's own module (and against that module
 live where the reference tree exists), the state-dict schema, the beam rules on crafted top-5 tables, the host rules of
-``Model32pxOCR._infer`` (model_32px.py:58-140), the C struct layouts and the plugin's lifecycle."""
+``Model32pxOCR._infer`` (model_32px.py:58-140) and the plugin's lifecycle (the C struct layouts: tests/test_capi.py)."""
 import asyncio
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,9 +11,6 @@ import torch
 
 import _ocr32_oracle as O
 from manga_image_translator_amd import lib, ocr32, ocr32_schema as S, plugins as P
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mit_hip.h")
 
 
 def run(coro):
@@ -145,25 +141,6 @@ def test_ignore_bubble_rule():
     crop[:, :32] = 0
     assert TL.is_ignore(crop, 10) and not TL.is_ignore(crop, 0) and not TL.is_ignore(crop, 51)
     assert not TL.is_ignore(np.full((32, 64, 3), 255, np.uint8), 10)
-
-
-def test_struct_layouts_match_c(tmp_path):
-    structs = {"MitOcr32Decoder": lib.MitOcr32Decoder, "MitOcr32DecodeArgs": lib.MitOcr32DecodeArgs}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void) {"]
-    for name, st in structs.items():
-        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
-        for fname, *_ in st._fields_:
-            lines.append(f'printf("{name}.{fname} %zu\\n", offsetof({name}, {fname}));')
-    lines += ["return 0; }"]
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c11", str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    for name, st in structs.items():
-        assert int(out[name]) == C.sizeof(st), name
-        for fname, *_ in st._fields_:
-            assert int(out[f"{name}.{fname}"]) == getattr(st, fname).offset, f"{name}.{fname}"
 
 
 def test_native_argument_checks_without_gpu():
