@@ -402,6 +402,15 @@ int mit_bilateral_u8c3(const uint8_t *src_dev, uint8_t *dst_dev, int B, int H, i
  * original mask thresholded at 127 (inpainting_lama_mpe.py:57-61,116). */
 int mit_select_u8(const uint8_t *mask_dev, int thr, const uint8_t *a_dev, const uint8_t *b_dev, uint8_t *out_dev, int64_t npix, int C,
                   void *stream);
+/* The mask tail of the DBNet detectors (detection/default.py:89-95, dbnet_convnext.py the same lines): cv2.resize(mask, (2w, 2h),
+ * INTER_LINEAR) of the float text mask, the crop of the padding and np.clip(m * 255, 0, 255).astype(np.uint8), in one pass.
+ * src f32 [B,h,w] with `src_batch_stride` / `src_row_stride` in elements (unit stride along w: an engine's workspace view as it is);
+ * out u8 [B,oh,ow] dense, oh <= 2h and ow <= 2w (the top-left oh x ow of the 2x map), oh and B at most 65535 a launch.  Output index i taps (i + 0.5) * 0.5 - 0.5:
+ * weights 0.75 / 0.25 on the two nearest sources, 1 / 0 on the edge element at both borders; the horizontal pass
+ * r = m[x0] * wx0 + m[x1] * wx1 first (fp32: two rounded products, one rounded sum, no FMA), the vertical pass the same way on its
+ * results, then v * 255.0f, clamp to [0, 255], truncate.  Inputs are finite; NaN has no defined result.  Additive in ABI 25. */
+int mit_dbnet_mask_tail(const float *src_dev, int64_t src_batch_stride, int64_t src_row_stride, int B, int h, int w, uint8_t *out_dev,
+                        int oh, int ow, void *stream);
 
 /* Webtoon strips: det_rearrange_forward's tiling around the detector network, on the device (ABI 25) ----------------------
  * Reference: utils/generic.py:876-997 (called from detection/ctd.py:137 and detection/default.py:60).  The plan (transpose, w, pw_num,

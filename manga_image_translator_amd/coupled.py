@@ -11,6 +11,10 @@ refinement with its DenseCRF (f1) — is inside the measured path.  Dense work r
 release the GIL) while the stream keeps executing.  A batch larger than one group of 16 pages flows through three stage threads
 (detector + boxes + refine_mask | OCR | merge + mask refinement + LaMa) that work on different groups at the same time (``run(group=)``).
 
+``CoupledPageEngine`` itself builds the ctd detector, the 48px OCR and a LaMa; ``from_engines`` takes the engines loaded plugins own,
+and there the detector may be of the DBNet kind (``default`` / ``dbconvnext``: ``plugins.dbnet_detect_pages``, no ``refine_mask``, the
+raw mask at the detector's own size) and the inpainter a LaMa of either depth or the AOT engine.
+
 Random-init networks do not detect text (their sigmoid maps hover around 0.5 everywhere), so a benchmark passes ``inject``: per-page
 maps a trained head would have produced for the synthetic page (``synthetic_head_outputs``); they replace the network's own outputs
 AFTER the network has run (its cost is paid in full) — a stand-in for trained weights, never part of the product path (the plugins do
@@ -44,7 +48,32 @@ class CoupledResult:
     mask: torch.Tensor                         # u8 [B,H,W] final inpainting mask (device)
     inpainted: torch.Tensor                    # u8 [B,H,W,3] (device)
     seconds: Dict[str, float] = field(default_factory=dict)   # host wall time per phase (the GPU runs asynchronously underneath)
-    mask_raw: Optional[torch.Tensor] = None   # u8 [B,H,W] the mask the refinement started from (the detector's, or the request's)
+    # the mask the refinement started from (the detector's, or the request's): u8 [B,H,W] from the ctd engine (its refined mask, page
+    # size); u8 [B,h',w'] from a DBNet engine (its raw mask at the detector's own size, which mask refinement resizes), or a list of B
+    # such masks when a request brought page-sized ones for some pages
+    mask_raw: Optional[object] = None
+
+
+class RawMasks(list):
+    """Per-page raw masks of unequal sizes (a DBNet run in which a request replaced some pages' masks), with what ``merge_and_refine``
+    asks of the one-tensor form: the event recorded behind the last writer, and ``record_stream``."""
+    mit_ready_event = None
+
+    def record_stream(self, stream):
+        for m in self:
+            m.record_stream(stream)
+
+
+def is_dbnet_engine(engine) -> bool:
+    """Whether a detector engine is one of the DBNet kind (``DbnetEngine`` / ``DbconvnextEngine``: ``forward`` -> (db, mask), the page
+    function ``plugins.dbnet_detect_pages`` around it) rather than the ctd engine."""
+    from . import dbconvnext, dbnet
+
+    return isinstance(engine, (dbnet.DbnetEngine, dbconvnext.DbconvnextEngine))
+
+
+# DefaultDetector's parameters as the reference's Config sets them (config.py:276-290); ``run`` hands them to a DBNet engine only
+DETECT_SIZE, TEXT_THRESHOLD, DET_BOX_THRESHOLD, UNCLIP_RATIO = 2048, 0.5, 0.7, 2.3
 
 
 def synthetic_head_outputs(page: np.ndarray, quads: np.ndarray, map_hw, shrink_ratio: float = 0.4, unclip_ratio: float = 1.5):
@@ -90,17 +119,26 @@ class CoupledPageEngine:
         self.ctd = ctd.CtdEngine(weights["ctd.yolo"], weights["ctd.seg"], weights["ctd.det"], device=self.device)
         self.ocr = ocr48.Ocr48Engine(weights["ocr48"], len(self.dictionary), device=self.device)
         self.lama = lama.LamaEngine(weights["lama.gen"], weights.get("lama.mpe"), n_blocks=lama_blocks, device=self.device)
+        self.dbnet = False
         self._init_host(ctd_mb, lama_mb, host_workers, mask_workers, side_stream)
 
     @classmethod
     def from_engines(cls, ctd_engine, ocr_engine, lama_engine, dictionary: Sequence[str], ctd_mb: int = 16, lama_mb: int = 16,
                      host_workers: int = 16, mask_workers: int = 4, side_stream: Optional[bool] = None) -> "CoupledPageEngine":
         """On the engines loaded plugins already own (``plugin.engine``): no second copy of any weight.  The engine objects are kept,
-        not their methods, so whatever a caller hangs on ``engine.forward`` afterwards is what a run calls."""
+        not their methods, so whatever a caller hangs on ``engine.forward`` afterwards is what a run calls.
+
+        The detector slot takes the ctd engine or one of the DBNet kind (``DbnetEngine``, ``DbconvnextEngine``; ``ctd_mb`` is its
+        micro-batch as well), the inpainter slot a ``LamaEngine`` of either depth or the ``AotEngine``.  With a DBNet detector
+        ``detect`` is ``plugins.dbnet_detect_pages``: no ``refine_mask``, the raw mask at the detector's own size, and no webtoon
+        strips (``takes_strips`` is False: a server sends those pages through its page loop)."""
         self = cls.__new__(cls)
         self.device = torch.device(ctd_engine.device)
         self.dictionary = list(dictionary)
         self.ctd, self.ocr, self.lama = ctd_engine, ocr_engine, lama_engine
+        self.dbnet = is_dbnet_engine(ctd_engine)
+        if self.dbnet:
+            self.takes_strips = False
         self._init_host(ctd_mb, lama_mb, host_workers, mask_workers, side_stream)
         return self
 
@@ -129,12 +167,19 @@ class CoupledPageEngine:
 
     # ---- stage 1: detector network + boxes (host pool) + mask resize + refine_mask ------------------------------------------
     @torch.no_grad()
-    def detect(self, pages_u8: torch.Tensor, inject=None):
+    def detect(self, pages_u8: torch.Tensor, inject=None, det: Optional[dict] = None):
         """-> (textlines per page, refined mask u8 [B,H,W] on the device): ComicTextDetector._infer (ctd.py:129-179) for a batch.
 
         Webtoon strips (``rearrange.plan(H, W, 1024)`` is not None) take det_rearrange_forward's branch (ctd.py:137) like the plugin
         does, on the device: see ``_detect_strips``.  ``inject`` on a strip holds maps of the STITCHED geometry: ``prob`` f32
-        [B, hh, pw] and ``mask`` u8 [B, hh, pw] ([B, pw, hh] for a wide strip), ``(step, pw, hh, _) = rearrange.stitch_geometry(plan, 1024)``."""
+        [B, hh, pw] and ``mask`` u8 [B, hh, pw] ([B, pw, hh] for a wide strip), ``(step, pw, hh, _) = rearrange.stitch_geometry(plan, 1024)``.
+
+        With a DBNet engine in the detector slot: DefaultDetector._infer (default.py:56-103) for the batch, which is
+        ``plugins.dbnet_detect_pages`` with the parameters of ``det`` (``detect_size`` / ``text_threshold`` / ``box_threshold`` /
+        ``unclip_ratio``; the ctd engine ignores them, as the reference's ctd does) -> (textlines per page, the RAW mask u8 [B,h',w'] at the
+        detector's own size): that detector has no ``refine_mask``."""
+        if self.dbnet:
+            return self._detect_dbnet(pages_u8, inject, det or {})
         B, H, W, _ = pages_u8.shape
         mask_full = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
         keep = []
@@ -172,6 +217,19 @@ class CoupledPageEngine:
         # for the whole queue): no table keyed by address that a failed stage could leave behind for an unrelated tensor to inherit
         refined.mit_ready_event = torch.cuda.current_stream().record_event()
         return textlines, refined
+
+    def _detect_dbnet(self, pages_u8: torch.Tensor, inject, det: dict):
+        from . import plugins as P
+
+        size = int(det.get("detect_size", DETECT_SIZE))
+        if rearrange.plan(int(pages_u8.shape[1]), int(pages_u8.shape[2]), size) is not None:
+            raise NotImplementedError("CoupledPageEngine: webtoon strips with a DBNet detector are not batched (takes_strips is False); "
+                                      "run such pages through the detector plugin")
+        textlines, raw = P.dbnet_detect_pages(self.ctd, pages_u8, size, float(det.get("text_threshold", TEXT_THRESHOLD)),
+                                              float(det.get("box_threshold", DET_BOX_THRESHOLD)), float(det.get("unclip_ratio", UNCLIP_RATIO)),
+                                              self.ctd_mb, inject, quad_type=Quadrilateral)
+        raw.mit_ready_event = torch.cuda.current_stream().record_event()    # as detect() does behind its refined masks
+        return textlines, raw
 
     def _detect_strips(self, pages_u8: torch.Tensor, pl, inject, mask_full: torch.Tensor):
         """The network part of ``detect`` for a batch of equal webtoon strips, det_rearrange_forward (utils/generic.py:876-997) on the
@@ -294,7 +352,8 @@ class CoupledPageEngine:
     def run(self, pages_u8: torch.Tensor, max_seq_length: int = 255, suppress_eos: bool = False, prob_threshold: float = 0.2,
             inject=None, group: Optional[int] = 16, textlines: Optional[Sequence] = None, mask_raw: Optional[Sequence] = None,
             mask: Optional[Sequence] = None, mask_dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE,
-            inpainting_size: Optional[int] = None, precision: str = "fp32") -> CoupledResult:
+            inpainting_size: Optional[int] = None, precision: str = "fp32", detect_size: int = DETECT_SIZE,
+            text_threshold: float = TEXT_THRESHOLD, box_threshold: float = DET_BOX_THRESHOLD, unclip_ratio: float = UNCLIP_RATIO) -> CoupledResult:
         """``group``: pages per pipeline slot.  A batch larger than one group flows through three stage threads (detector + boxes +
         refine_mask | OCR | merge + mask refinement + LaMa), each working on a different group at a time, so the host phases of one
         group run while the kernels of its neighbours execute; every stage sees the groups in order and owns its engines, and each
@@ -305,7 +364,11 @@ class CoupledPageEngine:
         that replaces the detector's refined mask ahead of merge + refinement; ``mask`` — the final mask, which skips merge +
         refinement.  ``inpainting_size``: the inpainter plugin's resize rule (``plugins.inpaint_pages``); None = the pages go to the
         network as they are (H, W multiples of 8).  ``precision``: the inpainter's, "fp32" | "bf16" (``LamaEngine.forward``) —
-        a server passes its plugin's ``precision_for(config)``.  The defaults are the constants the benchmark path has always used."""
+        a server passes its plugin's ``precision_for(config)``.  The defaults are the constants the benchmark path has always used.
+        ``detect_size`` / ``text_threshold`` / ``box_threshold`` / ``unclip_ratio``: the detector's parameters (DetectorConfig,
+        config.py:274-290), for a DBNet engine; the ctd engine ignores them as the reference's ctd does (fixed 1024, 0.3, 0.6, 1.5).
+        With a DBNet engine a request's ``mask_raw`` may be page-sized or of the detector's mask size; ``CoupledResult.mask_raw`` is
+        then a list when the sizes differ between pages."""
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"CoupledPageEngine.run: precision must be 'fp32' or 'bf16' (got {precision!r})")
         if pages_u8.dtype != torch.uint8 or pages_u8.dim() != 4 or pages_u8.shape[-1] != 3 or not pages_u8.is_cuda:
@@ -315,12 +378,14 @@ class CoupledPageEngine:
             if v is not None and len(v) != B:
                 raise ValueError(f"CoupledPageEngine.run: {name} must have one entry per page ({len(v)} for {B} pages)")
         req = {"textlines": textlines, "mask_raw": mask_raw, "mask": mask, "offset": int(mask_dilation_offset), "kernel": int(kernel_size),
-               "inpainting_size": inpainting_size, "precision": precision}
+               "inpainting_size": inpainting_size, "precision": precision,
+               "det": {"detect_size": int(detect_size), "text_threshold": float(text_threshold), "box_threshold": float(box_threshold),
+                       "unclip_ratio": float(unclip_ratio)}}
         if group is not None and B > group:
             return self._run_pipelined(pages_u8, max_seq_length, suppress_eos, prob_threshold, inject, int(group), req)
         sec = {}
         t = time.perf_counter()
-        tl, mraw = self._requested(*self.detect(pages_u8, inject), req, 0, B)
+        tl, mraw = self._requested(*self.detect(pages_u8, inject, req["det"]), req, 0, B, tuple(pages_u8.shape[1:3]))
         sec["detect+boxes+refine_mask"] = time.perf_counter() - t
         t = time.perf_counter()
         tl = self.recognize(pages_u8, tl, max_seq_length, suppress_eos, prob_threshold)
@@ -334,8 +399,10 @@ class CoupledPageEngine:
         sec["inpaint (enqueue)"] = time.perf_counter() - t
         return CoupledResult(tl, regions, final, inpainted, sec, mraw)
 
-    def _requested(self, textlines, mask_raw, req, a, b):
-        """The detector's lines / refined masks of pages a..b with what the request brings for them laid over."""
+    def _requested(self, textlines, mask_raw, req, a, b, page_hw=None):
+        """The detector's lines / refined masks of pages a..b with what the request brings for them laid over.  ``page_hw``: the pages'
+        (H, W); a DBNet engine's raw masks have a size of their own, and a request's page-sized ``mask_raw`` then turns the group's
+        masks into a per-page list (``RawMasks``: mask refinement resizes a raw mask of any size)."""
         tin, min_ = req["textlines"], req["mask_raw"]
         if tin is not None:
             for k in range(a, b):
@@ -343,12 +410,16 @@ class CoupledPageEngine:
                     textlines[k - a] = [Quadrilateral(np.asarray(p, dtype=np.int64), "", 1.0) for p in tin[k]]
         if min_ is not None and any(min_[k] is not None for k in range(a, b)):
             ready = getattr(mask_raw, "mit_ready_event", None)
+            own = tuple(mask_raw.shape[1:])
+            sizes = (own,) if page_hw is None or not self.dbnet else (own, tuple(page_hw))
             for k in range(a, b):
                 if min_[k] is not None:
                     m = min_[k]
                     m = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(m, dtype=np.uint8))
-                    if tuple(m.shape) != tuple(mask_raw.shape[1:]):
-                        raise ValueError(f"mask_raw of page {k} must be {tuple(mask_raw.shape[1:])} (got {tuple(m.shape)})")
+                    if tuple(m.shape) not in sizes:
+                        raise ValueError(f"mask_raw of page {k} must be {' or '.join(str(s) for s in sizes)} (got {tuple(m.shape)})")
+                    if tuple(m.shape) != own and not isinstance(mask_raw, RawMasks):
+                        mask_raw = RawMasks(mask_raw[i] for i in range(b - a))
                     mask_raw[k - a] = m.to(self.device)
             if ready is not None:
                 mask_raw.mit_ready_event = torch.cuda.current_stream().record_event()
@@ -372,7 +443,9 @@ class CoupledPageEngine:
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         sec = {"detect+boxes+refine_mask": 0.0, "ocr": 0.0, "textline_merge+mask_refinement": 0.0, "inpaint (enqueue)": 0.0}
         mask = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
-        mask_raw_all = torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        # (a DBNet engine's raw masks have a size of their own, per page once a request replaces some: they are gathered at the end)
+        mask_raw_all = None if self.dbnet else torch.empty(B, H, W, dtype=torch.uint8, device=self.device)
+        raws = [None] * len(spans)
         inpainted = torch.empty_like(pages_u8)
         caller = torch.cuda.current_stream()
         # One stream per stage thread (``stage_streams``, MIT_COUPLED_STAGE_STREAMS=1): a stage's read-backs wait for ITS kernels only, and
@@ -398,7 +471,7 @@ class CoupledPageEngine:
 
         def st_detect(a, b):
             inj = None if inject is None else {k: v[a:b] for k, v in inject.items()}
-            return timed("detect+boxes+refine_mask", lambda: self._requested(*self.detect(pages_u8[a:b], inj), req, a, b))
+            return timed("detect+boxes+refine_mask", lambda: self._requested(*self.detect(pages_u8[a:b], inj, req["det"]), req, a, b, (H, W)))
 
         def st_ocr(a, b, f_det):
             tl, mraw = f_det.result()
@@ -410,7 +483,10 @@ class CoupledPageEngine:
             regions, m = timed("textline_merge+mask_refinement", self.merge_and_refine, pages_u8[a:b], tl, mraw, given, req["offset"], req["kernel"])
             with torch.cuda.stream(st["tail"]):
                 mask[a:b] = m
-                mask_raw_all[a:b] = mraw
+                if mask_raw_all is not None:
+                    mask_raw_all[a:b] = mraw
+                else:
+                    raws[a // group] = mraw
             timed("inpaint (enqueue)", self._inpaint, pages_u8[a:b], mask[a:b], inpainted[a:b], req["inpainting_size"], req["precision"])
             return tl, regions
 
@@ -424,4 +500,7 @@ class CoupledPageEngine:
                 caller.wait_stream(x)
         textlines = [t for tl, _ in done for t in tl]
         regions = [r for _, rg in done for r in rg]
+        if mask_raw_all is None:   # one tensor while every group kept the detector's size, else the per-page list
+            same = all(isinstance(r, torch.Tensor) and r.shape[1:] == raws[0].shape[1:] for r in raws)
+            mask_raw_all = torch.cat(raws) if same else RawMasks(m for r in raws for m in r)
         return CoupledResult(textlines, regions, mask, inpainted, sec, mask_raw_all)

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 from functools import lru_cache
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -219,6 +219,38 @@ def select_u8(mask: torch.Tensor, thr: int, a: torch.Tensor, b: torch.Tensor) ->
     _lib.check(_lib.load().mit_select_u8(mask.data_ptr(), int(thr), a.data_ptr(), b.data_ptr(), out.data_ptr(), mask.numel(), a.shape[3],
                                          C.c_void_p(ops.current_stream())), "mit_select_u8")
     return out
+
+
+def dbnet_mask_tail(mask_f32: torch.Tensor, oh: int, ow: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The DBNet detectors' mask tail (detection/default.py:89-95) through ``mit_dbnet_mask_tail``: the float text mask f32 [B,h,w]
+    (or [h,w]) on the device — any batch and row stride, unit stride along w — resized 2x (INTER_LINEAR), cropped to its top-left
+    ``oh`` x ``ow`` and turned into bytes.  -> u8 [B,oh,ow] ([oh,ow]), byte for byte
+    ``np.clip(plugins._resize2x_f32(m)[:oh, :ow] * 255, 0, 255).astype(np.uint8)``.  ``out``: a dense u8 device tensor of that shape
+    to write into (a slice of a batch's masks) instead of a new one."""
+    from . import lib as _lib
+    from . import ops
+
+    if mask_f32.dtype != torch.float32 or mask_f32.dim() not in (2, 3):
+        raise ValueError(f"dbnet_mask_tail expects float32 [B,h,w] or [h,w], got {mask_f32.dtype} {tuple(mask_f32.shape)}")
+    if not mask_f32.is_cuda:
+        raise ValueError("dbnet_mask_tail runs on device tensors (plugins._resize2x_f32 is the numpy statement for host arrays)")
+    squeeze = mask_f32.dim() == 2
+    s = mask_f32[None] if squeeze else mask_f32
+    if s.stride(2) != 1 or s.stride(1) < s.shape[2] or s.stride(0) < 0:
+        s = s.contiguous()
+    B, h, w = s.shape
+    oh, ow = int(oh), int(ow)
+    if not (0 < oh <= 2 * h and 0 < ow <= 2 * w):
+        raise ValueError(f"dbnet_mask_tail: the output {oh} x {ow} must lie inside the 2x map {2 * h} x {2 * w}")
+    if out is None:
+        out = torch.empty(B, oh, ow, dtype=torch.uint8, device=s.device)
+    elif out.dtype != torch.uint8 or out.device != s.device or not out.is_contiguous() or tuple(out.shape) != ((oh, ow) if squeeze else (B, oh, ow)):
+        raise ValueError(f"dbnet_mask_tail: out must be a dense uint8 tensor {(B, oh, ow)} on {s.device}, got {out.dtype} {tuple(out.shape)}")
+    else:
+        out = out[None] if squeeze else out
+    _lib.check(_lib.load().mit_dbnet_mask_tail(s.data_ptr(), s.stride(0), s.stride(1), B, h, w, out.data_ptr(), oh, ow,
+                                               C.c_void_p(ops.current_stream())), "mit_dbnet_mask_tail")
+    return out[0] if squeeze else out
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -38,6 +38,31 @@ def synthetic_weights(seed: int = 0, lama_blocks: int = 9, dict_size: int = DICT
     return w
 
 
+def synthetic_stage_weights(stage: str, key: str, seed: int = 0, dict_size: int = DICT_SIZE):
+    """The ``weights=`` argument of ONE stage plugin, seeded as ``synthetic_weights`` seeds its three: ``stage`` "detector" | "ocr" |
+    "inpainter", ``key`` the reference's name of the model (Detector / Ocr / Inpainter of config.py).  The keys ``synthetic_weights``
+    covers (ctd, 48px, lama_mpe) get the very tensors it returns."""
+    from . import aot_schema, dbconvnext_schema, dbnet_schema, ocr32_schema, ocr_ctc_schema
+
+    sd = lambda schema, gain=1.0: synth.synth_state_dict(schema, seed=seed, gain=gain)   # noqa: E731
+    g = ctd_schema.CTD_GAIN
+    table = {
+        ("detector", "ctd"): lambda: {"ctd.yolo": sd(ctd_schema.yolo_schema(), g), "ctd.seg": sd(ctd_schema.unet_head_schema(), g),
+                                      "ctd.det": sd(ctd_schema.db_head_schema(), g)},
+        ("detector", "default"): lambda: sd(dbnet_schema.text_detection_schema(), 1.2),
+        ("detector", "dbconvnext"): lambda: sd(dbconvnext_schema.dbnet_convnext_schema()),
+        ("ocr", "48px"): lambda: sd(ocr_schema.ocr48_schema(dict_size)),
+        ("ocr", "48px_ctc"): lambda: sd(ocr_ctc_schema.ocr_ctc_schema(dict_size), ocr_ctc_schema.CTC_GAIN),
+        ("ocr", "32px"): lambda: sd(ocr32_schema.ocr32_schema(dict_size)),
+        ("inpainter", "lama_mpe"): lambda: {"lama.gen": sd(lama_schema.lama_generator_schema(9)), "lama.mpe": sd(lama_schema.lama_mpe_schema())},
+        ("inpainter", "lama_large"): lambda: {"lama.gen": sd(lama_schema.lama_generator_schema(18))},
+        ("inpainter", "default"): lambda: {"aot": sd(aot_schema.aot_generator_schema())},
+    }
+    if (stage, key) not in table:
+        raise ValueError(f"synthetic_stage_weights: no {stage} {key!r} (have {sorted(k for s, k in table if s == stage)})")
+    return table[(stage, key)]()
+
+
 @dataclass
 class PageBatchResult:
     """Device tensors produced by one ``PageEngine.run``."""

@@ -310,8 +310,10 @@ class HipDefaultDetector(_EnginePlugin, _DetBase):
     async def _infer(self, image: np.ndarray, detect_size: int, text_threshold: float, box_threshold: float,
                      unclip_ratio: float, verbose: bool = False):
         """-> (textlines, raw_mask u8 [H,W], None) (default.py:56-103).  bilateralFilter + resize_aspect_ratio (:62) and the
-        network run on the GPU; SegDetectorRepresenter (:73-77) is the native host extraction (csrc/hostglue.hip), the x2 mask
-        resize (:89) a numpy bilinear; every step can still be injected (preprocess= / boxes_from_maps= / resize2x=)."""
+        network run on the GPU, SegDetectorRepresenter (:73-77) and the x2 mask resize with its crop and cast (:89-95) as well
+        (``dbnet_detect_pages``: the page function the batch engine shares); every step can still be injected (preprocess= /
+        boxes_from_maps= / resize2x=) and then takes its host path: the native host extraction (csrc/hostglue.hip), the numpy
+        bilinear ``_resize2x_f32``.  A webtoon strip's stitched mask takes the numpy resize as well."""
         from . import imgproc, rearrange
 
         boxes_fn = self._boxes or _native_dbnet_boxes
@@ -340,6 +342,11 @@ class HipDefaultDetector(_EnginePlugin, _DetBase):
             h, w = image.shape[:2]
             ratio, pad_w, pad_h = 1.0, 0, 0
         else:
+            if self._pre is None and self._boxes is None and self._resize2x is None and torch.device(self.engine.device).type == "cuda":
+                # nothing injected: the page function the batch engine runs, for one page — only the boxes and the finished mask come down
+                tls, masks = dbnet_detect_pages(self.engine, self._page_on_device(image), detect_size, text_threshold, box_threshold,
+                                                unclip_ratio, micro_batch=1)
+                return tls[0], masks[0].cpu().numpy(), None
             if self._pre is not None:
                 img_resized, target_ratio, pad_w, pad_h = self._pre(image, detect_size)
                 page = self._page_on_device(img_resized)
@@ -354,15 +361,13 @@ class HipDefaultDetector(_EnginePlugin, _DetBase):
                 boxes_fn = lambda d, hh, ww, tt, bt, ur: hostglue.dbnet_boxes_gpu(d, hh, ww, tt, bt, ur)[0]   # noqa: E731
             else:
                 db = db.cpu().numpy()
-            mask = mask[0].cpu().numpy()
+            mask = mask[0] if self._resize2x is None and mask.is_cuda else mask[0].cpu().numpy()
         boxes, scores = boxes_fn(db, h, w, text_threshold, box_threshold, unclip_ratio)
-        if boxes.size == 0:
-            polys, scores = [], []
-        else:
-            idx = boxes.reshape(boxes.shape[0], -1).sum(axis=1) > 0
-            polys = (boxes[idx].astype(np.float64) * ratio).astype(np.int64)  # adjustResultCoordinates with ratio_net = 1 (:83)
-        textlines = [_RefQuadrilateral(pts.astype(int), "", float(s)) for pts, s in zip(polys, scores)]
-        textlines = [q for q in textlines if q.area > 16]
+        textlines = _dbnet_textlines(boxes, scores, ratio)
+        if torch.is_tensor(mask):     # no resize2x injected: the mask tail (:89-95) where the mask is (csrc/dbnet_tail.hip)
+            mh, mw = 2 * int(mask.shape[0]), 2 * int(mask.shape[1])
+            oh, ow = (mh - pad_h, mw) if pad_h > 0 else ((mh, mw - pad_w) if pad_w > 0 else (mh, mw))
+            return textlines, imgproc.dbnet_mask_tail(mask, oh, ow).cpu().numpy(), None
         mask_resized = resize2x(mask)
         if pad_h > 0:
             mask_resized = mask_resized[:-pad_h, :]
@@ -979,19 +984,87 @@ def default_preprocess_gpu(image: torch.Tensor, detect_size: int):
     (detection/default.py:62, default_utils/imgproc.py:37-70) on the device: bilateral filter (mit_bilateral_u8c3), 8-bit
     INTER_LINEAR resize of the long side to ``detect_size`` (mit_resize_u8), zero canvas padded right / bottom to a multiple of 256.
     image u8 [H,W,3] (device) -> (page u8 [1,H',W',3], ratio, pad_w, pad_h)."""
+    return default_preprocess_pages(image[None], detect_size)
+
+
+def default_preprocess_pages(pages: torch.Tensor, detect_size: int):
+    """``default_preprocess_gpu`` for pages of one size: u8 [B,H,W,3] (device) -> (pages u8 [B,H',W',3], ratio, pad_w, pad_h).  The three
+    steps are batched launches of the kernels a single page goes through, so a page's bytes do not depend on its company."""
     from . import imgproc
 
-    height, width = int(image.shape[0]), int(image.shape[1])
+    n, height, width = int(pages.shape[0]), int(pages.shape[1]), int(pages.shape[2])
     ratio = detect_size / max(height, width)
     target_h, target_w = int(round(height * ratio)), int(round(width * ratio))
-    proc = imgproc.resize_u8(imgproc.bilateral_filter_u8(image, 17, 80.0, 80.0)[None], (target_w, target_h))
+    proc = imgproc.resize_u8(imgproc.bilateral_filter_u8(pages, 17, 80.0, 80.0), (target_w, target_h))
     pad_h = (256 - target_h % 256) % 256
     pad_w = (256 - target_w % 256) % 256
     if pad_h or pad_w:
-        canvas = torch.zeros(1, target_h + pad_h, target_w + pad_w, 3, dtype=torch.uint8, device=image.device)
+        canvas = torch.zeros(n, target_h + pad_h, target_w + pad_w, 3, dtype=torch.uint8, device=pages.device)
         canvas[:, :target_h, :target_w] = proc
         proc = canvas
     return proc, ratio, pad_w, pad_h
+
+
+def _dbnet_textlines(boxes: np.ndarray, scores, ratio: float, quad_type=None) -> list:
+    """The boxes of SegDetectorRepresenter at the network's page size -> the page's text lines (default.py:78-87): empty boxes dropped,
+    ``adjustResultCoordinates`` with ratio_net = 1 (:83), the int cast, then only lines of an area above 16."""
+    quad_type = quad_type or _RefQuadrilateral
+    if boxes.size == 0:
+        polys, scores = [], []
+    else:
+        idx = boxes.reshape(boxes.shape[0], -1).sum(axis=1) > 0
+        polys = (boxes[idx].astype(np.float64) * ratio).astype(np.int64)
+    textlines = [quad_type(pts.astype(int), "", float(s)) for pts, s in zip(polys, scores)]
+    return [q for q in textlines if q.area > 16]
+
+
+@torch.no_grad()
+def dbnet_detect_pages(engine, pages_u8: torch.Tensor, detect_size: int, text_threshold: float, box_threshold: float, unclip_ratio: float,
+                       micro_batch: int = 16, inject=None, quad_type=None):
+    """DefaultDetector._infer (detection/default.py:56-103; dbnet_convnext.py:541-588 is the same text) for device pages u8 [B,H,W,3]
+    of one size that are no webtoon strips, around ``engine.forward`` (a ``DbnetEngine`` or ``DbconvnextEngine``): what the plugin runs
+    for its one page and the coupled batch engine for a group — the same kernels in the same order, so a page's results do not
+    depend on how many pages travel with it.  Nothing but the boxes leaves the device:
+
+    * bilateralFilter + resize_aspect_ratio (:62) for the whole micro-batch (``default_preprocess_pages``);
+    * the network, ``micro_batch`` pages at a time;
+    * SegDetectorRepresenter (:73-77) where the map is (csrc/ctd_boxes.hip), enqueued per micro-batch and collected after the loop (the
+      handle owns its copy of the map, so the next micro-batch may overwrite the engine's workspace);
+    * the x2 resize of the float mask, the crop of the padding and the cast to bytes (:89-95) in one kernel (csrc/dbnet_tail.hip).  The
+      crop follows the reference's ``if pad_h > 0 … elif pad_w > 0``: only one side is ever cropped.
+
+    ``inject`` (a stand-in for trained weights, as in ``CoupledPageEngine.detect``; applied after the network has run): ``prob`` f32
+    [B,h,w] at the network's map size replaces ``db[:, 0]``, ``mask`` f32 [B,h/2,w/2] the mask head's output.
+    -> (text lines per page, raw masks u8 [B,h',w'] on the device)."""
+    from . import hostglue, imgproc
+
+    if pages_u8.dtype != torch.uint8 or pages_u8.dim() != 4 or pages_u8.shape[-1] != 3 or not pages_u8.is_cuda:
+        raise ValueError(f"dbnet_detect_pages expects a uint8 device tensor [B,H,W,3], got {pages_u8.dtype} {tuple(pages_u8.shape)}")
+    B = int(pages_u8.shape[0])
+    micro_batch = max(1, int(micro_batch))
+    masks, handles, ratio = None, [], 1.0
+    for a in range(0, B, micro_batch):
+        page, target_ratio, pad_w, pad_h = default_preprocess_pages(pages_u8[a:a + micro_batch], detect_size)
+        ratio = 1 / target_ratio
+        n, h, w = int(page.shape[0]), int(page.shape[1]), int(page.shape[2])
+        db, mask = engine.forward(page)
+        prob = db[:, 0]
+        if inject is not None:
+            prob, mask = inject["prob"][a:a + n], inject["mask"][a:a + n]
+            if tuple(prob.shape[1:]) != (h, w) or tuple(mask.shape[1:]) != (h // 2, w // 2):
+                raise ValueError(f"dbnet_detect_pages: inject must hold prob [B,{h},{w}] and mask [B,{h // 2},{w // 2}] "
+                                 f"(got {tuple(prob.shape)} / {tuple(mask.shape)})")
+        handles.append(hostglue.boxes_from_bitmap_gpu_launch(prob, text_threshold, w, h, unclip_ratio=unclip_ratio, min_sside=3.0,
+                                                             box_thresh=box_threshold, min_sside_out=5.0, roll_start=True))
+        oh, ow = (h - pad_h, w) if pad_h > 0 else ((h, w - pad_w) if pad_w > 0 else (h, w))
+        if masks is None:
+            masks = torch.empty(B, oh, ow, dtype=torch.uint8, device=pages_u8.device)
+        imgproc.dbnet_mask_tail(mask, oh, ow, out=masks[a:a + n])
+    textlines = []
+    for hd in handles:
+        for boxes, scores in hostglue.boxes_from_bitmap_gpu_collect(hd):
+            textlines.append(_dbnet_textlines(boxes, scores, ratio, quad_type))
+    return textlines, masks
 
 
 def _resize2x_f32(m: np.ndarray) -> np.ndarray:

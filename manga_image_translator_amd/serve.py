@@ -82,6 +82,48 @@ def restricted_loads(data: bytes):
     return RestrictedUnpickler(io.BytesIO(data)).load()
 
 
+# ---- which stages a request names ----------------------------------------------------------------------------------------------------
+STAGE_MODES = ("fixed", "config")
+FIXED_STAGE_KEYS = ("ctd", "48px", "lama_mpe")                # what a worker in "fixed" mode serves whatever the request says
+DEFAULT_STAGE_KEYS = ("default", "48px", "lama_large")        # the reference's defaults (config.py:274, :312, :294)
+SUPPORTED_STAGE_KEYS = {                                      # (section, field) -> the values this worker has a HIP plugin for
+    ("detector", "detector"): ("default", "dbconvnext", "ctd"),
+    ("ocr", "ocr"): ("48px", "48px_ctc", "32px"),
+    ("inpainter", "inpainter"): ("lama_large", "lama_mpe", "default"),
+}
+DETECTOR_FILTER_OPTIONS = ("det_rotate", "det_auto_rotate", "det_invert", "det_gamma_correct")   # DetectorConfig, config.py:280-286
+
+
+def _field(section, name):
+    """``section.name`` of a config section given as a dict, a pydantic model or a plain object; None when absent.  An enum member
+    (the reference's Detector / Ocr / Inpainter are str enums) gives its value."""
+    if section is None:
+        return None
+    v = section.get(name) if isinstance(section, dict) else getattr(section, name, None)
+    return getattr(v, "value", v)
+
+
+def stage_keys(config) -> Tuple[str, str, str]:
+    """(detector, ocr, inpainter) a request's ``Config`` names: ``config.detector.detector``, ``config.ocr.ocr``,
+    ``config.inpainter.inpainter``, each the reference's default where the field (or its section, or the config) is absent.  Raises
+    ValueError, naming the key and the supported set, for a model this worker has no HIP plugin for (craft, paddle, none, mocr, sd,
+    original, …) and for a detector filter option that is set (rotate / auto-rotate / invert / gamma-correct run inside the reference's
+    ``CommonDetector.detect``, which the worker does not go through): a request is never served by something else silently."""
+    cfg = _as_dict(config)
+    out = []
+    for (section, name), default in zip(SUPPORTED_STAGE_KEYS, DEFAULT_STAGE_KEYS):
+        v = _field(cfg.get(section), name)
+        v = default if v is None else str(v)
+        if v not in SUPPORTED_STAGE_KEYS[(section, name)]:
+            raise ValueError(f"{section}.{name} = {v!r} is not served by this worker (supported: {', '.join(SUPPORTED_STAGE_KEYS[(section, name)])})")
+        out.append(v)
+    for opt in DETECTOR_FILTER_OPTIONS:
+        if _field(cfg.get("detector"), opt):
+            raise ValueError(f"detector.{opt} is set, and this worker does not apply it (supported: {opt} unset / false; the detector "
+                             "runs on the page as it is)")
+    return tuple(out)
+
+
 # ---- what a worker hosts when the orchestrator itself cannot be imported ---------------------------------------------------------------
 class DenseStages:
     """The three HIP plugins of one GPU, chained as ``MangaTranslator._translate`` chains the stages it owns
@@ -91,6 +133,15 @@ class DenseStages:
 
     def __init__(self, params: Optional[dict] = None):
         self.params = dict(params or {})
+        # "fixed" (the default): ctd + 48px + lama_mpe whatever a request names, as this worker has always served.  "config": the
+        # stages the request's Config names (``stage_keys``), each plugin loaded at the first request that asks for it.
+        self.stages = str(self.params.get("stages") or os.environ.get("MIT_SERVE_STAGES") or "fixed").strip().lower()
+        if self.stages not in STAGE_MODES:
+            raise ValueError(f"stages must be one of {STAGE_MODES} (params['stages'], --stages or MIT_SERVE_STAGES; got {self.stages!r})")
+        self._plugins: Dict[Tuple[str, str], object] = {}     # config mode: (stage, key) -> the loaded plugin
+        # the stages self.det / self.ocr / self.inp are (to be) loaded for: ``_select`` sets them from each request
+        self._keys = DEFAULT_STAGE_KEYS if self.stages == "config" else FIXED_STAGE_KEYS
+        self.last_stage_keys: Optional[Tuple[str, str, str]] = None    # (detector, ocr, inpainter) that served the last request
         self._loaded = False
         self._coupled = None
         self.pages_batched = 0     # pages of translate_batch requests that went through one CoupledPageEngine.run with others
@@ -119,8 +170,42 @@ class DenseStages:
         up = _as_dict(cfg.get("upscale")) if cfg.get("upscale") is not None else {}
         return (up.get("upscale_ratio") or 0), bool(up.get("revert_upscaling", False))
 
+    def _select(self, config) -> Tuple[str, str, str]:
+        """The stages that serve a request with this config — ``FIXED_STAGE_KEYS`` in "fixed" mode, ``stage_keys(config)`` in
+        "config" mode — noted for ``_load`` (which brings ``self.det`` / ``self.ocr`` / ``self.inp`` to them) and in ``last_stage_keys``."""
+        self._keys = stage_keys(config) if self.stages == "config" else FIXED_STAGE_KEYS
+        self.last_stage_keys = self._keys
+        return self._keys
+
+    async def _load_selected(self):
+        """Config mode: the plugins of ``self._keys``, each loaded once and kept by (stage, key) like the upscaler — from the checkpoint
+        under ``model_dir``, else seeded synthetic weights (``pipeline.synthetic_stage_weights``), identical in every worker."""
+        from . import pipeline, plugins as P
+
+        classes = {("detector", "ctd"): P.HipComicTextDetector, ("detector", "default"): P.HipDefaultDetector,
+                   ("detector", "dbconvnext"): P.HipDBConvNextDetector, ("ocr", "48px"): P.HipModel48pxOCR,
+                   ("ocr", "48px_ctc"): P.HipModel48pxCTCOCR, ("ocr", "32px"): P.HipModel32pxOCR,
+                   ("inpainter", "lama_mpe"): P.HipLamaMPEInpainter, ("inpainter", "lama_large"): P.HipLamaLargeInpainter,
+                   ("inpainter", "default"): P.HipAotInpainter}
+        got = []
+        for stage, key in zip(("detector", "ocr", "inpainter"), self._keys):
+            if (stage, key) not in self._plugins:
+                if self.params.get("model_dir"):
+                    p = classes[(stage, key)]()
+                else:
+                    d = int(self.params.get("dict_size", 512))
+                    w = pipeline.synthetic_stage_weights(stage, key, dict_size=d)
+                    kw = {"dictionary": ["<PAD>", "<S>", "</S>", "<SP>"] + [chr(0x4E00 + i) for i in range(d - 4)]} if stage == "ocr" else {}
+                    p = classes[(stage, key)](weights=w, **kw)
+                await p.load("cuda")
+                self._plugins[(stage, key)] = p
+            got.append(self._plugins[(stage, key)])
+        self.det, self.ocr, self.inp = got
+
     async def _load(self):
         if self._loaded:
+            if self.stages == "config":
+                await self._load_selected()
             return
         import torch
 
@@ -129,9 +214,16 @@ class DenseStages:
         if not torch.cuda.is_available():
             raise RuntimeError("a serving worker needs its GPU (HIP_VISIBLE_DEVICES selects it); there is no CPU path")
         ckpt = self.params.get("model_dir")
+        if ckpt and not os.path.isdir(ckpt):
+            raise FileNotFoundError(f"--model-dir {ckpt!r} is not a directory")
+        if self.stages == "config":      # the plugins come with the requests (``_load_selected``); a worker loaded before its first
+            if ckpt:                     # request brings up the reference's default stages, so that a missing checkpoint shows at start
+                P.set_model_dir(os.path.abspath(ckpt))
+            self.device_name = torch.cuda.get_device_name(0)
+            await self._load_selected()
+            self._loaded = True
+            return
         if ckpt:      # real checkpoints in the reference's layouts (plugins._load_*_checkpoint), under <model_dir>/<detection|ocr|inpainting>/
-            if not os.path.isdir(ckpt):
-                raise FileNotFoundError(f"--model-dir {ckpt!r} is not a directory")
             P.set_model_dir(os.path.abspath(ckpt))
             self.det, self.ocr, self.inp = P.HipComicTextDetector(), P.HipModel48pxOCR(), P.HipLamaMPEInpainter()
         else:         # no checkpoint offline: seeded synthetic weights of the reference architectures (synth.py), identical in every worker
@@ -149,8 +241,9 @@ class DenseStages:
     async def translate(self, image, config=None):
         from . import mask_refinement as MR, textline_merge as TM
 
-        await self._load()
         cfg = _as_dict(config)
+        keys = self._select(cfg)
+        await self._load()
         page = np.ascontiguousarray(np.asarray(image.convert("RGB") if hasattr(image, "convert") else image, dtype=np.uint8))
         if page.ndim != 3 or page.shape[2] != 3:
             raise ValueError(f"image must be HxWx3 (got {page.shape})")
@@ -162,9 +255,7 @@ class DenseStages:
             up = await self._load_upscaler()
             page = np.ascontiguousarray(up.engine.upscale(torch.from_numpy(page).to(up.engine.device)[None], ratio)[0].cpu().numpy())
         H, W = page.shape[:2]
-        det = cfg.get("detector", {})
-        tls, mask_raw, _ = await self.det.infer(page, int(det.get("detection_size", 1024)), float(det.get("text_threshold", 0.5)),
-                                                float(det.get("box_threshold", 0.7)), float(det.get("unclip_ratio", 2.3)))
+        tls, mask_raw, _ = await self.det.infer(page, *self._detector_args(cfg))
         raw_in = cfg.get("mask_raw")        # a request may bring the raw text mask ([H, W] uint8) instead of the detector's: unlike "mask"
         if raw_in is not None:              # it goes through text-line merge + mask refinement
             mask_raw = np.ascontiguousarray(np.asarray(raw_in, dtype=np.uint8))
@@ -179,9 +270,18 @@ class DenseStages:
 
         class _Cfg:   # OcrConfig.prob (config.py): None unless the request sets it — the plugin then keeps the reference's 0.2 (model_48px.py:104)
             prob = None if ocr.get("prob") is None else float(ocr["prob"])
+            ignore_bubble = int(ocr.get("ignore_bubble", 0) or 0)     # (the ctc and 32px plugins read it from the config)
 
         steps = int(ocr.get("max_seq_length", 255))
-        lines = await self.ocr.infer(page, tls, _Cfg(), False, int(ocr.get("ignore_bubble", 0)), steps, bool(ocr.get("suppress_eos", False))) if tls else []
+        if keys[1] == "48px":
+            ocr_args = (_Cfg(), False, int(ocr.get("ignore_bubble", 0)), steps, bool(ocr.get("suppress_eos", False)))
+        else:       # config mode: Model48pxCTCOCR._infer(image, textlines, config, verbose), Model32pxOCR's with max_seq_length after it
+            if ocr.get("suppress_eos"):
+                raise ValueError(f"ocr.suppress_eos is set, and ocr.ocr = {keys[1]!r} has no such option (supported: ocr.ocr = '48px')")
+            if keys[1] == "48px_ctc" and ocr.get("max_seq_length") is not None:
+                raise ValueError("ocr.max_seq_length is set, and ocr.ocr = '48px_ctc' has no step limit (supported: ocr.ocr = '48px', '32px')")
+            ocr_args = (_Cfg(), False) + ((steps,) if keys[1] == "32px" else ())
+        lines = await self.ocr.infer(page, tls, *ocr_args) if tls else []
         lines = [l for l in lines if l.text.strip()]
         inp = cfg.get("inpainter", {})
         mask_in = cfg.get("mask")          # a request may bring the mask to inpaint ([H, W] uint8) instead of the refined detector mask
@@ -248,6 +348,15 @@ class DenseStages:
                 plan.append((run, "" if len(run) > 1 else "alone in its size group"))
         return sorted(plan, key=lambda e: e[0][0])
 
+    def _detector_args(self, cfg: dict) -> Tuple[int, float, float, float]:
+        """(detect_size, text_threshold, box_threshold, unclip_ratio) of a request: DetectorConfig's fields (config.py:274-290), an
+        absent one at the reference's default in "config" mode (2048, 0.5, 0.7, 2.3); "fixed" mode keeps its 1024 for the size (the
+        ctd detector ignores all four)."""
+        det = _as_dict(cfg.get("detector")) if cfg.get("detector") is not None else {}
+        size = det.get("detection_size")
+        return (int(size) if size is not None else (2048 if self.stages == "config" else 1024), float(det.get("text_threshold", 0.5)),
+                float(det.get("box_threshold", 0.7)), float(det.get("unclip_ratio", 2.3)))
+
     def _loop_reason(self, page: np.ndarray, cfg: dict) -> Optional[str]:
         """Why a page cannot join a coupled run (None: it can)."""
         from . import rearrange
@@ -256,7 +365,13 @@ class DenseStages:
             return "not HxWx3"
         if self._upscale_options(cfg)[0]:
             return "upscale"
-        if rearrange.plan(page.shape[0], page.shape[1], 1024) is not None and not getattr(self._coupled_engine(), "takes_strips", False):
+        if self._keys[1] != "48px":     # (config mode only) the coupled engine is written around the 48px model's pooled beam search
+            return f"ocr.ocr = {self._keys[1]} is not in the coupled engine"
+        # a strip is one at the size its detector tiles at: 1024 for ctd whatever the request says (ctd.py:84), detection_size for DBNet
+        size = 1024 if self._keys[0] == "ctd" else self._detector_args(cfg)[0]
+        if rearrange.plan(page.shape[0], page.shape[1], size) is not None and not getattr(self._coupled_engine(), "takes_strips", False):
+            if self._keys[0] != "ctd":
+                return f"webtoon strip with detector.detector = {self._keys[0]} (DBNet strips are not batched)"
             return "webtoon strip (rearranged detection)"      # (the engine is asked only when the page is a strip)
         if int(_as_dict(cfg.get("ocr", {})).get("ignore_bubble", 0)):
             return "ocr.ignore_bubble is not implemented by the coupled engine"
@@ -289,9 +404,10 @@ class DenseStages:
         ``device_info`` say which way the pages went."""
         import torch
 
-        await self._load()
         images = list(images)
         cfgs = self.page_configs(config, len(images))
+        self._select(cfgs[0] if cfgs else config)     # (the pages of a request share everything but textlines / mask / mask_raw)
+        await self._load()
         pages = [np.ascontiguousarray(np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.uint8)) for im in images]
         plan = self.plan_batches([p.shape[:2] for p in pages], [self._loop_reason(p, c) for p, c in zip(pages, cfgs)], int(batch_size))
         self.last_batch_plan = plan
@@ -312,14 +428,23 @@ class DenseStages:
                     raise ValueError(f"mask must be {H}x{W} (got {np.asarray(m).shape})")
             eng = self._coupled_engine()
             pages_dev = torch.from_numpy(np.stack([pages[i] for i in idx])).to(eng.device)      # one upload per group
+            det_kw = {}
+            if self.stages == "config":     # the detector's parameters travel with the run (a DBNet engine uses them, ctd ignores them)
+                det_kw = dict(zip(("detect_size", "text_threshold", "box_threshold", "unclip_ratio"), self._detector_args(cfg)))
+                for i in idx:               # the page loop's check (translate): a request's raw mask is page-sized
+                    m = cfgs[i].get("mask_raw")
+                    if m is not None and np.asarray(m).shape != (H, W):
+                        raise ValueError(f"mask_raw must be {H}x{W} (got {np.asarray(m).shape})")
             r = eng.run(pages_dev, max_seq_length=int(ocr.get("max_seq_length", 255)), suppress_eos=bool(ocr.get("suppress_eos", False)),
                         prob_threshold=0.2 if ocr.get("prob") is None else float(ocr["prob"]),
                         textlines=[cfgs[i].get("textlines") for i in idx], mask_raw=[cfgs[i].get("mask_raw") for i in idx],
                         mask=[cfgs[i].get("mask") for i in idx], mask_dilation_offset=int(cfg.get("mask_dilation_offset", 20)),
                         kernel_size=int(cfg.get("kernel_size", 3)), inpainting_size=int(inp.get("inpainting_size", 2048)),
-                        precision=self._inpaint_precision())
+                        precision=self._inpaint_precision(), **det_kw)
             self.last_coupled_seconds.append(dict(r.seconds))
-            mask_raw, mask, out = r.mask_raw.cpu().numpy(), r.mask.cpu().numpy(), r.inpainted.cpu().numpy()
+            # (a DBNet run's raw masks have the detector's size, and come as a per-page list once a request replaced some of them)
+            mask_raw = [m.cpu().numpy() for m in r.mask_raw] if isinstance(r.mask_raw, list) else r.mask_raw.cpu().numpy()
+            mask, out = r.mask.cpu().numpy(), r.inpainted.cpu().numpy()
             for k, i in enumerate(idx):
                 results[i] = {"textlines": [{"pts": np.asarray(l.pts).tolist(), "text": l.text, "prob": float(l.prob),
                                              "fg": [int(l.fg_r), int(l.fg_g), int(l.fg_b)], "bg": [int(l.bg_r), int(l.bg_g), int(l.bg_b)]}
@@ -334,7 +459,8 @@ class DenseStages:
         import torch
 
         return {"device": self.device_name, "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES"), "n_visible": torch.cuda.device_count(),
-                "pid": os.getpid(), "pages_batched": self.pages_batched, "pages_looped": self.pages_looped}
+                "pid": os.getpid(), "pages_batched": self.pages_batched, "pages_looped": self.pages_looped, "stages": self.stages,
+                "last_stage_keys": self.last_stage_keys}
 
 
 def _as_dict(config) -> dict:
@@ -717,12 +843,15 @@ def _main(argv=None) -> int:
     w.add_argument("--model-dir", default=None, help="directory with the reference's checkpoints; synthetic weights without it")
     w.add_argument("--dict-size", type=int, default=512)
     w.add_argument("--esrgan-blocks", type=int, default=23, help="RRDB blocks of the synthetic upscaler weights (without --model-dir)")
+    w.add_argument("--stages", choices=STAGE_MODES, default=None,
+                   help="fixed: ctd + 48px + lama_mpe whatever a request names (default); config: the detector / ocr / inpainter the request's "
+                        "Config names, loaded at first use (MIT_SERVE_STAGES sets the default)")
     w.add_argument("--lazy", action="store_true", help="load the plugins at the first request instead of before listening (default: before, so "
                                                       "that a worker without its GPU or its checkpoints never reports ready)")
     w.add_argument("--preload", action="store_true", help=argparse.SUPPRESS)   # the default since round 6
     a = ap.parse_args(argv)
     params = {"host": a.host, "port": a.port, "nonce": a.nonce, "model_dir": a.model_dir, "dict_size": a.dict_size, "esrgan_blocks": a.esrgan_blocks,
-              "use_gpu": True}
+              "use_gpu": True, "stages": a.stages}
     worker = make_worker(params)
     loop = asyncio.new_event_loop()
     asyncio.set_event_loop(loop)

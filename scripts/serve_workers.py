@@ -30,8 +30,11 @@ def main() -> int:
     ap.add_argument("--server-nonce", default=None, help="the front server's nonce (defaults to --nonce)")
     ap.add_argument("--model-dir", default=None)
     ap.add_argument("--preload", action="store_true")
+    ap.add_argument("--stages", choices=serve.STAGE_MODES, default=None,
+                    help="fixed: every worker serves ctd + 48px + lama_mpe (default); config: the detector / ocr / inpainter each request's "
+                         "Config names (MIT_SERVE_STAGES sets the default)")
     a = ap.parse_args()
-    wargs = (["--model-dir", a.model_dir] if a.model_dir else []) + (["--preload"] if a.preload else [])
+    wargs = (["--model-dir", a.model_dir] if a.model_dir else []) + (["--preload"] if a.preload else []) + (["--stages", a.stages] if a.stages else [])
     pool = serve.WorkerPool(host=a.host, base_port=a.base_port, nonce=a.nonce, worker_args=wargs)
     signal.signal(signal.SIGTERM, lambda *_: (pool.stop(), sys.exit(0)))
     try:
