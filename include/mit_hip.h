@@ -995,6 +995,59 @@ int mit_ocr32_decode(const MitOcr32Decoder *dec, MitOcr32DecodeArgs *args, void 
  * trace_hist ([steps][N*5][T+2]) of args (N, max_seq_length, start_tok, end_tok, max_finished, workspace as for the decode). */
 int mit_ocr32_beam_replay(const float *vals_dev, const int32_t *idx_dev, int steps, MitOcr32DecodeArgs *args, void *stream);
 
+/* ESRGAN dense blocks on bf16-resident activations (additive in ABI 25) ------------------------------------------------------------
+ * mit_rdb_conv3x3_bf16 — the 3x3, stride 1, zero-pad 1 convolution of ResidualDenseBlock_5C (upscaling/esrgan_pytorch.py:152-166) for
+ * the upscaler's bf16 precision, on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  The dense block lives in one bf16 NHWC buffer
+ * [B,H,W,ld] = [x | x1 | x2 | x3 | x4]; a launch reads its first Cin channels and may write its N results into a later channel slice of
+ * the SAME buffer.  A workgroup owns MIT_RDB_TILE_H x MIT_RDB_TILE_W output pixels: per chunk of 32 input channels it stages the tile
+ * plus its one-pixel halo (zeros outside the image) and the chunk's 9 x 32 weight rows to LDS once and serves all nine taps from
+ * there; nothing is rounded or split in the kernel on the way to the MFMA.
+ *
+ *   acc[n]  = sum_{tap = (ky, kx)} sum_{c < Cin} in[b, y + ky - 1, x + kx - 1, c] * w[(tap * Cin + c) * N + n]        (fp32, exact products)
+ *   v       = acc * scale[n] + bias[n]                  scale NULL = 1, bias NULL = 0; two rounded operations, no FMA
+ *   v       = act == MIT_ACT_LEAKY ? (v >= 0 ? v : v * act_alpha) : v
+ *   v       = v + post[b, y, x, n]                      when post  != NULL
+ *   v       = v * s2 + post2[b, y, x, n]                when post2 != NULL   (the RRDB's outer x * 0.2 + rrdb_in, :139-148)
+ *   out_f32[b, y, x, n] = v                             when out_f32  != NULL
+ *   out_bf16[b, y, x, n] = bf16(v)                      when out_bf16 != NULL: round to nearest even of the fp32 value, the bits of
+ *                                                       torch.Tensor.to(torch.bfloat16)
+ * A pixel's result depends on nothing but its own 3 x 3 x Cin window: not on B, the tile it falls in or the launch's other images.
+ *
+ * Requirements (anything else is refused before any HIP call): Cin % 32 == 0 and 64 <= Cin <= 192; N 32 or 64; act NONE or LEAKY;
+ * at least one output; B, H, W > 0; every x stride >= the channels addressed through it, y stride >= x stride, batch stride >= 0;
+ * in, w 16-byte aligned and the input strides multiples of 8 elements (16-byte loads); one image of every tensor spans fewer than
+ * 2^31 elements (image bases are 64-bit, offsets inside an image 32-bit); ceil(H / MIT_RDB_TILE_H) and B <= 65535 (grid y / z);
+ * out_bf16 must not overlap the Cin input channels (same strides: disjoint channel ranges; other strides: disjoint extents).
+ * All strides are element counts of the tensor's own type. */
+#define MIT_RDB_TILE_H 8
+#define MIT_RDB_TILE_W 32
+typedef struct MitRdbConv {
+    const uint16_t *in;               /* bf16 bits, NHWC */
+    int64_t in_bs, in_ys, in_xs;
+    int32_t B, H, W, Cin;
+    const uint16_t *w;                /* [9 * Cin][N] bf16 bits, k = (ky * 3 + kx) * Cin + c */
+    int32_t N;
+    int32_t act;
+    float act_alpha;
+    float s2;
+    const float *scale, *bias;        /* [N] */
+    const float *post;
+    int64_t post_bs, post_ys, post_xs;
+    const float *post2;
+    int64_t post2_bs, post2_ys, post2_xs;
+    float *out_f32;
+    int64_t of_bs, of_ys, of_xs;
+    uint16_t *out_bf16;
+    int64_t ob_bs, ob_ys, ob_xs;
+} MitRdbConv;
+int mit_rdb_conv3x3_bf16(const MitRdbConv *d, void *stream);
+/* dst[b, y, x, c] = bf16(src[b, y, x, c]) for c < Cn: an NHWC channel-slice cast, fp32 -> bf16 bits, round to nearest even (the bits of
+ * torch.Tensor.to(torch.bfloat16)); element strides, x stride >= Cn, y stride >= x stride, batch stride >= 0.  Puts ``fea`` into the
+ * first 64 channels of the dense-block buffer.  Four channels a lane where every stride and base allows (16-byte loads, 8-byte
+ * stores), else one. */
+int mit_cast_f32_bf16(const float *src_dev, int64_t s_bs, int64_t s_ys, int64_t s_xs, uint16_t *dst_dev, int64_t d_bs, int64_t d_ys,
+                      int64_t d_xs, int B, int H, int W, int Cn, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

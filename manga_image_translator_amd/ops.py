@@ -20,11 +20,11 @@ import torch
 
 from . import lib as _lib
 from .lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_SIGMOID, ACT_SILU, MIT_MAX_TAPS, PAD_REFLECT,
-                  PAD_ZERO, MitConvGemm, MitPGemm, MitTensorMap)
+                  PAD_ZERO, MitConvGemm, MitPGemm, MitRdbConv, MitTensorMap)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "ACT_LEAKY", "ACT_SILU", "ACT_SIGMOID", "ACT_GELU", "ACT_POST_FIRST", "PAD_ZERO", "PAD_REFLECT",
-    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "current_stream",
+    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "pack_rdb_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "current_stream",
 ]
 
 
@@ -675,7 +675,8 @@ class UpsampleConv2d:
                 self.sub.append((a, b, _Packed(wk, Kp, Np, taps)))
         self.bias = None if bias is None else bias.detach().to(torch.float32).to(device).contiguous()
 
-    def descs(self, x: torch.Tensor, out: torch.Tensor) -> List[MitConvGemm]:
+    def descs(self, x: torch.Tensor, out: torch.Tensor, nprod: int = 0) -> List[MitConvGemm]:
+        """``nprod`` = 1: the four parity launches on the one-product bf16 tiles (MitConvGemm.nprod)."""
         _check_nhwc(x, "UpsampleConv2d input")
         _check_nhwc(out, "UpsampleConv2d output")
         B, H, W, Cx = x.shape
@@ -684,18 +685,90 @@ class UpsampleConv2d:
         ds = []
         for a, b, pk in self.sub:
             ov = out[:, a::2, b::2]
+            if nprod:
+                ensure_split(pk.w)
             ds.append(conv_gemm_desc(
                 a=x, NB=B, Hi=H, Wi=W, Cin=self.Cin, a_strides=(x.stride(0), x.stride(1), x.stride(2)), Ho=H, Wo=W, sy=1, sx=1,
                 taps=pk.taps, pad_mode=PAD_ZERO, w=pk.w, ldw=pk.Np, Kw=pk.Kp, Nw=pk.Np, N=self.Cout, c=tensor_map(ov),
-                bias=self.bias, act=self.act, alpha=self.alpha))
+                bias=self.bias, act=self.act, alpha=self.alpha, nprod=nprod))
         return ds
 
-    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, cfg: int = -1) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, cfg: int = -1, nprod: int = 0) -> torch.Tensor:
         if out is None:
             out = torch.empty(x.shape[0], 2 * x.shape[1], 2 * x.shape[2], self.Cout, dtype=torch.float32, device=x.device)
-        for d in self.descs(x, out):
+        for d in self.descs(x, out, nprod):
             launch_conv_gemm(d, cfg)
         return out
+
+
+def pack_rdb_weight(weight: torch.Tensor) -> torch.Tensor:
+    """[N, Cin, 3, 3] (torch layout) -> bf16 ``[9 * Cin, N]`` with k = (ky * 3 + kx) * Cin + c, rounded to nearest even
+    (``.to(torch.bfloat16)``): the W operand of ``mit_rdb_conv3x3_bf16``.  On the weight's own device."""
+    N, Cin, kh, kw = weight.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError(f"pack_rdb_weight: 3x3 kernels only (got {kh}x{kw})")
+    return weight.detach().to(torch.float32).permute(2, 3, 1, 0).reshape(9 * Cin, N).to(torch.bfloat16).contiguous()
+
+
+def _check_nhwc_as(t: torch.Tensor, dtype, shape, what: str) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or (t.shape[-1] > 1 and t.stride(-1) != 1):
+        raise ValueError(f"{what}: expected {dtype} {tuple(shape)} with channel stride 1, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+
+
+def cast_bf16(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """``dst[...] = src.to(bfloat16)`` for NHWC views (channel slices allowed on both sides) through ``mit_cast_f32_bf16``."""
+    _check_nhwc(src, "cast_bf16 source")
+    _check_nhwc_as(dst, torch.bfloat16, src.shape, "cast_bf16 destination")
+    B, H, W, Cn = src.shape
+    _lib.check(_lib.load().mit_cast_f32_bf16(src.data_ptr(), src.stride(0), src.stride(1), src.stride(2), dst.data_ptr(), dst.stride(0),
+                                             dst.stride(1), dst.stride(2), B, H, W, Cn, C.c_void_p(current_stream())), "mit_cast_f32_bf16")
+    return dst
+
+
+class RdbConv3x3:
+    """A 3x3, stride 1, zero-pad 1 convolution of ESRGAN's dense block on bf16-resident activations: one ``mit_rdb_conv3x3_bf16``
+    launch.  ``x`` is a bf16 NHWC view (the first Cin channels of the block's buffer); the result goes to a bf16 view (which may be a
+    later channel slice of the same buffer), an fp32 view, or both.  ``out_scale`` rides in the epilogue scale with the bias
+    pre-multiplied, as in ``Conv2d``.  weight: [N, Cin, 3, 3]."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act: int = ACT_NONE, alpha: float = 0.0,
+                 out_scale: Optional[torch.Tensor] = None, device="cuda"):
+        self.Cout, self.Cin = int(weight.shape[0]), int(weight.shape[1])
+        self.act, self.alpha = act, alpha
+        self.w = pack_rdb_weight(weight).to(device)
+        bias_t = None if bias is None else bias.detach().to(torch.float32)
+        scale = None
+        if out_scale is not None:
+            scale = out_scale.detach().to(torch.float32).reshape(-1)
+            if bias_t is not None:
+                bias_t = bias_t * scale
+        self.scale = None if scale is None else scale.to(device).contiguous()
+        self.bias = None if bias_t is None else bias_t.to(device).contiguous()
+
+    def desc(self, x: torch.Tensor, *, out_bf16: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None,
+             post: Optional[torch.Tensor] = None, post2: Optional[torch.Tensor] = None, s2: float = 0.0) -> MitRdbConv:
+        """``post``: fp32, added after the activation; ``post2`` with ``s2``: then ``y * s2 + post2`` (MitRdbConv)."""
+        B, H, W, Cx = x.shape
+        _check_nhwc_as(x, torch.bfloat16, (B, H, W, self.Cin), "RdbConv3x3 input")
+        oshape = (B, H, W, self.Cout)
+        d = MitRdbConv()
+        d.B, d.H, d.W, d.Cin, d.N = B, H, W, self.Cin, self.Cout
+        d.in_bs, d.in_ys, d.in_xs = x.stride(0), x.stride(1), x.stride(2)
+        setattr(d, "in", x.data_ptr())   # ``in`` is a keyword
+        d.w, d.scale, d.bias = self.w.data_ptr(), _ptr(self.scale), _ptr(self.bias)
+        d.act, d.act_alpha, d.s2 = self.act, self.alpha, s2
+        for t, dtype, ptr, pre in ((post, torch.float32, "post", "post"), (post2, torch.float32, "post2", "post2"),
+                                   (out_f32, torch.float32, "out_f32", "of"), (out_bf16, torch.bfloat16, "out_bf16", "ob")):
+            if t is None:
+                continue
+            _check_nhwc_as(t, dtype, oshape, f"RdbConv3x3 {ptr}")
+            setattr(d, ptr, t.data_ptr())
+            for ax, nm in enumerate(("bs", "ys", "xs")):
+                setattr(d, f"{pre}_{nm}", t.stride(ax))
+        return d
+
+    def __call__(self, x: torch.Tensor, **kw) -> None:
+        _lib.check(_lib.load().mit_rdb_conv3x3_bf16(C.byref(self.desc(x, **kw)), C.c_void_p(current_stream())), "mit_rdb_conv3x3_bf16")
 
 
 class ConvTranspose2d:

@@ -860,8 +860,21 @@ class HipAotInpainter(HipLamaMPEInpainter):
         self.device = device
 
 
+ESRGAN_PRECISIONS = ("fp32", "bf16")
+
+
+def esrgan_precision_default() -> str:
+    """The ``precision`` of an ESRGAN plugin created without one (``register()``, ``serve.py``): ``MIT_ESRGAN_PRECISION`` in the
+    environment ("fp32" | "bf16"), else "fp32"."""
+    v = os.environ.get("MIT_ESRGAN_PRECISION", "").strip().lower() or "fp32"
+    if v not in ESRGAN_PRECISIONS:
+        raise ValueError(f"MIT_ESRGAN_PRECISION must be one of {ESRGAN_PRECISIONS} (got {v!r})")
+    return v
+
+
 class HipESRGANUpscaler(_EnginePlugin, _UpBase):
-    """``--upscaler 4xultrasharp`` (RRDBNet 4x) on the HIP engine."""
+    """``--upscaler 4xultrasharp`` (RRDBNet 4x) on the HIP engine.  ``precision``: "fp32" (default) or "bf16" (the dense blocks on
+    bf16-resident activations, ``EsrganEngine``); None = ``esrgan_precision_default()``."""
     _KEY = _key = "4xultrasharp_hip"
     _MODEL_MAPPING: Dict = {  # upscaling/esrgan_pytorch.py:513-518
         "4x-UltraSharp": {
@@ -871,8 +884,11 @@ class HipESRGANUpscaler(_EnginePlugin, _UpBase):
     }
     _VALID_UPSCALE_RATIOS = [2, 3, 4]
 
-    def __init__(self, *args, weights: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
+    def __init__(self, *args, weights: Optional[Dict[str, torch.Tensor]] = None, precision: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        self.precision = esrgan_precision_default() if precision is None else precision
+        if self.precision not in ESRGAN_PRECISIONS:      # a bad value raises here, not at the first page
+            raise ValueError(f"ESRGAN precision must be one of {ESRGAN_PRECISIONS} (got {self.precision!r})")
         self._hand_over(weights)
 
     async def _load(self, device: str):
@@ -880,7 +896,7 @@ class HipESRGANUpscaler(_EnginePlugin, _UpBase):
 
         dev = _gpu_device(device)
         sd = self._weights or _load_esrgan_checkpoint(self)
-        self.engine = esrgan.EsrganEngine(sd, nb=_esrgan_blocks(sd), device=dev)
+        self.engine = esrgan.EsrganEngine(sd, nb=_esrgan_blocks(sd), device=dev, precision=self.precision)
         self.device = device
 
     @staticmethod
@@ -912,13 +928,14 @@ class HipESRGANUpscaler(_EnginePlugin, _UpBase):
         for i, p in enumerate(pages):
             groups.setdefault(p.shape[:2], []).append(i)
         out: List = [None] * len(pages)
+        fwd_kw = {} if self.precision == "fp32" else {"precision": self.precision}   # an engine is handed the argument only when it is not fp32
         for (h, w), idx in groups.items():
             mb = max(1, self.MAX_LR_PIXELS // max(1, h * w))
             size = esrgan.pass_size(w, h, upscale_ratio)
             for a in range(0, len(idx), mb):
                 run = idx[a:a + mb]
                 dev = torch.from_numpy(np.ascontiguousarray(np.stack([pages[i] for i in run]))).to(self.engine.device)
-                res = self._pil_resized(self.engine.forward(dev), size, "bilinear").cpu().numpy()
+                res = self._pil_resized(self.engine.forward(dev, **fwd_kw), size, "bilinear").cpu().numpy()
                 for k, i in enumerate(run):
                     out[i] = Image.fromarray(res[k])
         return out
