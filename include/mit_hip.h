@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MIT_ABI_VERSION 25
+#define MIT_ABI_VERSION 26
 #define MIT_MAX_TAPS 64
 
 /* activation codes for fused epilogues */
@@ -824,6 +824,30 @@ typedef struct MitOcr48Decoder {
     int32_t dict_size, _pad;
 } MitOcr48Decoder;
 
+/* Kernel forms of a beam-search step inside mit_ocr48_decode.  Each is taken where the GEMM mode, the row count R = 5 N (lines x
+ * beams) and the packed weights allow; a call can refuse any of them per call (MitOcr48DecodeArgs.forms_off) and reports the ones it
+ * took (forms_run).  Nothing in the reference corresponds to them: forms_off exists so that tests and A/B runs can compare a form with
+ * the one it replaces, production passes 0.  LN_FUSED, Q2_FUSED and FF2_SPLITK exist inside the ROWS form only, Q2_FUSED inside LN_FUSED
+ * only.  All forms give bit-identical results except FF2_SPLITK. */
+#define MIT_OCR48_FORM_ROWS 1        /* the few-row step (pgemm_rows): every Linear of a step as one wave per 32 x 32 output block on
+                                      * bf16-plane activations, the LayerNorm / attention kernels producing the planes — instead of the
+                                      * tiled form that pays off on full batches; a third of the time per Linear at one page.  Needs
+                                      * GEMM mode 6 | 9 and R <= MIT_OCR48_ROWS_MAX */
+#define MIT_OCR48_FORM_LN_FUSED 2    /* LayerNorm inside the consuming Linear (norm1 / norm2 / norm3 computed by the waves of the
+                                      * Linear that reads them) instead of two launches */
+#define MIT_OCR48_FORM_Q2_FUSED 4    /* norm2 + q projection inside the cross-attention kernel instead of separate launches; GEMM
+                                      * mode 6 and up to 128 lines */
+#define MIT_OCR48_FORM_FF2_SPLITK 8  /* K-cut FFN output Linear (<= 640 rows): K = 2048 cut across the four waves of a workgroup and
+                                      * summed in a fixed order.  Its sums round differently from the k-sequential chain every other
+                                      * form uses, so a page decoded alone differs from the same page inside a group of more than 640
+                                      * rows in the last bits of the log-probabilities (tokens equal, probabilities within 1e-4); with
+                                      * it off the step is bit for bit the tiled form */
+#define MIT_OCR48_FORM_SELF_ROWS 16  /* row-staged self-attention kernel: one workgroup per row stages the row's key history once for
+                                      * its four heads (attention_self_kernel) instead of one single-wave workgroup per (head, row)
+                                      * (attention_kernel) */
+#define MIT_OCR48_ROWS_MAX 2560      /* rows up to which FORM_ROWS is taken (16 pages of 32 lines): measured equal to the 64 x 64
+                                      * split tiles there, 2-3.5x faster per Linear at 160 .. 640 rows */
+
 typedef struct MitOcr48DecodeArgs {
     int32_t N, L;               /* text lines; padded encoder-memory length */
     const float *mem_k;         /* [5][N][L][320] cross-attention keys (k_proj + XPOS) per decoder layer */
@@ -841,6 +865,8 @@ typedef struct MitOcr48DecodeArgs {
     float *trace_logits;        /* optional [T][N*5][dict] raw logits (pred(pred1(decoded)), :713); NULL in production */
     int32_t *trace_hist;        /* optional [T][N*5][T+1] beam tokens after each step */
     int32_t steps_run;          /* out: steps executed */
+    int32_t forms_off;          /* MIT_OCR48_FORM_* this call must not take; 0 = what ships */
+    int32_t forms_run;          /* out: MIT_OCR48_FORM_* at least one step of this call took */
 } MitOcr48DecodeArgs;
 
 /* One text line to rectify: cv2.warpPerspective of the page crop [y1:y1+ch, x1:x1+cw] to (dw, dh) with inverse map minv
@@ -892,10 +918,6 @@ int mit_attention(const float *q_dev, int64_t q_rs, int64_t q_ts, const float *k
 int mit_attention_lines_xpos(const float *q_dev, const float *k_dev, const float *v_dev, float *out_dev, int64_t row_stride,
                              const int32_t *lines_dev, const int *klen_dev, int n_lines, int Lmax, int heads, int head_dim,
                              const MitXposTables *tables, void *stream);
-/* The decoder's self-attention kernel: 1 (default) = one workgroup per row stages the row's key history once for its four heads
- * (attention_self_kernel), 0 = one single-wave workgroup per (head, row) (attention_kernel); bitwise the same results.  on < 0 only
- * queries.  Returns the previous value.  Nothing in the reference corresponds to it (A/B switch). */
-int mit_attention_self_rows_set(int on);
 /* Longest line (Lmax) whose keys + per-wave score rows fit mit_attention_lines_xpos's LDS form for this head_dim (308 at head_dim 80);
  * longer lines take the chunk-by-chunk path (mit_xpos_rotate + mit_attention), which has no such limit.  0 for an unsupported head_dim. */
 int mit_attention_lines_xpos_max_len(int head_dim);
@@ -926,20 +948,16 @@ int mit_sigmoid_inplace(float *x_dev, int64_t n, void *stream);
 /* x <- gelu(x) (erf form) over n floats: the nn.GELU of char_pred_norm (model_48px_ctc.py:435). */
 int mit_gelu_inplace(float *x_dev, int64_t n, void *stream);
 /* log_softmax over D columns + the 5 largest (value, index) per row, ties to the lower index; suppress_tok < 0: none.
- * Row r: vals_dev[5r..], idx_dev[5r..].  decode_ctc_top1's log_softmax + max (model_48px_ctc.py:477-478) uses entry 0. */
+ * Row r: vals_dev[5r..], idx_dev[5r..].  decode_ctc_top1's log_softmax + max (model_48px_ctc.py:477-478) uses entry 0.
+ * loop_form 0: a thread's elements loaded once and every pass on registers where D allows (what every model runs); non-zero: the
+ * three-pass loop form for every D — bit for bit the same values and indices (tests/test_ocr_gpu.py compares the two). */
 int mit_logsoftmax_top5(const float *logits_dev, int64_t ld, int R, int D, int suppress_tok, float *vals_dev, int *idx_dev,
-                        void *stream);
+                        int loop_form, void *stream);
 /* The whole beam search of OCR.infer_beam_batch_tensor (:691-784) after the encoder, as one native call: per step
  * embedding -> 5 decoder layers (KV cache instead of the reference's per-step K/V recomputation) -> pred1/pred ->
  * log-softmax/top-5 -> beam bookkeeping, all on `stream`; synchronises the stream every few steps to test for early exit. */
 int64_t mit_ocr48_decode_workspace_bytes(int N, int T, int dict_size);
 int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *args, void *stream);
-/* Largest number of decoder rows (5 N: lines x beams) whose steps run in the few-row form — every Linear of a step as one wave per
- * 32 x 32 output block on bf16-plane activations (pgemm_rows_kernel), the LayerNorm / attention kernels producing the planes — instead
- * of the tiled form that pays off on full batches.  Both forms give identical results (tests/test_ocr_gpu.py); the few-row one takes a
- * third of the time per Linear at one page.  Needs GEMM mode 6 | 9.  rows < 0 only queries; 0 = never.  Initial value 2560 (16 pages of
- * 32 lines).  Returns the previous value.  Nothing in the reference corresponds to it. */
-int mit_ocr48_decode_rows_max_set(int rows);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * 32px OCR (``--ocr 32px``): reference manga_translator/ocr/model_32px.py.  Backbone and encoder run on the entry points above

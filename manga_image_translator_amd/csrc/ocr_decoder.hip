@@ -11,9 +11,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "../../include/mit_hip.h"
-#include <atomic>
 #include "common.h"
 #include "ocr_kernels.h"
 #include "pgemm_rows.h"
@@ -79,15 +77,8 @@ __global__ void fill_int_kernel(int *p, int64_t n, int v) {
     for (; i < n; i += stride) p[i] = v;
 }
 
-std::atomic<int> g_rows_max{2560};  // 16 pages of 32 lines
-int rows_max_now() { return g_rows_max.load(std::memory_order_relaxed); }
+constexpr int FORMS_ALL = MIT_OCR48_FORM_ROWS | MIT_OCR48_FORM_LN_FUSED | MIT_OCR48_FORM_Q2_FUSED | MIT_OCR48_FORM_FF2_SPLITK | MIT_OCR48_FORM_SELF_ROWS;
 }  // namespace
-
-extern "C" int mit_ocr48_decode_rows_max_set(int rows) {
-    const int prev = rows_max_now();
-    if (rows >= 0) g_rows_max.store(rows, std::memory_order_relaxed);
-    return prev;
-}
 
 extern "C" int64_t mit_ocr48_decode_workspace_bytes(int N, int T, int dict_size) {
     if (N <= 0 || T <= 0 || dict_size <= 0) return 0;
@@ -96,6 +87,8 @@ extern "C" int64_t mit_ocr48_decode_workspace_bytes(int N, int T, int dict_size)
 
 extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *a, void *stream) {
     if (!dec || !a) return mit_set_error("mit_ocr48_decode: null argument");
+    const int forms_off = a->forms_off;
+    if (forms_off & ~FORMS_ALL) return mit_set_error("mit_ocr48_decode: unknown bits in forms_off");
     const int N = a->N, L = a->L, T = a->max_seq_length, D = dec->dict_size;
     if (N <= 0 || L <= 0 || T <= 0) return mit_set_error("mit_ocr48_decode: empty problem");
     if (!a->mem_k || !a->mem_v || !a->mem_len || !a->workspace || !a->res_tok || !a->res_len || !a->res_prob || !a->res_row || !a->colors)
@@ -121,28 +114,27 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
 
     int cur = 0, steps = 0;
     // One beam-search step is a launch sequence on the stream (body below); its step-dependent arguments are host values.
-    // rows_path: the few-row form of a step (see body).  mit_ocr48_decode_rows_max_set: largest R = 5 N it is used for; measured equal to
-    // the 64 x 64 split tiles at R = 2560 (16 pages) and 2-3.5x faster per Linear at R = 160 .. 640 (profiles/r04u_pgemm_rows.log)
-    const int rows_max = rows_max_now();
+    // rows_path: the few-row form of a step (see body).  MIT_OCR48_ROWS_MAX: largest R = 5 N it is used for; measured equal to
+    // the 64 x 64 split tiles at R = 2560 (16 pages) and 2-3.5x faster per Linear at R = 160 .. 640 (profiles/r04u_pgemm_rows.log).
+    // Which forms a call takes: the conditions below and a->forms_off (mit_hip.h, MIT_OCR48_FORM_*) — per call, no process-wide switch.
     const int gmode = mit_gemm_mode_get();
-    bool rows_path = (gmode == 6 || gmode == 9) && R <= rows_max && rows_ok(dec->pred1) && dec->pred.w_split &&
+    bool rows_path = (gmode == 6 || gmode == 9) && R <= MIT_OCR48_ROWS_MAX && !(forms_off & MIT_OCR48_FORM_ROWS) && rows_ok(dec->pred1) && dec->pred.w_split &&
                      dec->pred.Kp == dec->pred.K && (dec->pred.K % 16) == 0 && (dec->pred.N % 4) == 0;
     for (int l = 0; l < 5 && rows_path; ++l) {
         const MitOcrDecoderLayer &ly = dec->layers[l];
         rows_path = rows_ok(ly.qkv) && rows_ok(ly.out) && rows_ok(ly.q2) && rows_ok(ly.out2) && rows_ok(ly.ff1) && rows_ok(ly.ff2);
     }
-    // LayerNorm inside the Linear that consumes it (read per call: tests switch it in-process; MIT_OCR_LN_FUSED=0 = the two-launch form)
-    const char *lnf_env = getenv("MIT_OCR_LN_FUSED");
-    const bool ln_fused = rows_path && !(lnf_env && *lnf_env && atoi(lnf_env) == 0);
+    // LayerNorm inside the Linear that consumes it (else the two-launch form)
+    const bool ln_fused = rows_path && !(forms_off & MIT_OCR48_FORM_LN_FUSED);
     // The FFN's second Linear (K = 2048) with K cut across four waves: for FEW rows only (a page or two, where its 10 us accumulator chain
     // is a sixth of the step) — its sums round differently from the k-sequential chain every other form uses, so a page decoded alone
     // differs from the same page inside a large group in the last bits of the log-probabilities (tests: tokens equal, 1e-5 on the
-    // probabilities).  MIT_OCR_FF2_SPLITK=0 keeps the one-chain kernel (bit for bit the tiled form); read per call.
-    // norm2 + q projection inside the cross-attention kernel (MIT_OCR_Q2_FUSED=0 = separate launches; bit-identical either way; gemm mode 6 only)
-    const char *q2_env = getenv("MIT_OCR_Q2_FUSED");
-    const bool q2_fused = ln_fused && gmode == 6 && !(q2_env && *q2_env && atoi(q2_env) == 0);
-    const char *sk_env = getenv("MIT_OCR_FF2_SPLITK");
-    const int ff2_splitk = (rows_path && R <= FF2_SPLITK_MAX_ROWS && !(sk_env && *sk_env && atoi(sk_env) == 0)) ? 1 : 0;
+    // probabilities).  Without it: the one-chain kernel (bit for bit the tiled form).
+    const int ff2_splitk = (rows_path && R <= FF2_SPLITK_MAX_ROWS && !(forms_off & MIT_OCR48_FORM_FF2_SPLITK)) ? 1 : 0;
+    // norm2 + q projection inside the cross-attention kernel (else separate launches; bit-identical either way; gemm mode 6 only)
+    const bool q2_fused = ln_fused && gmode == 6 && !(forms_off & MIT_OCR48_FORM_Q2_FUSED);
+    const bool per_head_self = forms_off & MIT_OCR48_FORM_SELF_ROWS;
+    int forms_run = (rows_path ? MIT_OCR48_FORM_ROWS : 0) | (ln_fused ? MIT_OCR48_FORM_LN_FUSED : 0) | (ff2_splitk ? MIT_OCR48_FORM_FF2_SPLITK : 0);
     auto body = [&](const int step, hipStream_t st) -> int {
         const int64_t so = (int64_t)step * E;  // the step's column block of the q / k / v and activation caches
         // (w.tgt holds the embedded tokens of this step: the start tokens before the loop, then written by the previous step's beam kernel)
@@ -165,7 +157,8 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                     if (pgemm(ly.qkv, w.nrm_p, Rp, R, qc + so, TE, MIT_ACT_NONE, nullptr, 0, nullptr, 0, st, E, (int64_t)R * TE)) return 1;
                 }
                 OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1};
-                ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, nullptr, 0, 0, nullptr, R, 1, Tk, 1, st, 4, 80, &xs, &att_pl);
+                if (ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, nullptr, 0, 0, nullptr, R, 1, Tk, 1, st, 4, 80, &xs, &att_pl, per_head_self) == OcrAttKernel::SelfRows)
+                    forms_run |= MIT_OCR48_FORM_SELF_ROWS;
                 if (pgemm(ly.out, w.att_p, Rp, R, w.tgt, E, MIT_ACT_NONE, w.tgt, E, nullptr, 0, st)) return 1;
                 const float *mk = a->mem_k + (int64_t)l * N * L * E;
                 const float *mv = a->mem_v + (int64_t)l * N * L * E;
@@ -175,6 +168,7 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 if (q2_fused && ly.q2.bias && ly.q2.N == E) {
                     const OcrAttQProj qp{w.tgt, E, ly.ln2_w, ly.ln2_b, 1e-5f, ly.q2.w_split, ly.q2.ldw, ly.q2.scale, ly.q2.bias};
                     q_inside = ocrk_cross_attention_qproj(qp, mk, (int64_t)L * E, E, mv, (int64_t)L * E, E, a->mem_len, R, L, st, &xc, &att_pl);
+                    if (q_inside) forms_run |= MIT_OCR48_FORM_Q2_FUSED;
                 }
                 if (!q_inside) {
                     if (ln_fused) {
@@ -211,7 +205,8 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
                 if (gemm(ly.qkv, w.nrm, E, qc + so, TE, R, MIT_ACT_NONE, nullptr, 0, st, E, (int64_t)R * TE)) return 1;
                 // (the XPOS rotation of the step's query and of the key history 0 .. step happens inside the attention kernel)
                 OcrAttXpos xs{dec->xpos.cos_t, dec->xpos.sin_t, dec->xpos.scale_t, dec->xpos.iscale_t, dec->xpos.pmax, step, 1};
-                ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, w.att, E, E, nullptr, R, 1, Tk, 1, st, 4, 80, &xs);
+                if (ocrk_attention(qc + so, TE, E, kc, TE, E, vc, TE, E, w.att, E, E, nullptr, R, 1, Tk, 1, st, 4, 80, &xs, nullptr, per_head_self) == OcrAttKernel::SelfRows)
+                    forms_run |= MIT_OCR48_FORM_SELF_ROWS;
                 if (gemm(ly.out, w.att, E, w.tgt, E, R, MIT_ACT_NONE, w.tgt, E, st)) return 1;
                 // cross attention (:567)
                 if (ocrk_layernorm(w.tgt, E, ly.ln2_w, ly.ln2_b, w.nrm, E, R, E, 1e-5f, st)) return 1;
@@ -268,5 +263,6 @@ extern "C" int mit_ocr48_decode(const MitOcr48Decoder *dec, MitOcr48DecodeArgs *
     if (gemm(dec->color_heads, w.cfeat, 64, a->colors, 12, R * T, MIT_ACT_NONE, nullptr, 0, s)) return 1;
     MIT_CHECK_LAUNCH("mit_ocr48_decode");
     a->steps_run = steps;
+    a->forms_run = forms_run;
     return 0;
 }

@@ -23,10 +23,13 @@ struct OcrAttXpos {
     const float *cos_t, *sin_t, *scale_t, *iscale_t;   // cos_t == NULL: no rotation
     int pmax, step, rot_k;
 };
-void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, int64_t k_rs, int64_t k_ts, const float *V,
-                    int64_t v_rs, int64_t v_ts, float *O, int64_t o_rs, int64_t o_ts, const int *klen, int R, int Tq, int Tk,
-                    int kv_div, hipStream_t s, int heads = 4, int head_dim = 80,
-                    const OcrAttXpos *xpos = nullptr, const OcrPlanes *o_planes = nullptr);   // o_planes: instead of O (Tq == 1, head_dim % 8 == 0)
+// Returns the kernel it launched.  per_head_self: the decoder's self-attention on attention_kernel, not on attention_self_kernel.
+enum class OcrAttKernel { SharedKv, Rows, SelfRows, PerHead };
+OcrAttKernel ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, int64_t k_rs, int64_t k_ts, const float *V,
+                            int64_t v_rs, int64_t v_ts, float *O, int64_t o_rs, int64_t o_ts, const int *klen, int R, int Tq, int Tk,
+                            int kv_div, hipStream_t s, int heads = 4, int head_dim = 80,
+                            const OcrAttXpos *xpos = nullptr, const OcrPlanes *o_planes = nullptr,   // o_planes: instead of O (Tq == 1, head_dim % 8 == 0)
+                            bool per_head_self = false);
 // The q projection of the decoder's cross-attention inside its attention kernel (few rows; heads 4 x 80, 5 beams per line):
 // q = LayerNorm(x) @ W + bias, W as the planes of pgemm_rows.h.  Bit for bit mit_pgemm_rows_ln + ocrk_attention.
 struct OcrAttQProj {
@@ -43,7 +46,7 @@ bool ocrk_cross_attention_qproj(const OcrAttQProj &qp, const float *K, int64_t k
                                 const int *klen, int R, int Tk, hipStream_t s, const OcrAttXpos *xpos, const OcrPlanes *o_planes);
 void ocrk_embed(const int *tok, int64_t tok_stride, const float *E, float *out, int R, int D, hipStream_t s);
 void ocrk_logsoftmax_top5(const float *logits, int64_t ld, int R, int D, int suppress_tok, float *vals, int *idx,
-                          float *logp_out, hipStream_t s);
+                          float *logp_out, hipStream_t s, bool loop_form = false);   // loop_form: logsoftmax_top5_kernel<0> for every D
 // next_E / next_out / next_D (beam kernels, optional): the embedding rows [R][next_D] of the tokens just chosen = the residual stream of
 // the next step, written by the bookkeeping kernel instead of a separate ocrk_embed launch at the head of that step
 void ocrk_beam_init(const float *vals, const int *idx, int *hist, int hist_ld, float *logp, int N, int start_tok,

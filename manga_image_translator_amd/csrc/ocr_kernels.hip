@@ -7,10 +7,8 @@
 // ocr/xpos_relative_position.py (:9-71).
 
 #include <hip/hip_runtime.h>
-#include <atomic>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include "../../include/mit_hip.h"
 #include "common.h"
 #include "ocr_kernels.h"
@@ -1632,18 +1630,12 @@ __global__ void memory_kv_lines_kernel(const float *__restrict__ Kf, const float
     }
 }
 
-// the decoder's self-attention on attention_self_kernel (1, default) or on attention_kernel (0): same bits either way
-// (tests/test_ocr_gpu.py), a switch for A/B runs
-static std::atomic<int> g_att_self_rows{1};
-extern "C" int mit_attention_self_rows_set(int on) {
-    const int prev = g_att_self_rows.load(std::memory_order_relaxed);
-    if (on >= 0) g_att_self_rows.store(on ? 1 : 0, std::memory_order_relaxed);
-    return prev;
-}
-
-void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, int64_t k_rs, int64_t k_ts, const float *V,
-                    int64_t v_rs, int64_t v_ts, float *O, int64_t o_rs, int64_t o_ts, const int *klen, int R, int Tq, int Tk,
-                    int kv_div, hipStream_t s, int heads, int head_dim, const OcrAttXpos *xpos, const OcrPlanes *o_planes) {
+// per_head_self: the decoder's self-attention on attention_kernel instead of attention_self_kernel: same bits either way
+// (tests/test_ocr_gpu.py), for A/B runs
+OcrAttKernel ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, int64_t k_rs, int64_t k_ts, const float *V,
+                            int64_t v_rs, int64_t v_ts, float *O, int64_t o_rs, int64_t o_ts, const int *klen, int R, int Tq, int Tk,
+                            int kv_div, hipStream_t s, int heads, int head_dim, const OcrAttXpos *xpos, const OcrPlanes *o_planes,
+                            bool per_head_self) {
     OcrAttXpos xp{};
     if (xpos) xp = *xpos;
     const OcrPlanes opl = (o_planes && Tq == 1) ? *o_planes : OcrPlanes{nullptr, 0, 0};
@@ -1656,13 +1648,13 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
             MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops);
             hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK_L, ATT_STAGE_L, 80, 5>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes(ATT_KCHUNK_L), s, Q, q_rs,
                                K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, xp, opl, OcrAttQProj{});
-            return;
+            return OcrAttKernel::SharedKv;
         }
         if (ATT_KCHUNK * (head_dim / 4) <= ATT_STAGE * ATT_THREADS && lds_bytes(ATT_KCHUNK) <= 64 * 1024) {
             MitProbeScope probe("attention_shared_kv_kernel", s, bytes, flops);
             hipLaunchKernelGGL((attention_shared_kv_kernel<ATT_KCHUNK, ATT_STAGE, 80, 5>), dim3(heads, R / kv_div), dim3(ATT_THREADS), lds_bytes(ATT_KCHUNK), s, Q, q_rs, K,
                                k_rs, k_ts, V, v_rs, v_ts, O, o_rs, klen, Tk, xp, opl, OcrAttQProj{});
-            return;
+            return OcrAttKernel::SharedKv;
         }
     }
     if (!xp.cos_t && !opl.p && kv_div == 1 && Tq >= 2 * ATTR_GQ && R <= 65535 && Tq <= 65535 * 32 && head_dim <= 128 && ((q_rs | q_ts | k_rs | k_ts | v_rs | v_ts) & 3) == 0) {
@@ -1675,10 +1667,10 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
             optin.ensure(reinterpret_cast<const void *>(attention_rows_kernel), sm);
             hipLaunchKernelGGL(attention_rows_kernel, dim3(heads, R, (Tq + (ATTR_THREADS / 64) * ATTR_GQ - 1) / ((ATTR_THREADS / 64) * ATTR_GQ)), dim3(ATTR_THREADS), sm, s, Q, q_rs, q_ts, K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs,
                                o_ts, klen, Tq, Tk, head_dim);
-            return;
+            return OcrAttKernel::Rows;
         }
     }
-    if (g_att_self_rows.load(std::memory_order_relaxed) && Tq == 1 && kv_div == 1 && !klen && xp.cos_t && xp.rot_k && heads == 4 && head_dim == 80 && k_ts == (int64_t)heads * head_dim && v_ts == k_ts &&
+    if (!per_head_self && Tq == 1 && kv_div == 1 && !klen && xp.cos_t && xp.rot_k && heads == 4 && head_dim == 80 && k_ts == (int64_t)heads * head_dim && v_ts == k_ts &&
         !((q_rs | k_rs | k_ts | v_rs | v_ts) & 3) && !((reinterpret_cast<uintptr_t>(K) | reinterpret_cast<uintptr_t>(Q)) & 15) && ((heads * Tk) & 3) == 0) {
         const size_t sm = ((size_t)heads * head_dim + (size_t)heads * Tk + (size_t)Tk * (heads * head_dim + 4) + (size_t)2 * Tk * (head_dim / 2 + SELF_TP_PAD)) * sizeof(float);
         if (sm <= 64 * 1024) {
@@ -1686,7 +1678,7 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
             MitProbeScope probe("attention_self_kernel", s, 4.0 * heads * head_dim * ((double)R * 2.0 * Tk + 2.0 * (double)R),
                                 4.0 * (double)R * heads * Tk * head_dim);
             hipLaunchKernelGGL((attention_self_kernel<4, 80>), dim3(R), dim3(256), sm, s, K, k_rs, V, v_rs, Q, q_rs, Tk, O, o_rs, xp, opl);
-            return;
+            return OcrAttKernel::SelfRows;
         }
     }
     const size_t smem = ((size_t)head_dim + (size_t)Tk) * sizeof(float);
@@ -1694,6 +1686,7 @@ void ocrk_attention(const float *Q, int64_t q_rs, int64_t q_ts, const float *K, 
                         4.0 * (double)R * Tq * heads * Tk * head_dim);
     hipLaunchKernelGGL(attention_kernel, dim3(Tq, heads, R), dim3(64), smem, s, Q, q_rs, q_ts, K, k_rs, k_ts, V, v_rs, v_ts, O, o_rs,
                        o_ts, klen, Tk, kv_div, head_dim, xp, opl);
+    return OcrAttKernel::PerHead;
 }
 
 // The decoder's cross-attention with its q projection inside (QF form above).  Returns false — nothing launched — when the problem is
@@ -1721,10 +1714,9 @@ void ocrk_embed(const int *tok, int64_t tok_stride, const float *E, float *out, 
 }
 
 void ocrk_logsoftmax_top5(const float *logits, int64_t ld, int R, int D, int suppress_tok, float *vals, int *idx,
-                          float *logp_out, hipStream_t s) {
+                          float *logp_out, hipStream_t s, bool loop_form) {
     MitProbeScope probe("logsoftmax_top5_kernel", s, 4.0 * (double)R * D + (logp_out ? 4.0 * (double)R * D : 0.0));
-    const char *loop_form = getenv("MIT_OCR_TOP5_LOOP");   // the loop form for every D (tests: both forms bit for bit)
-    if (loop_form && atoi(loop_form))
+    if (loop_form)   // the loop form for every D (tests: both forms bit for bit)
         hipLaunchKernelGGL(logsoftmax_top5_kernel<0>, dim3(R), dim3(256), 0, s, logits, ld, D, suppress_tok, vals, idx, logp_out);
     else if (D <= 256 * 8)
         hipLaunchKernelGGL(logsoftmax_top5_kernel<8>, dim3(R), dim3(256), 0, s, logits, ld, D, suppress_tok, vals, idx, logp_out);
@@ -1868,10 +1860,10 @@ extern "C" int mit_affine_act_nhwc(const float *in_dev, int64_t in_pixstride, co
 }
 
 extern "C" int mit_logsoftmax_top5(const float *logits_dev, int64_t ld, int R, int D, int suppress_tok, float *vals_dev, int *idx_dev,
-                                   void *stream) {
+                                   int loop_form, void *stream) {
     if (!logits_dev || !vals_dev || !idx_dev) return mit_set_error("mit_logsoftmax_top5: null pointer");
     if (R <= 0 || D < 5) return mit_set_error("mit_logsoftmax_top5: need R > 0 and D >= 5");
-    ocrk_logsoftmax_top5(logits_dev, ld, R, D, suppress_tok, vals_dev, idx_dev, nullptr, (hipStream_t)stream);
+    ocrk_logsoftmax_top5(logits_dev, ld, R, D, suppress_tok, vals_dev, idx_dev, nullptr, (hipStream_t)stream, loop_form != 0);
     MIT_CHECK_LAUNCH("mit_logsoftmax_top5");
     return 0;
 }

@@ -662,7 +662,7 @@ __global__ __launch_bounds__(64) void pgemm_rows_kernel(const uint16_t *pa, cons
 // of them park their accumulators in LDS, wave 0 adds them in the fixed order ((p0 + p1) + p2) + p3 and runs the epilogue: 12.0 us per
 // launch instead of 16.0.  Deterministic, but NOT the k-sequential sum of the other tiles: a page decoded with this kernel differs from
 // the same page inside a 16-page group in the last bits of this Linear's output (fp32 rounding of three extra additions per element).
-// ocr_decoder.hip uses it for few rows only and says so; MIT_OCR_FF2_SPLITK=0 keeps the one-chain kernel.
+// ocr_decoder.hip uses it for few rows only and says so; MIT_OCR48_FORM_FF2_SPLITK in forms_off keeps the one-chain kernel.
 // Measured and dropped (profiles/r11j, r11k): the four slices as four one-wave workgroups on four CUs with a last-arriver reduction
 // through a workspace (release fence + device-scope counter per slice) — 12.8 us; sixteen slices — 28.9 us: every device-scope
 // release fence writes the XCD's L2 back, which costs more than the 786 KB of operand cells cost one CU's L2 port.

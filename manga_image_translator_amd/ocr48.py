@@ -144,12 +144,13 @@ class _Block:
             self._fused = (p1, ops.split_weight(w2p), w2.Np)
         return self._fused
 
-    def mlp(self, t: torch.Tensor, h: torch.Tensor, x: torch.Tensor, rows: int):
+    def mlp(self, t: torch.Tensor, h: torch.Tensor, x: torch.Tensor, rows: int, fused: bool = True):
         """x += gamma * pwconv2(gelu(pwconv1(t))) (:207-213) on flat [rows, C] views: ONE launch with the hidden activations in
         registers where the library has that width and the split-bf16 p6 mode is on (mit_convnext_mlp), else the two GEMM launches
-        through the [rows, 4C] buffer ``h``.  Which form runs depends only on the layer width and the GEMM mode — never on the batch."""
+        through the [rows, 4C] buffer ``h`` (``fused=False``: always those; tests compare the two).  Which form runs depends only on the
+        layer width and the GEMM mode — never on the batch."""
         lib = _lib.load()
-        planes = self._fused_planes() if fused_mlp_enabled() and ops.split_mode() == 6 and lib.mit_convnext_mlp_supported(self.dim) else None
+        planes = self._fused_planes() if fused and ops.split_mode() == 6 and lib.mit_convnext_mlp_supported(self.dim) else None
         if planes is not None:
             p1, p2, ldn2 = planes
             _lib.check(lib.mit_convnext_mlp(t.data_ptr(), self.dim, rows, self.dim, p1.data_ptr(), self.pw1.bias.data_ptr(), p2.data_ptr(), ldn2,
@@ -159,20 +160,6 @@ class _Block:
         t4, h4, x4 = t.view(1, 1, rows, self.dim), h.view(1, 1, rows, 4 * self.dim), x.view(1, 1, rows, self.dim)
         self.pw1(t4, out=h4)
         self.pw2(h4, out=x4, post=x4)
-
-
-_FUSED_MLP = [True]
-
-
-def fused_mlp_enabled() -> bool:
-    return _FUSED_MLP[0]
-
-
-def set_fused_mlp(on: bool) -> bool:
-    """Switch the one-launch ConvNeXt pointwise pair (on by default; tests compare it with the two launches); returns the previous
-    setting."""
-    prev, _FUSED_MLP[0] = _FUSED_MLP[0], bool(on)
-    return prev
 
 
 class Ocr48Engine(ops.Engine):
@@ -498,11 +485,12 @@ class Ocr48Engine(ops.Engine):
 
     @torch.no_grad()
     def decode(self, mem_k: torch.Tensor, mem_v: torch.Tensor, mem_len: torch.Tensor, max_seq_length: int = 255,
-               suppress_eos: bool = False, trace: bool = False):
+               suppress_eos: bool = False, trace: bool = False, forms_off: int = 0):
         """Beam search (:691-801) over N lines at once. mem_k/mem_v [5,N,L,320], mem_len [N] int32.
 
         Returns a dict of device tensors: tokens [N,T+1] int32, length [N], prob [N], colors [N,T,10]
-        (+ trace_logits [T,N*5,dict], trace_hist when ``trace``)."""
+        (+ trace_logits [T,N*5,dict], trace_hist when ``trace``), steps_run and forms_run.  ``forms_off``: the kernel forms
+        (``lib.MIT_OCR48_FORM_*``) this call must not take — tests and A/B runs; ``forms_run``: the ones it took."""
         _, N, L, _ = mem_k.shape
         T = max_seq_length
         lib = _lib.load()
@@ -517,7 +505,7 @@ class Ocr48Engine(ops.Engine):
         a = MitOcr48DecodeArgs()
         a.N, a.L = N, L
         a.mem_k, a.mem_v, a.mem_len = mem_k.contiguous().data_ptr(), mem_v.contiguous().data_ptr(), mem_len.data_ptr()
-        a.max_seq_length, a.start_tok, a.end_tok, a.max_finished, a.suppress_eos = T, 1, 2, 2, int(suppress_eos)
+        a.max_seq_length, a.start_tok, a.end_tok, a.max_finished, a.suppress_eos, a.forms_off = T, 1, 2, 2, int(suppress_eos), forms_off
         a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
         a.res_tok, a.res_len, a.res_prob, a.res_row, a.colors = (t.data_ptr() for t in (res_tok, res_len, res_prob, res_row, colors))
         out = {}
@@ -527,7 +515,7 @@ class Ocr48Engine(ops.Engine):
             a.trace_logits, a.trace_hist = out["trace_logits"].data_ptr(), out["trace_hist"].data_ptr()
         _lib.check(lib.mit_ocr48_decode(C.byref(self.dec), C.byref(a), C.c_void_p(ops.current_stream())), "mit_ocr48_decode")
         sel = colors.reshape(N, 5, T, 12)[torch.arange(N, device=dev), (res_row.long() % 5)]
-        out.update(tokens=res_tok, length=res_len, prob=res_prob, colors=sel[..., :10], steps_run=a.steps_run)
+        out.update(tokens=res_tok, length=res_len, prob=res_prob, colors=sel[..., :10], steps_run=a.steps_run, forms_run=a.forms_run)
         return out
 
     # -- host batching of Model48pxOCR._infer (:79-91) -----------------------------------------

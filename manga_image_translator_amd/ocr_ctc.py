@@ -244,7 +244,7 @@ class OcrCtcEngine(ops.Engine):
         if flat.stride(1) != 1:
             flat = flat.contiguous()
         _lib.check(lib.mit_logsoftmax_top5(flat.data_ptr(), flat.stride(0), N * T, D, -1, vals.data_ptr(), idx.data_ptr(),
-                                           C.c_void_p(ops.current_stream())), "mit_logsoftmax_top5")
+                                           0, C.c_void_p(ops.current_stream())), "mit_logsoftmax_top5")
         best = idx[:, 0].reshape(N, T).cpu().numpy()
         lp = vals[:, 0].reshape(N, T).cpu().numpy()
         col = colors.clamp(0, 1).cpu().numpy()

@@ -81,6 +81,20 @@ def test_pgemm_argument_checks_without_gpu():
     assert handle.mit_split_planes(4096, 12, 4, 12, 8192, 4, None) != 0 and b"K % 8" in handle.mit_last_error()
 
 
+def test_ocr48_decode_refuses_unknown_forms_without_gpu():
+    """MitOcr48DecodeArgs.forms_off is checked before the decoder is read and before any HIP call: a bit that names no kernel form
+    is an error, not a form silently left on."""
+    from manga_image_translator_amd import lib
+
+    handle = lib.load()
+    dec, a = lib.MitOcr48Decoder(), lib.MitOcr48DecodeArgs()
+    a.forms_off = 1 << 9
+    assert handle.mit_ocr48_decode(C.byref(dec), C.byref(a), None) != 0
+    assert b"forms_off" in handle.mit_last_error()
+    assert (lib.MIT_OCR48_FORM_ROWS, lib.MIT_OCR48_FORM_LN_FUSED, lib.MIT_OCR48_FORM_Q2_FUSED, lib.MIT_OCR48_FORM_FF2_SPLITK,
+            lib.MIT_OCR48_FORM_SELF_ROWS, lib.MIT_OCR48_ROWS_MAX) == (1, 2, 4, 8, 16, 2560)
+
+
 def test_ctypes_structs_match_c_layout(tmp_path):
     """Every struct the header declares, not a hand-kept list: size and every field offset as gcc lays them out."""
     from manga_image_translator_amd import lib
@@ -119,7 +133,8 @@ def test_prototype_pins():
     assert lib.SYMBOLS["mit_mask_assign_lines"] == (I, [P, I, I, P, P, P, I, I, D, P, Q, P, Q, P, P, P])
     assert lib.SYMBOLS["mit_ocr32_decode"] == (I, [P, P, P])
     assert lib.SYMBOLS["mit_prof_enable"] == (I, [I])
-    assert (lib.MIT_ABI_VERSION, lib.MIT_MAX_TAPS, lib.MIT_CONVT_COUT1_STRIP_K4, lib.MIT_CONVT_COUT1_STRIP_K2) == (25, 64, 16, 64)
+    assert lib.SYMBOLS["mit_logsoftmax_top5"] == (I, [P, Q, I, I, I, P, P, I, P])
+    assert (lib.MIT_ABI_VERSION, lib.MIT_MAX_TAPS, lib.MIT_CONVT_COUT1_STRIP_K4, lib.MIT_CONVT_COUT1_STRIP_K2) == (26, 64, 16, 64)
     assert (lib.ACT_NONE, lib.ACT_RELU, lib.ACT_LEAKY, lib.ACT_SILU, lib.ACT_SIGMOID, lib.ACT_GELU) == tuple(range(6))
     assert (lib.ACT_POST_FIRST, lib.PAD_ZERO, lib.PAD_REFLECT) == (0x100, 0, 1)
 

@@ -26,6 +26,22 @@ def _crops(widths, seed=0):
     return [rng.integers(0, 256, size=(48, w, 3), dtype=np.uint8) for w in widths]
 
 
+def _pooled_memory(eng, crops, cuda):
+    """The encoder memory of every chunk of ``crops`` pooled for one ``decode``: mem_k / mem_v [5, N, Lmax, 320] (zero-padded), mem_len [N]."""
+    mks, mvs, lens = [], [], []
+    for indices, ws, region in eng.make_chunks(crops):
+        mk, mv, kl, _ = eng.encode(torch.from_numpy(region).to(cuda), ws)
+        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
+    Lmax = max(m.shape[2] for m in mks)
+    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
+    return torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
+
+
+def _forms(L):
+    """The decode's kernel forms (MitOcr48DecodeArgs.forms_off / forms_run) under short names."""
+    return L.MIT_OCR48_FORM_ROWS, L.MIT_OCR48_FORM_LN_FUSED, L.MIT_OCR48_FORM_Q2_FUSED, L.MIT_OCR48_FORM_FF2_SPLITK, L.MIT_OCR48_FORM_SELF_ROWS
+
+
 def test_encoder_memory_parity(cuda, gemm_mode, ocr_setup):
     from oracle import ocr48 as OO
 
@@ -334,36 +350,22 @@ def test_dwconv_ragged_rows_equals_per_row_kernel(cuda, k, C_, H, shapes):
 
 @pytest.mark.parametrize("widths,T,suppress", [([50, 77, 120, 121, 64, 200], 14, True), ([90, 33], 9, False), ([40 + 5 * i for i in range(40)], 6, True)])
 def test_few_row_decode_equals_the_tiled_form(cuda, ocr_setup, widths, T, suppress):
-    """The few-row form of a decode step (mit_ocr48_decode_rows_max_set: every Linear one wave per 32 x 32 block on bf16-plane
+    """The few-row form of a decode step (MIT_OCR48_FORM_ROWS: every Linear one wave per 32 x 32 block on bf16-plane
     activations, LayerNorm / attention kernels producing the planes) against the tiled form the full batches take: the plane split,
     the MFMA pair order and the epilogue arithmetic are the same, so tokens, lengths, probabilities and colours must be identical."""
-    from manga_image_translator_amd import lib as L
+    from manga_image_translator_amd import lib as L, ops
 
     sd, D, eng = ocr_setup
-    crops = _crops(widths, seed=5)
-    mks, mvs, lens = [], [], []
-    for indices, ws, region in eng.make_chunks(crops):
-        mk, mv, kl, _ = eng.encode(torch.from_numpy(region).to(cuda), ws)
-        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
-    Lmax = max(m.shape[2] for m in mks)
-    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
-    mem_k, mem_v, klen = torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
-    lib = L.load()
-    prev = lib.mit_ocr48_decode_rows_max_set(-1)
-    assert prev >= 5 * len(widths), "the few-row form must be the default at these sizes"
+    mem_k, mem_v, klen = _pooled_memory(eng, _crops(widths, seed=5), cuda)
+    ROWS, LN, Q2, SK, SELF = _forms(L)
+    assert L.MIT_OCR48_ROWS_MAX >= 5 * len(widths), "the few-row form must be the default at these sizes"
     outs = []
-    import os
-    prev_sk = os.environ.get("MIT_OCR_FF2_SPLITK")
-    os.environ["MIT_OCR_FF2_SPLITK"] = "0"   # the one-chain FFN kernel: the k-sequential sum of the tiles (the K-cut form has its own test)
-    try:
-        for rows_max in (0, prev):
-            lib.mit_ocr48_decode_rows_max_set(rows_max)
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
-            torch.cuda.synchronize()
-            outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
-    finally:
-        lib.mit_ocr48_decode_rows_max_set(prev)
-        os.environ.pop("MIT_OCR_FF2_SPLITK", None) if prev_sk is None else os.environ.__setitem__("MIT_OCR_FF2_SPLITK", prev_sk)
+    for off in (ROWS, SK):   # SK off: the one-chain FFN kernel, the k-sequential sum of the tiles (the K-cut form has its own test)
+        o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, forms_off=off)
+        torch.cuda.synchronize()
+        outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
+    assert outs[0]["forms_run"] & (ROWS | LN | Q2 | SK) == 0
+    assert outs[1]["forms_run"] == ROWS | LN | SELF | (Q2 if ops.split_mode() == 6 else 0)
     for o in outs[1:]:
         assert o["steps_run"] == outs[0]["steps_run"]
         for k in ("tokens", "length", "prob", "colors"):
@@ -376,7 +378,7 @@ def test_fused_convnext_mlp_matches_the_two_launch_form(cuda, ocr_setup, rows):
     against the two GEMM launches it replaces and against a float64 evaluation of the block's formula.  The first contraction is the
     tiles' own arithmetic; the second adds the same products with an MFMA step's 16 values in other k slots: differences of a few fp32
     ulps of the sums at most.  Ragged row counts (not a multiple of the 32-pixel wave tile / 128-row workgroup) included."""
-    from manga_image_translator_amd import ocr48, ops
+    from manga_image_translator_amd import ops
 
     sd, D, eng = ocr_setup
     blk = eng.stages[0][0]
@@ -386,15 +388,10 @@ def test_fused_convnext_mlp_matches_the_two_launch_form(cuda, ocr_setup, rows):
     x0 = torch.randn(rows, 80, generator=g).to(cuda)
     h = torch.empty(rows, 320, device=cuda)
     with ops.gemm_mode(6, min_tiles=1):
-        assert ocr48.fused_mlp_enabled()
         x1 = x0.clone()
         blk.mlp(t, h, x1, rows)
-        prev = ocr48.set_fused_mlp(False)
-        try:
-            x2 = x0.clone()
-            blk.mlp(t, h, x2, rows)
-        finally:
-            ocr48.set_fused_mlp(prev)
+        x2 = x0.clone()
+        blk.mlp(t, h, x2, rows, fused=False)
         x1b = x0.clone()
         blk.mlp(t, h, x1b, rows)
     torch.cuda.synchronize()
@@ -416,21 +413,17 @@ def test_row_staged_self_attention_is_bitwise_the_per_head_kernel(cuda, ocr_setu
     """attention_self_kernel (the decoder's self-attention with a row's key history staged once for its four heads) against
     attention_kernel (one single-wave workgroup per head and row): the whole beam search — tokens, lengths, probabilities, colours —
     must come out bit for bit the same (6 lines: the few-row decoder form with planar outputs; 40 lines: likewise, pooled)."""
-    from manga_image_translator_amd import lib as L_
+    from manga_image_translator_amd import lib as L, ops
 
     sd, D, eng = ocr_setup
-    lib = L_.load()
-    crops = _crops(widths, seed=3)
+    mem_k, mem_v, klen = _pooled_memory(eng, _crops(widths, seed=3), cuda)
+    ROWS, LN, Q2, SK, SELF = _forms(L)
     outs = []
-    for on in (1, 0, 1):
-        prev = lib.mit_attention_self_rows_set(on)
-        try:
-            assert lib.mit_attention_self_rows_set(-1) == on
-            r = eng.recognize(crops, max_seq_length=T, suppress_eos=True)
-            torch.cuda.synchronize()
-        finally:
-            lib.mit_attention_self_rows_set(prev)
+    for off in (0, SELF, 0):
+        r = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=True, forms_off=off)
+        torch.cuda.synchronize()
         outs.append({k: v.clone() for k, v in r.items() if torch.is_tensor(v)})
+        assert r["forms_run"] == (ROWS | LN | SK | SELF | (Q2 if ops.split_mode() == 6 else 0)) & ~off   # 0: everything that ships
     assert {"tokens", "length", "prob", "colors"} <= set(outs[0])
     for other in outs[1:]:
         for k, v in outs[0].items():
@@ -440,11 +433,10 @@ def test_row_staged_self_attention_is_bitwise_the_per_head_kernel(cuda, ocr_setu
 @pytest.mark.parametrize("R,D,suppress", [(7, 6004, 2), (160, 6004, -1), (5, 2047, 0), (3, 300, -1), (4, 7000, 5)])
 def test_register_form_of_logsoftmax_top5_is_bitwise_the_loop_form(cuda, R, D, suppress):
     """logsoftmax_top5_kernel<NJ>: a thread's elements loaded once and every pass on registers (all loads in flight together) against the
-    loop form (MIT_OCR_TOP5_LOOP=1: three passes over the row, loads serialised by the candidate insertion): same elements per thread in
+    loop form (loop_form = 1: three passes over the row, loads serialised by the candidate insertion): same elements per thread in
     the same order, same pairing across threads — the five values and the five indices must be identical, with ties
     (lower index first), a suppressed token and rows of -inf padding."""
     import ctypes as C
-    import os
     from manga_image_translator_amd import lib as L, ops
 
     lib = L.load()
@@ -456,21 +448,13 @@ def test_register_form_of_logsoftmax_top5_is_bitwise_the_loop_form(cuda, R, D, s
     x[0, : min(D, 40)] = float("-inf")  # a run of -inf entries
     x = x.to(cuda)
     outs = []
-    prev = os.environ.get("MIT_OCR_TOP5_LOOP")
-    try:
-        for loop in ("1", "0"):
-            os.environ["MIT_OCR_TOP5_LOOP"] = loop
-            vals = torch.empty(R, 5, device=cuda)
-            idx = torch.empty(R, 5, dtype=torch.int32, device=cuda)
-            L.check(lib.mit_logsoftmax_top5(x.data_ptr(), Dp, R, D, suppress, vals.data_ptr(), idx.data_ptr(),
-                                            C.c_void_p(ops.current_stream())), "mit_logsoftmax_top5")
-            torch.cuda.synchronize()
-            outs.append((vals.clone(), idx.clone()))
-    finally:
-        if prev is None:
-            os.environ.pop("MIT_OCR_TOP5_LOOP", None)
-        else:
-            os.environ["MIT_OCR_TOP5_LOOP"] = prev
+    for loop_form in (1, 0):
+        vals = torch.empty(R, 5, device=cuda)
+        idx = torch.empty(R, 5, dtype=torch.int32, device=cuda)
+        L.check(lib.mit_logsoftmax_top5(x.data_ptr(), Dp, R, D, suppress, vals.data_ptr(), idx.data_ptr(), loop_form,
+                                        C.c_void_p(ops.current_stream())), "mit_logsoftmax_top5")
+        torch.cuda.synchronize()
+        outs.append((vals.clone(), idx.clone()))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
     # and against torch (values within fp32 rounding; indices exactly, ties to the lower index)
@@ -486,40 +470,21 @@ def test_register_form_of_logsoftmax_top5_is_bitwise_the_loop_form(cuda, R, D, s
 @pytest.mark.parametrize("widths,T,suppress", [([50, 77, 120, 121, 64, 200], 14, True), ([90, 33], 9, False), ([40 + 5 * i for i in range(40)], 6, True)])
 def test_layernorm_inside_the_few_row_gemm_is_bit_identical(cuda, ocr_setup, widths, T, suppress):
     """pgemm_rows_ln_kernel (the decoder's norm1 / norm2 / norm3 computed by the waves of the Linear that consumes them, same butterfly
-    as layernorm_kernel) against the two-launch form (MIT_OCR_LN_FUSED=0) and against the tiled form of full batches: every result
-    tensor identical; 6, 2 and 40 lines = 30, 10 and 200 rows (ragged last row block)."""
-    import os
-    from manga_image_translator_amd import lib as L
+    as layernorm_kernel) against the two-launch form (MIT_OCR48_FORM_LN_FUSED off) and against the tiled form of full batches: every
+    result tensor identical; 6, 2 and 40 lines = 30, 10 and 200 rows (ragged last row block).  The K-cut FFN Linear is off throughout."""
+    from manga_image_translator_amd import lib as L, ops
 
     sd, D, eng = ocr_setup
-    crops = _crops(widths, seed=23)
-    mks, mvs, lens = [], [], []
-    for indices, ws, region in eng.make_chunks(crops):
-        mk, mv, kl, _ = eng.encode(torch.from_numpy(region).to(cuda), ws)
-        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
-    Lmax = max(m.shape[2] for m in mks)
-    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
-    mem_k, mem_v, klen = torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
-    lib = L.load()
-    prev_rows = lib.mit_ocr48_decode_rows_max_set(-1)
-    prev_env = os.environ.get("MIT_OCR_LN_FUSED")
-    prev_sk = os.environ.get("MIT_OCR_FF2_SPLITK")
-    os.environ["MIT_OCR_FF2_SPLITK"] = "0"
+    mem_k, mem_v, klen = _pooled_memory(eng, _crops(widths, seed=23), cuda)
+    ROWS, LN, Q2, SK, SELF = _forms(L)
     outs = []
-    try:
-        for fused, rows_max in (("0", prev_rows), ("1", prev_rows), ("1", 0)):
-            os.environ["MIT_OCR_LN_FUSED"] = fused
-            lib.mit_ocr48_decode_rows_max_set(rows_max)
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
-            torch.cuda.synchronize()
-            outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
-    finally:
-        lib.mit_ocr48_decode_rows_max_set(prev_rows)
-        os.environ.pop("MIT_OCR_FF2_SPLITK", None) if prev_sk is None else os.environ.__setitem__("MIT_OCR_FF2_SPLITK", prev_sk)
-        if prev_env is None:
-            os.environ.pop("MIT_OCR_LN_FUSED", None)
-        else:
-            os.environ["MIT_OCR_LN_FUSED"] = prev_env
+    for off in (LN | SK, SK, ROWS):
+        o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, forms_off=off)
+        torch.cuda.synchronize()
+        outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
+    assert outs[0]["forms_run"] == ROWS | SELF                    # (the q projection inside the cross-attention needs the fused LayerNorm)
+    assert outs[1]["forms_run"] == ROWS | LN | SELF | (Q2 if ops.split_mode() == 6 else 0)
+    assert outs[2]["forms_run"] & (ROWS | LN | Q2 | SK) == 0
     for o in outs[1:]:
         assert o["steps_run"] == outs[0]["steps_run"]
         for k in ("tokens", "length", "prob", "colors"):
@@ -529,30 +494,20 @@ def test_layernorm_inside_the_few_row_gemm_is_bit_identical(cuda, ocr_setup, wid
 @pytest.mark.parametrize("widths,T,suppress", [([50, 77, 120, 121, 64, 200], 14, True), ([90, 33], 9, False), ([40 + 5 * i for i in range(32)], 12, True)])
 def test_k_cut_ffn_linear_of_the_few_row_decode(cuda, ocr_setup, widths, T, suppress):
     """pgemm_rows_splitk_kernel (the FFN's K = 2048 Linear with K cut across four waves, summed in a fixed order; the default up to 640
-    rows) against the one-chain kernel (MIT_OCR_FF2_SPLITK=0): a different fp32 rounding of the same sums — tokens and lengths must be
-    identical, probabilities within 1e-4 relative (the oracle bar on log-probabilities is 5e-4), colour heads within 1e-4; run to run the
-    K-cut form is bit-reproducible ."""
-    import os
+    rows) against the one-chain kernel (MIT_OCR48_FORM_FF2_SPLITK off): a different fp32 rounding of the same sums — tokens and lengths
+    must be identical, probabilities within 1e-4 relative (the oracle bar on log-probabilities is 5e-4), colour heads within 1e-4; run to
+    run the K-cut form is bit-reproducible ."""
+    from manga_image_translator_amd import lib as L, ops
 
     sd, D, eng = ocr_setup
-    crops = _crops(widths, seed=31)
-    mks, mvs, lens = [], [], []
-    for indices, ws, region in eng.make_chunks(crops):
-        mk, mv, kl, _ = eng.encode(torch.from_numpy(region).to(cuda), ws)
-        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
-    Lmax = max(m.shape[2] for m in mks)
-    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
-    mem_k, mem_v, klen = torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
-    prev_sk = os.environ.get("MIT_OCR_FF2_SPLITK")
+    mem_k, mem_v, klen = _pooled_memory(eng, _crops(widths, seed=31), cuda)
+    ROWS, LN, Q2, SK, SELF = _forms(L)
     outs = []
-    try:
-        for sk in ("0", "1", "1"):
-            os.environ["MIT_OCR_FF2_SPLITK"] = sk
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
-            torch.cuda.synchronize()
-            outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
-    finally:
-        os.environ.pop("MIT_OCR_FF2_SPLITK", None) if prev_sk is None else os.environ.__setitem__("MIT_OCR_FF2_SPLITK", prev_sk)
+    for off in (SK, 0, 0):
+        o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, forms_off=off)
+        torch.cuda.synchronize()
+        outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
+        assert o["forms_run"] == (ROWS | LN | SK | SELF | (Q2 if ops.split_mode() == 6 else 0)) & ~off   # 0: everything that ships
     for k in ("tokens", "length", "prob", "colors"):
         assert torch.equal(outs[1][k], outs[2][k]), k
     assert outs[1]["steps_run"] == outs[0]["steps_run"]
@@ -566,28 +521,18 @@ def test_k_cut_ffn_linear_of_the_few_row_decode(cuda, ocr_setup, widths, T, supp
 def test_q_projection_inside_the_cross_attention_is_bit_identical(cuda, ocr_setup, widths, T, suppress):
     """attention_shared_kv_kernel<..., QF> (norm2 and multihead_attn's q projection computed inside the decoder's cross-attention kernel:
     one wave normalises the line's five beams with layernorm_kernel's butterfly, three waves run pgemm_rows_kernel's K loop on the head's
-    columns) against the separate launches (MIT_OCR_Q2_FUSED=0): every result tensor identical."""
-    import os
+    columns) against the separate launches (MIT_OCR48_FORM_Q2_FUSED off): every result tensor identical."""
+    from manga_image_translator_amd import lib as L, ops
 
     sd, D, eng = ocr_setup
-    crops = _crops(widths, seed=41)
-    mks, mvs, lens = [], [], []
-    for indices, ws, region in eng.make_chunks(crops):
-        mk, mv, kl, _ = eng.encode(torch.from_numpy(region).to(cuda), ws)
-        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
-    Lmax = max(m.shape[2] for m in mks)
-    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
-    mem_k, mem_v, klen = torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
-    prev = os.environ.get("MIT_OCR_Q2_FUSED")
+    mem_k, mem_v, klen = _pooled_memory(eng, _crops(widths, seed=41), cuda)
+    ROWS, LN, Q2, SK, SELF = _forms(L)
     outs = []
-    try:
-        for q2 in ("0", "1"):
-            os.environ["MIT_OCR_Q2_FUSED"] = q2
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress)
-            torch.cuda.synchronize()
-            outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
-    finally:
-        os.environ.pop("MIT_OCR_Q2_FUSED", None) if prev is None else os.environ.__setitem__("MIT_OCR_Q2_FUSED", prev)
+    for off in (Q2, 0):
+        o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=suppress, forms_off=off)
+        torch.cuda.synchronize()
+        outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
+        assert o["forms_run"] == (ROWS | LN | SK | SELF | (Q2 if ops.split_mode() == 6 else 0)) & ~off   # 0: everything that ships
     for o in outs[1:]:
         assert o["steps_run"] == outs[0]["steps_run"]
         for k in ("tokens", "length", "prob", "colors"):
@@ -598,32 +543,18 @@ def test_q_projection_inside_the_cross_attention_is_bit_identical(cuda, ocr_setu
 def test_few_row_decode_at_the_edges_of_its_forms(cuda, ocr_setup, n_lines, T):
     """One line (5 rows: a single ragged row block), 129 lines (past the 128 the q-projecting cross-attention takes: separate launches) and
     140 lines (700 rows: past the 640 the K-cut FFN Linear takes: the one-chain K = 2048 kernel) against the tiled form, with the K-cut
-    off — every result tensor identical."""
-    import os
-    from manga_image_translator_amd import lib as L
+    off — every result tensor identical.  Past 640 rows nothing switches the K-cut off but the row count: that leg is what ships."""
+    from manga_image_translator_amd import lib as L, ops
 
     sd, D, eng = ocr_setup
-    crops = _crops([48 + (7 * i) % 90 for i in range(n_lines)], seed=53)
-    mks, mvs, lens = [], [], []
-    for indices, ws, region in eng.make_chunks(crops):
-        mk, mv, kl, _ = eng.encode(torch.from_numpy(region).to(cuda), ws)
-        mks.append(mk.clone()); mvs.append(mv.clone()); lens.append(kl.clone())
-    Lmax = max(m.shape[2] for m in mks)
-    pad = lambda m: m if m.shape[2] == Lmax else torch.cat([m, m.new_zeros(5, m.shape[1], Lmax - m.shape[2], 320)], 2)
-    mem_k, mem_v, klen = torch.cat([pad(m) for m in mks], 1).contiguous(), torch.cat([pad(m) for m in mvs], 1).contiguous(), torch.cat(lens)
-    lib = L.load()
-    prev = lib.mit_ocr48_decode_rows_max_set(-1)
-    prev_sk = os.environ.get("MIT_OCR_FF2_SPLITK")
-    os.environ["MIT_OCR_FF2_SPLITK"] = "0"
+    mem_k, mem_v, klen = _pooled_memory(eng, _crops([48 + (7 * i) % 90 for i in range(n_lines)], seed=53), cuda)
+    ROWS, LN, Q2, SK, SELF = _forms(L)
     outs = []
-    try:
-        for rows_max in (0, prev):
-            lib.mit_ocr48_decode_rows_max_set(rows_max)
-            o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=True)
-            torch.cuda.synchronize()
-            outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
-    finally:
-        lib.mit_ocr48_decode_rows_max_set(prev)
-        os.environ.pop("MIT_OCR_FF2_SPLITK", None) if prev_sk is None else os.environ.__setitem__("MIT_OCR_FF2_SPLITK", prev_sk)
+    for off in (ROWS, SK if 5 * n_lines <= 640 else 0):
+        o = eng.decode(mem_k, mem_v, klen, max_seq_length=T, suppress_eos=True, forms_off=off)
+        torch.cuda.synchronize()
+        outs.append({k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()})
+    assert outs[0]["forms_run"] & (ROWS | LN | Q2 | SK) == 0
+    assert outs[1]["forms_run"] == ROWS | LN | SELF | (Q2 if ops.split_mode() == 6 and n_lines <= 128 else 0)
     for k in ("tokens", "length", "prob", "colors"):
         assert torch.equal(outs[1][k], outs[0][k]), k
