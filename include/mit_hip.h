@@ -181,6 +181,38 @@ const char *mit_conv_gemm_config_name(int cfg);
  * by itself when it is launched.  Makes no HIP call and dereferences no operand pointer: it works without a GPU, which is how
  * tests/test_conv_gemm_plan.py pins the automatic tile choice. */
 int mit_conv_gemm_plan(const MitConvGemm *desc, int cfg, int32_t *tile, int32_t *nb_run);
+/* Grouped launch: n convolutions that share everything but the image — weights, taps, strides, padding, N, K, epilogue vectors and
+ * activation come from ``base``; the operand and result base pointers, NB, Hi, Wi, Ho, Wo and the image / row strides come from the
+ * member records (base's own a, c.base, c.bs, c.ys, a_bs, a_ys, NB, Hi, Wi, Ho, Wo are ignored; a_xs and c.xs are shared).  The 48px OCR
+ * runs the chunks of a page group through it: their padded widths differ, everything else is one layer (Ocr48Engine.encode_group).
+ *
+ * One launch whose grid is the concatenation of the members' grids: a workgroup finds its member from the prefix of tile counts
+ * (scalar code) and runs the tile body of the single launch with that member's sizes and pointers, so every member's result has the
+ * bits of mit_conv_gemm on that member alone.  The tile is the one mit_conv_gemm would choose for ONE launch with the group's total
+ * rows (all tiles of a family give the same bits).  The records travel by value in the kernel arguments: no allocation, no
+ * synchronisation, no device table; more than MIT_CONV_GROUP_MAX members run as several grouped launches of up to that many.
+ *
+ * Falls back to member-by-member mit_conv_gemm launches, inside the same call, when the group cannot run as one grid: the chosen tile
+ * has no grouped form (they exist for the generic 128x128 / 128x64 tiles, the fp32 MFMA 128x128 / 128x64 / 64x64 tiles and the p6
+ * buffer-load tiles 128x64, 128x96, 128x160, 64x64x16, 64x64x32), a member is not eligible for it, or the base carries a live-block
+ * list, wino_m, lut_rows, Z > 1, or a member's batch would be cut into runs.  base.pre / base.post must be NULL (refused otherwise:
+ * a residual is per member and the records carry none).  With mit_prof_enable a grouped launch is ONE launch under its tile's index
+ * with the members' summed FLOPs. */
+#define MIT_CONV_GROUP_MAX 32
+typedef struct MitConvGemmMember {
+    const float *a;        /* A operand of this member */
+    float *c;              /* its result */
+    int64_t a_bs, a_ys;    /* image / row strides of A */
+    int64_t c_bs, c_ys;    /* image / row strides of the result */
+    int32_t NB, Hi, Wi, Ho, Wo, _pad;
+} MitConvGemmMember;
+int mit_conv_gemm_group(const MitConvGemm *base, const MitConvGemmMember *members, int n, void *stream);
+/* What mit_conv_gemm_group would do, without doing it (no HIP call, no operand dereferenced: works without a GPU).  *tile = the tile
+ * chosen for the group's total rows; per member i: launch[i] = the index of the grouped launch it rides in (0, 1, ... — a new one
+ * every MIT_CONV_GROUP_MAX members) or -1 when the group falls back to member-by-member launches, first_tile[i] = its first workgroup
+ * in that launch's grid (0 on the fallback), ntiles[i] = its workgroups on *tile.  Any output may be NULL. */
+int mit_conv_gemm_group_plan(const MitConvGemm *base, const MitConvGemmMember *members, int n, int32_t *tile, int32_t *launch,
+                             int32_t *first_tile, int32_t *ntiles);
 /* the kernel's template-id as rocprofv3 prints it (without namespace), e.g. "conv_gemm_fast_kernel<128, 128, 16, 1, 4, 4, 4>":
  * lets bench.py join its per-tile probe numbers with the profiler's kernel-trace / PMC rows; NULL past the table. */
 const char *mit_conv_gemm_config_kernel(int cfg);
@@ -881,6 +913,17 @@ typedef struct MitWarpLine {
 int mit_ocr_warp_lines(const uint8_t *pages_dev, int H, int W, const MitWarpLine *lines_dev, int n_lines, uint8_t *out_dev,
                        int Hout, int Wp, void *stream);
 int mit_ocr_prep(const uint8_t *lines_dev, float *out_dev, int N, int H, int Wp, void *stream);
+/* The same for the chunks of a page group in ONE launch, over a device table in the manner of MitRaggedSeg: segment s converts the
+ * N * H * Wp pixels at src to the output slab from pixel pixel_start on; block_start = running count of MIT_OCR_PREP_BLOCK-pixel work
+ * items = sum over earlier segments of ceil(N * H * Wp / MIT_OCR_PREP_BLOCK), total_blocks = that sum over all (the grid).  Per pixel
+ * the expression of mit_ocr_prep: same bits. */
+#define MIT_OCR_PREP_BLOCK 1024
+typedef struct MitOcrPrepSeg {
+    const uint8_t *src;
+    int64_t pixel_start, block_start;
+    int32_t N, Wp;
+} MitOcrPrepSeg;
+int mit_ocr_prep_ragged(const MitOcrPrepSeg *segs_dev, int nsegs, int64_t total_blocks, float *out_dev, int H, void *stream);
 /* depthwise k x k conv + per-channel scale/bias (ConvNeXtBlock.dwconv + norm, model_48px.py:195-196,205-206). w [k*k][C]. */
 int mit_dwconv_nhwc(const float *in_dev, const float *w_dev, const float *scale_dev, const float *bias_dev, float *out_dev,
                     int B, int H, int W, int C, int k, void *stream);

@@ -43,7 +43,7 @@ HIPCC_FLAGS = [
 # (profiles/r07h) —, the planar GEMM) and are checked by tests/test_build_flags.py to contain no packed-fp32 instruction with a
 # modifier; every other unit must contain none at all.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-PACKED_FP32_BY_DESIGN = {"conv_small_cout.hip", "pgemm.hip"} | {f"conv_gemm_inst{i}.hip" for i in range(7)}
+PACKED_FP32_BY_DESIGN = {"conv_small_cout.hip", "pgemm.hip"} | {f"conv_gemm_inst{i}.hip" for i in range(8)}
 
 
 # Kernel-argument preloading (gfx940+): the leading scalar arguments of a kernel arrive in user SGPRs with the wave instead of behind a scalar

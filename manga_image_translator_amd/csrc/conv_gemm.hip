@@ -1,9 +1,16 @@
 // conv_gemm.hip — tile choice, kernel-time probe and C entry points of mit_conv_gemm (validate -> plan -> launch).
 // The kernels are in conv_gemm_kernels.h, their instantiations are compiled in conv_gemm_inst<group>.hip, the tile table is conv_gemm_table.h.
+// mit_conv_gemm_group (several images of one layer as one grid) is at the end; its kernels are the grouped twins of conv_gemm_inst7.hip.
 #include "conv_gemm_table.h"
 #include <atomic>
 
 using namespace mitcg;
+
+// the grouped twins (conv_gemm_group_cfgs.inc), instantiated in conv_gemm_inst7.hip
+#define G(name, fam, BM, BN, BK, ...) \
+    extern template void mitcg::launch_##fam##_group<BM, BN, BK, __VA_ARGS__>(const mitcg::GroupArgs &, int, int, hipStream_t);
+#include "conv_gemm_group_cfgs.inc"
+#undef G
 
 namespace {
 
@@ -456,6 +463,151 @@ extern "C" int mit_conv_gemm_cfg(const MitConvGemm *d, int cfg, void *stream) {
 }
 
 extern "C" int mit_conv_gemm(const MitConvGemm *d, void *stream) { return mit_conv_gemm_cfg(d, -1, stream); }
+
+// ---- grouped launches: n convolutions that share everything but the image, as one grid (include/mit_hip.h, mit_conv_gemm_group) ----
+namespace {
+struct GroupTwin {
+    int cfg;
+    void (*launch)(const GroupArgs &, int NT, int KT, hipStream_t);
+};
+constexpr bool row_is(const CfgEntry &e, TileFamily f, int BM, int BN, int BK, int a0 = 0, int a1 = 0, int a2 = 0, int a3 = 0, int a4 = 0) {
+    return e.family == f && e.BM == BM && e.BN == BN && e.BK == BK && e.args[0] == a0 && e.args[1] == a1 && e.args[2] == a2 && e.args[3] == a3 && e.args[4] == a4;
+}
+#define G(name, fam, ...) static_assert(row_is(kCfgs[CFG(name)], TileFamily::fam, __VA_ARGS__), "grouped twin " name " differs from its row in conv_gemm_cfgs.inc");
+#include "conv_gemm_group_cfgs.inc"
+#undef G
+const GroupTwin kGroupTwins[] = {
+#define G(name, fam, BM, BN, BK, ...) {CFG(name), launch_##fam##_group<BM, BN, BK, __VA_ARGS__>},
+#include "conv_gemm_group_cfgs.inc"
+#undef G
+};
+const GroupTwin *group_twin(int cfg) {
+    for (const GroupTwin &t : kGroupTwins)
+        if (t.cfg == cfg) return &t;
+    return nullptr;
+}
+
+// the base descriptor with member m's image in place of its own
+MitConvGemm member_desc(const MitConvGemm &b, const MitConvGemmMember &m) {
+    MitConvGemm d = b;
+    d.a = m.a, d.a_bs = m.a_bs, d.a_ys = m.a_ys;
+    d.NB = m.NB, d.Hi = m.Hi, d.Wi = m.Wi, d.Ho = m.Ho, d.Wo = m.Wo;
+    d.c.base = m.c, d.c.bs = m.c_bs, d.c.ys = m.c_ys;
+    return d;
+}
+
+struct GroupPlan {
+    std::vector<MitConvGemm> desc;  // the members as descriptors of their own, as given (the fallback launches them)
+    std::vector<MitConvGemm> p;     // ... validated
+    int cfg = -1;                   // the tile of one launch with the group's total rows (-1: not determined, the group falls back)
+    bool grouped = false;           // the group runs as concatenated grids on cfg's twin
+    const GroupTwin *twin = nullptr;
+};
+// validate every member, choose the tile, decide between the grouped launch and the member-by-member fallback
+int plan_group(const MitConvGemm *base, const MitConvGemmMember *members, int n, GroupPlan &g) {
+    if (!base || !members) return mit_set_error("mit_conv_gemm_group: null pointer");
+    if (n <= 0) return mit_set_error("mit_conv_gemm_group: empty group");
+    if (base->pre.base || base->post.base) return mit_set_error("mit_conv_gemm_group: pre / post operands are per image and the member records carry none");
+    g.desc.resize(n);
+    g.p.resize(n);
+    for (int i = 0; i < n; ++i) {
+        g.desc[i] = member_desc(*base, members[i]);
+        if (int rc = validate(&g.desc[i], g.p[i])) return rc;
+    }
+    const MitConvGemm &b = g.p[0];
+    if (b.live_blocks || b.wino_m || b.lut_rows || b.Z != 1) return 0;  // forms the grouped kernels do not take: member by member
+    int64_t Mtot = 0;
+    for (int i = 0; i < n; ++i) {
+        if (images_per_run(g.p[i]) != g.p[i].NB) return 0;  // a cut batch
+        Mtot += rows_of(g.p[i]);
+    }
+    if (Mtot > 0x7fffffffLL) return 0;
+    if (b.nprod == 1 && !split_eligible(b, 16)) return 0;  // (the member launches refuse it with their own message)
+    g.cfg = pick_cfg(b, Mtot);
+    const CfgEntry &c = kCfgs[g.cfg];
+    int64_t tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        const MitConvGemm &q = g.p[i];
+        // every member eligible for the group's tile: the choice made for it alone at the group's size is the same tile (this covers the
+        // fast / split / buffer-load preconditions, which depend on the member's offsets), and the tile does not refuse it
+        if (q.act != b.act || (q.nprod == 1 && !split_eligible(q, 16)) || pick_cfg(q, Mtot) != g.cfg) return 0;
+        int t = -1;
+        if (plan_run(q, g.cfg, &t) != 0) return 0;
+        tiles += (rows_of(q) + c.BM - 1) / c.BM * ((q.N + c.BN - 1) / c.BN);
+    }
+    if (tiles > 0x7fffffffLL) return 0;
+    g.twin = group_twin(g.cfg);
+    g.grouped = g.twin != nullptr;
+    return 0;
+}
+int64_t member_tiles(const MitConvGemm &q, const CfgEntry &c) { return (rows_of(q) + c.BM - 1) / c.BM * ((q.N + c.BN - 1) / c.BN); }
+}  // namespace
+
+extern "C" int mit_conv_gemm_group_plan(const MitConvGemm *base, const MitConvGemmMember *members, int n, int32_t *tile, int32_t *launch,
+                                        int32_t *first_tile, int32_t *ntiles) {
+    GroupPlan g;
+    if (int rc = plan_group(base, members, n, g)) return rc;
+    if (tile) *tile = g.cfg;
+    int32_t t0 = 0;
+    for (int i = 0; i < n; ++i) {
+        if (i % GROUP_MAX == 0) t0 = 0;
+        const int32_t nt = g.cfg >= 0 ? (int32_t)member_tiles(g.p[i], kCfgs[g.cfg]) : 0;
+        if (launch) launch[i] = g.grouped ? i / GROUP_MAX : -1;
+        if (first_tile) first_tile[i] = g.grouped ? t0 : 0;
+        if (ntiles) ntiles[i] = nt;
+        t0 += nt;
+    }
+    return 0;
+}
+
+extern "C" int mit_conv_gemm_group(const MitConvGemm *base, const MitConvGemmMember *members, int n, void *stream) {
+    GroupPlan g;
+    if (int rc = plan_group(base, members, n, g)) return rc;
+    hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+    if (!g.grouped) {
+        for (int i = 0; i < n; ++i)
+            if (int rc = mit_conv_gemm_cfg(&g.desc[i], -1, stream)) return rc;
+        return 0;
+    }
+    const CfgEntry &c = kCfgs[g.cfg];
+    const MitConvGemm &b = g.p[0];
+    const int NT = (b.N + c.BN - 1) / c.BN;
+    const int Ktot = b.ntaps * b.Cin;
+    const int KT = (Ktot + c.BK - 1) / c.BK;
+    const double tagged = g_next_alg_flops;
+    g_next_alg_flops = -1.0;
+    for (int i0 = 0; i0 < n; i0 += GROUP_MAX) {
+        GroupArgs ga = {};
+        ga.p = b;
+        ga.n = n - i0 < GROUP_MAX ? n - i0 : GROUP_MAX;
+        int64_t rows = 0;
+        for (int i = 0; i < ga.n; ++i) {
+            ga.m[i] = members[i0 + i];
+            ga.tile0[i + 1] = ga.tile0[i] + (int32_t)member_tiles(g.p[i0 + i], c);
+            rows += rows_of(g.p[i0 + i]);
+        }
+        if (g_probe_on) {  // one launch under its tile's index with the members' summed FLOPs
+            std::lock_guard<std::mutex> lk(g_probe_mu);
+            ProbeRec r;
+            MIT_CHECK_HIP(hipEventCreate(&r.start));
+            MIT_CHECK_HIP(hipEventCreate(&r.stop));
+            r.cfg = g.cfg;
+            r.exec_flops = 2.0 * (double)rows * b.N * Ktot;
+            r.alg_flops = tagged >= 0.0 && n <= GROUP_MAX ? tagged : r.exec_flops;
+            r.M = (int)rows, r.N = b.N, r.K = Ktot, r.ntaps = b.ntaps, r.Z = 1, r.act = b.act;
+            r.wino_bytes = 0.0;
+            MIT_CHECK_HIP(hipEventRecord(r.start, hs));
+            g.twin->launch(ga, NT, KT, hs);
+            MIT_CHECK_HIP(hipEventRecord(r.stop, hs));
+            g_probe.push_back(r);
+        } else {
+            g.twin->launch(ga, NT, KT, hs);
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return mit_set_error("mit_conv_gemm_group: launch failed: %s", hipGetErrorString(e));
+    }
+    return 0;
+}
 
 extern "C" int mit_gemm_mode_set(int mode) {
     if (mode != 0 && mode != 6 && mode != 9) return mit_set_error("mit_gemm_mode_set: mode must be 0, 6 or 9 (got %d)", mode);

@@ -77,7 +77,8 @@ __device__ __forceinline__ float apply_act(float v, float alpha) {
 // Dense launch: m = (nb * Ho + oy) * Wo + ox; rows m >= M are dead.  With MitConvGemm.live_blocks the rows are those of the listed
 // 8 x 8 blocks: row m is position m & 63 (row-major) of the (m >> 6)-th live block of this run; rows past the live blocks and positions
 // of a clipped edge block outside Ho x Wo are dead.  A dead row gathers zeros and stores nothing.  Called outside the K loops only.
-__device__ __forceinline__ bool decode_row(const MitConvGemm &p, const int m, const int M, const int HoWo, int &nb, int &oy, int &ox) {
+template <class P>
+__device__ __forceinline__ bool decode_row(const P &p, const int m, const int M, const int HoWo, int &nb, int &oy, int &ox) {
     if (p.live_blocks == nullptr) {
         if (m >= M) return false;
         nb = m / HoWo;
@@ -100,8 +101,8 @@ __device__ __forceinline__ bool decode_row(const MitConvGemm &p, const int m, co
 }
 // workgroups of a launch: MT * NT, or with a live-block list the tiles that hold live rows — the caller returns when blockIdx.x is
 // past them and forms its XCD-contiguous tile order over this count, so the live tiles spread over all XCDs
-template <int BM>
-__device__ __forceinline__ int live_workgroups(const MitConvGemm &p, const int MT, const int NT) {
+template <int BM, class P>
+__device__ __forceinline__ int live_workgroups(const P &p, const int MT, const int NT) {
     if (p.live_blocks == nullptr) return MT * NT;
     const int live = p.live_start[p.NB] - p.live_start[0];  // wave-uniform: scalar loads
     return ((live * 64 + BM - 1) / BM) * NT;
@@ -110,8 +111,8 @@ __device__ __forceinline__ int live_workgroups(const MitConvGemm &p, const int M
 // ---- epilogue shared by both kernels: row offsets computed once per row, shared through LDS ----
 // The activation (and whether a residual joins) is a compile-time parameter of the store loop and dispatched once per
 // wave: a per-element switch costs more than the stores on the small-K layers.
-template <int TM, int TN, int ACT, bool HAS_POST>
-__device__ __forceinline__ void epilogue_store(const MitConvGemm &p, f32x16 (&acc)[TM][TN], const RowOff *rowoff, const int n0,
+template <int TM, int TN, int ACT, bool HAS_POST, class P>
+__device__ __forceinline__ void epilogue_store(const P &p, f32x16 (&acc)[TM][TN], const RowOff *rowoff, const int n0,
                                                const int wm0, const int wn0, const int tid) {
     const int lane = tid & 63;
     const int li = lane & 31;
@@ -154,8 +155,8 @@ __device__ __forceinline__ void epilogue_store(const MitConvGemm &p, f32x16 (&ac
 constexpr int EPI_PITCH = 36;
 #define MIT_ACT_VEC_OK 0x200
 
-template <int TM, int TN, int ACT, bool HAS_POST, bool HAS_LUT = false>
-__device__ __forceinline__ void epilogue_store_vec(const MitConvGemm &p, f32x16 (&acc)[TM][TN], const RowOff *rowoff, float *tbuf,
+template <int TM, int TN, int ACT, bool HAS_POST, bool HAS_LUT = false, class P>
+__device__ __forceinline__ void epilogue_store_vec(const P &p, f32x16 (&acc)[TM][TN], const RowOff *rowoff, float *tbuf,
                                                    const int n0, const int wm0, const int wn0, const int tid, const LutOff *lutoff = nullptr) {
     const int lane = tid & 63;
     const int li = lane & 31;
@@ -214,8 +215,8 @@ __device__ __forceinline__ void epilogue_store_vec(const MitConvGemm &p, f32x16 
 // (wino_at6.h: same expressions, same order) in registers: no LDS, no cross-lane traffic.  The tile is there exactly when its first
 // position (r = 0) decodes to a live row: oy = 4 ty < Ho <=> ty < ceil(Ho / 4), the same along x; positions of an edge tile outside
 // Ho x Wo receive a value and stay dead rows that the store loops skip.
-template <int TM, int TN>
-__device__ __forceinline__ void wino_pre_add(const MitConvGemm &p, f32x16 (&acc)[TM][TN], const int M, const int m0, const int n0,
+template <int TM, int TN, class P>
+__device__ __forceinline__ void wino_pre_add(const P &p, f32x16 (&acc)[TM][TN], const int M, const int m0, const int n0,
                                              const int wm0, const int wn0, const int HoWo, const int tid) {
     const int lane = tid & 63;
     const int li = lane & 31;
@@ -250,8 +251,8 @@ __device__ __forceinline__ void wino_pre_add(const MitConvGemm &p, f32x16 (&acc)
 }
 
 // WINO: the kernel takes MitConvGemm.wino_m (the fast and split tiles; the launcher refuses it on the others)
-template <int BM, int TM, int TN, int SMEM_FLOATS = 0, int NTHR = 256, bool WINO = false>
-__device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM][TN], float *smem, const int M, const int m0,
+template <int BM, int TM, int TN, int SMEM_FLOATS = 0, int NTHR = 256, bool WINO = false, class P>
+__device__ __forceinline__ void epilogue(const P &p, f32x16 (&acc)[TM][TN], float *smem, const int M, const int m0,
                                          const int n0, const int wm0, const int wn0, const int z1, const int z0,
                                          const int HoWo, const int tid) {
     if (WINO && p.wino_m != nullptr) wino_pre_add<TM, TN>(p, acc, M, m0, n0, wm0, wn0, HoWo, tid);
@@ -311,9 +312,71 @@ __device__ __forceinline__ void epilogue(const MitConvGemm &p, f32x16 (&acc)[TM]
 #undef MIT_EPI
 }
 
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
-__global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, const int M, const int MT,
-                                                          const int NT, const int KT) {
+// ---- grouped launches (mit_conv_gemm_group): n convolutions that share everything but the image, as ONE grid ---------------------
+// The grid is the concatenation of the members' grids.  A workgroup forms its XCD-contiguous tile index over the group's total, finds
+// its member from the prefix of tile counts (blockIdx.x is wave-uniform: scalar loads and compares, nothing per lane), rebases the
+// index and runs the tile body of the single launch on a MemberView: the base descriptor with the member's pointers, sizes and
+// strides in place of its own.  The bodies are templates on the descriptor type for that; P = MitConvGemm is the single launch.
+constexpr int GROUP_MAX = MIT_CONV_GROUP_MAX;  // member records that travel by value in the kernel arguments (a larger group runs as several launches)
+struct GroupArgs {
+    MitConvGemm p;
+    MitConvGemmMember m[GROUP_MAX];
+    int32_t tile0[GROUP_MAX + 1];  // first tile of member i in the concatenated grid; tile0[n] = the grid
+    int32_t n;
+};
+static_assert(sizeof(GroupArgs) + 2 * sizeof(int) <= 4096, "a grouped launch's arguments must fit the kernel-argument segment");
+// What the tile bodies, decode_row and the epilogue read of a descriptor, under the names MitConvGemm gives them.  Every field is
+// wave-uniform (SGPRs); the options a grouped launch does not take are compile-time nulls, so their code is not generated.
+struct MemberView {
+    const float *a;
+    int64_t a_bs, a_ys, a_xs;
+    int32_t NB, Hi, Wi, Cin, Ho, Wo, sy, sx, ntaps, pad_mode;
+    const int8_t *tap_dy, *tap_dx;
+    const int32_t *tap_off;
+    const float *w;
+    int64_t ldw;
+    int32_t Kw, Nw, N;
+    MitTensorMap c;
+    const float *scale, *bias;
+    int32_t act;
+    float act_alpha;
+    const uint16_t *w_split;
+    const int64_t a_zs1 = 0, a_zs0 = 0, w_zs1 = 0, w_zs0 = 0, ws_zs0 = 0, lut_ld = 0, wino_zs = 0;
+    const int32_t zdiv = 1, live_img0 = 0, wino_n = 0, wino_th = 0, wino_tw = 0;
+    const MitTensorMap pre = {}, post = {};
+    const int32_t *const lut_rows = nullptr, *const live_blocks = nullptr, *const live_start = nullptr;
+    const float *const lut1 = nullptr, *const lut2 = nullptr, *const wino_m = nullptr;
+    __device__ __forceinline__ MemberView(const MitConvGemm &b, const MitConvGemmMember &m)
+        : a(m.a), a_bs(m.a_bs), a_ys(m.a_ys), a_xs(b.a_xs), NB(m.NB), Hi(m.Hi), Wi(m.Wi), Cin(b.Cin), Ho(m.Ho), Wo(m.Wo), sy(b.sy), sx(b.sx),
+          ntaps(b.ntaps), pad_mode(b.pad_mode), tap_dy(b.tap_dy), tap_dx(b.tap_dx), tap_off(b.tap_off), w(b.w), ldw(b.ldw), Kw(b.Kw), Nw(b.Nw),
+          N(b.N), c(b.c), scale(b.scale), bias(b.bias), act(b.act), act_alpha(b.act_alpha), w_split(b.w_split) {
+        c.base = m.c;
+        c.bs = m.c_bs;
+        c.ys = m.c_ys;
+    }
+};
+// the XCD-contiguous tile order: block b runs on XCD b % 8; each XCD gets a contiguous run of tiles, n fastest, so that tiles sharing
+// an A panel share an L2
+__device__ __forceinline__ int xcd_tile(const int bid, const int nwg) {
+    const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+// member of tile t of a grouped launch (wave-uniform)
+__device__ __forceinline__ int group_member(const GroupArgs &g, const int t) {
+    int mem = 0;
+    for (int i = 1; i < g.n; ++i) mem += t >= g.tile0[i] ? 1 : 0;
+    return mem;
+}
+// the grouped twin of a kernel: KERNEL##_group runs BODY on the member that owns the block's tile
+#define MIT_GROUP_PROLOGUE(BM_)                                                              \
+    const int gt = xcd_tile((int)blockIdx.x, g.tile0[g.n]);                                  \
+    const int mem = group_member(g, gt);                                                     \
+    const MemberView v(g.p, g.m[mem]);                                                       \
+    const int M = v.NB * v.Ho * v.Wo, MT = (M + (BM_) - 1) / (BM_);                          \
+    const int tile = gt - g.tile0[mem]
+
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, class P>
+__device__ __forceinline__ void conv_gemm_body(const P &p, const int M, const int MT, const int NT, const int KT, int bid) {
     constexpr int WM = BM / WAVES_M;  // wave tile rows
     constexpr int WN = BN / WAVES_N;
     constexpr int TM = WM / 32;  // 32x32 blocks per wave
@@ -344,14 +407,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, con
     const int li = lane & 31;
     const int lh = lane >> 5;
 
-    // ---- block -> tile mapping (XCD-aware: block b runs on XCD b % 8; give each XCD a
-    // contiguous run of tiles, n fastest, so tiles sharing an A panel share an L2) ----
-    const int nwg = MT * NT;
-    int bid = blockIdx.x;
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    // ---- tile mapping: bid is the block's position in the XCD-contiguous tile order (xcd_tile) ----
     const int mt = bid / NT, nt = bid - mt * NT;
     const int m0 = mt * BM, n0 = nt * BN;
     const int z = blockIdx.y;
@@ -495,6 +551,16 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, con
 
     epilogue<BM, TM, TN, 2 * A_TILE + 2 * B_TILE>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
 }
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(256) void conv_gemm_kernel(const MitConvGemm p, const int M, const int MT,
+                                                          const int NT, const int KT) {
+    conv_gemm_body<BM, BN, BK, WAVES_M, WAVES_N>(p, M, MT, NT, KT, xcd_tile((int)blockIdx.x, MT * NT));
+}
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
+__global__ __launch_bounds__(256) void conv_gemm_kernel_group(const GroupArgs g, const int NT, const int KT) {
+    MIT_GROUP_PROLOGUE(BM);
+    conv_gemm_body<BM, BN, BK, WAVES_M, WAVES_N>(v, M, MT, NT, KT, tile);
+}
 
 // ---- fast path: Cin % BK == 0, so every K-tile lies inside ONE tap ----------------------------
 // The gather geometry (reflect / zero padding, strides, tap offsets) is evaluated once per block
@@ -507,9 +573,8 @@ constexpr int FAST_MAX_TAPS = 16;
 
 // VAR = 4 (the only schedule built; it stays in the template-id, which profiles and the roofline name): gather offsets kept in
 // registers while the tap does not change + incremental weight pointer.
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR>
-__global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConvGemm p, const int M, const int MT,
-                                                               const int NT, const int KT) {
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int VAR, class P>
+__device__ __forceinline__ void conv_gemm_fast_body(const P &p, const int M, const int MT, const int NT, const int KT, const int bid) {
     constexpr int WM = BM / WAVES_M;
     constexpr int WN = BN / WAVES_N;
     constexpr int TM = WM / 32;
@@ -542,14 +607,7 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     const int li = lane & 31;
     const int lh = lane >> 5;
 
-    const int nwg = live_workgroups<BM>(p, MT, NT);
-    int bid = blockIdx.x;
-    if (bid >= nwg) return;  // (only with a live-block list: the tiles past the live rows)
-    {
-        const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
-    const int mt = bid / NT, nt = bid - mt * NT;
+    const int mt = bid / NT, nt = bid - mt * NT;  // bid: the block's position in the XCD-contiguous tile order (xcd_tile)
     const int m0 = mt * BM, n0 = nt * BN;
     const int z = blockIdx.y;
     const int z1 = z / p.zdiv, z0 = z - z1 * p.zdiv;
@@ -692,6 +750,18 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConv
     constexpr int SMEM_F = (2 * A_TILE + 2 * B_TILE) > EPI_FLOATS ? (2 * A_TILE + 2 * B_TILE) : EPI_FLOATS;
     epilogue<BM, TM, TN, SMEM_F, 256, true>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, (int)threadIdx.x);
 }
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR>
+__global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel(const MitConvGemm p, const int M, const int MT,
+                                                               const int NT, const int KT) {
+    const int nwg = live_workgroups<BM>(p, MT, NT);
+    if ((int)blockIdx.x >= nwg) return;  // (only with a live-block list: the tiles past the live rows)
+    conv_gemm_fast_body<BM, BN, BK, WAVES_M, WAVES_N, VAR>(p, M, MT, NT, KT, xcd_tile((int)blockIdx.x, nwg));
+}
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR>
+__global__ __launch_bounds__(256, MINW) void conv_gemm_fast_kernel_group(const GroupArgs g, const int NT, const int KT) {
+    MIT_GROUP_PROLOGUE(BM);
+    conv_gemm_fast_body<BM, BN, BK, WAVES_M, WAVES_N, VAR>(v, M, MT, NT, KT, tile);
+}
 // ---- N <= 4: one output column group per row — a dot product, not a tile ------------------------------------------------
 // An MFMA tile would idle >= 28 of its 32 columns (the ctd heads' last ConvTranspose2d 64 -> 1 and 16 -> 1 ran at 2 TFLOP/s on
 // the 128 x 32 tile).  Here LPR lanes share one output row: each tap's Cin contiguous floats are read as float4 by those lanes
@@ -812,6 +882,27 @@ void launch_fast(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_
     optin.ensure(reinterpret_cast<const void *>(kern), smem);
     dim3 grid(MT * NT, p.Z, 1);
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, p, M, MT, NT, KT);
+}
+// grouped twins: the same LDS sizes, the concatenated grid (GroupArgs.tile0[n] workgroups, Z == 1)
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
+void launch_generic_group(const GroupArgs &g, int NT, int KT, hipStream_t s) {
+    size_t smem = smem_bytes<BM, BN, BK, WAVES_M, WAVES_N>();
+    auto kern = conv_gemm_kernel_group<BM, BN, BK, WAVES_M, WAVES_N>;
+    static DynSmemOptIn optin;
+    optin.ensure(reinterpret_cast<const void *>(kern), smem);
+    hipLaunchKernelGGL(kern, dim3(g.tile0[g.n]), dim3(256), smem, s, g, NT, KT);
+}
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int VAR>
+void launch_fast_group(const GroupArgs &g, int NT, int KT, hipStream_t s) {
+    constexpr int LDA = BM + (BK == 16 ? 2 : 1);
+    constexpr int LDB = BN + 4;
+    size_t staging = (size_t)(2 * BK * LDA + 2 * BK * LDB) * sizeof(float) + (size_t)g.p.ntaps * BM * sizeof(int);
+    size_t rows = ((size_t)BM * sizeof(RowOff) + 15) / 16 * 16 + (size_t)4 * 32 * EPI_PITCH * sizeof(float) + (size_t)BM * sizeof(LutOff);
+    size_t smem = staging > rows ? staging : rows;
+    auto kern = conv_gemm_fast_kernel_group<BM, BN, BK, WAVES_M, WAVES_N, MINW, VAR>;
+    static DynSmemOptIn optin;
+    optin.ensure(reinterpret_cast<const void *>(kern), smem);
+    hipLaunchKernelGGL(kern, dim3(g.tile0[g.n]), dim3(256), smem, s, g, NT, KT);
 }
 template <int RPI, int NMAX, int KV, int LPR>
 void launch_gemv(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream_t s) {

@@ -41,9 +41,9 @@ __device__ __forceinline__ constexpr int split_swz(int kh) { return kh * (64 / B
 
 // VAR bits 1 + 128 (always together): software pipeline — the next tile's operands (loaded one iteration ahead) are split and written to
 // the other LDS buffer among this tile's MFMAs, and the loads of the tile after it are issued behind them; VAR 0: the plain schedule.
-template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
-__global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitConvGemm p, const int M, const int MT, const int NT,
-                                                                  const int KT) {
+// cur_tile: the block's position in the XCD-contiguous tile order (xcd_tile) — consecutive tiles (n fastest) share the A panel
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int NPROD, int VAR, class P>
+__device__ __forceinline__ void conv_gemm_split_body(const P &p, const int M, const int MT, const int NT, const int KT, const int cur_tile) {
     constexpr int WM = BM / WAVES_M;
     constexpr int WN = BN / WAVES_N;
     constexpr int TM = WM / 32;
@@ -87,13 +87,6 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     const int li = lane & 31;
     const int lh = lane >> 5;
 
-    const int nwg = live_workgroups<BM>(p, MT, NT);
-    if ((int)blockIdx.x >= nwg) return;  // (only with a live-block list: the tiles past the live rows)
-    int cur_tile;  // block id -> position in the XCD-contiguous order: consecutive tiles (n fastest) share the A panel
-    {
-        const int v = blockIdx.x, xcd = v & 7, q = nwg >> 3, r = nwg & 7;
-        cur_tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-    }
     int m0 = 0, n0 = 0;
     const int z = blockIdx.y;
     const int z1 = z / p.zdiv, z0 = z - z1 * p.zdiv;
@@ -355,6 +348,19 @@ __global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitCon
     const int tid_e = wave * 64 + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     epilogue<BM, TM, TN, SMEM_F, 256, true>(p, acc, smem, M, m0, n0, wm0, wn0, z1, z0, HoWo, tid_e);
 }
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
+__global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel(const MitConvGemm p, const int M, const int MT, const int NT,
+                                                                  const int KT) {
+    const int nwg = live_workgroups<BM>(p, MT, NT);
+    if ((int)blockIdx.x >= nwg) return;  // (only with a live-block list: the tiles past the live rows)
+    conv_gemm_split_body<BM, BN, BK, WAVES_M, WAVES_N, NPROD, VAR>(p, M, MT, NT, KT, xcd_tile((int)blockIdx.x, nwg));
+}
+// the grouped twin (MIT_GROUP_PROLOGUE, conv_gemm_kernels.h): the member lookup is scalar, the body is the one above
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
+__global__ __launch_bounds__(256, MINW) void conv_gemm_split_kernel_group(const GroupArgs g, const int NT, const int KT) {
+    MIT_GROUP_PROLOGUE(BM);
+    conv_gemm_split_body<BM, BN, BK, WAVES_M, WAVES_N, NPROD, VAR>(v, M, MT, NT, KT, tile);
+}
 
 // (A one-wave-per-32x32-block form with register-streamed operands for few-row GEMMs — a page's decoder Linears, M = 160 — was built and
 // measured in round 3: bit-identical to the tiles but 10-20 % SLOWER than the 64 x 64 tile at every decoder shape.  Prefetch depth 4 / 8 /
@@ -400,6 +406,19 @@ void launch_split(const MitConvGemm &p, int M, int MT, int NT, int KT, hipStream
     optin.ensure(reinterpret_cast<const void *>(kern), smem);
     dim3 grid(MT * NT, p.Z, 1);
     hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, p, M, MT, NT, KT);
+}
+template <int BM, int BN, int BK, int WAVES_M, int WAVES_N, int MINW, int NPROD, int VAR>
+void launch_split_group(const GroupArgs &g, int NT, int KT, hipStream_t s) {
+    constexpr int KH = BK / 8;
+    constexpr int SA = BM, SB = BN;
+    constexpr int NPL = NPROD == 1 ? 1 : 3;
+    size_t staging = (size_t)(2 * NPL * KH * SA + 2 * NPL * KH * SB) * 16 + (size_t)g.p.ntaps * BM * sizeof(int);
+    size_t rows = ((size_t)BM * sizeof(RowOff) + 15) / 16 * 16 + (size_t)4 * 32 * EPI_PITCH * sizeof(float) + (size_t)BM * sizeof(LutOff);
+    size_t smem = staging > rows ? staging : rows;
+    auto kern = conv_gemm_split_kernel_group<BM, BN, BK, WAVES_M, WAVES_N, MINW, NPROD, VAR>;
+    static DynSmemOptIn optin;
+    optin.ensure(reinterpret_cast<const void *>(kern), smem);
+    hipLaunchKernelGGL(kern, dim3(g.tile0[g.n]), dim3(256), smem, s, g, NT, KT);
 }
 
 }  // namespace mitcg

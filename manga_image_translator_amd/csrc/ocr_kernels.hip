@@ -57,6 +57,28 @@ __global__ void ocr_prep_kernel(const uint8_t *__restrict__ in, float4 *__restri
     }
 }
 
+// The chunks of a page group in one launch (mit_ocr_prep_ragged): a block converts MIT_OCR_PREP_BLOCK consecutive pixels of one segment,
+// found from the table's running block counts (blockIdx.x is wave-uniform: a scalar search).
+__global__ __launch_bounds__(256) void ocr_prep_ragged_kernel(const MitOcrPrepSeg *__restrict__ segs, const int nsegs, float4 *__restrict__ out, const int H) {
+    int s = 0;
+    for (int i = 1; i < nsegs; ++i) s += (int64_t)blockIdx.x >= segs[i].block_start ? 1 : 0;
+    const MitOcrPrepSeg sg = segs[s];
+    const int64_t npix = (int64_t)sg.N * H * sg.Wp;
+    const int64_t i0 = ((int64_t)blockIdx.x - sg.block_start) * MIT_OCR_PREP_BLOCK;
+    const uint8_t *__restrict__ in = sg.src;
+    float4 *__restrict__ o = out + sg.pixel_start;
+    for (int j = threadIdx.x; j < MIT_OCR_PREP_BLOCK; j += 256) {
+        const int64_t i = i0 + j;
+        if (i >= npix) break;
+        float4 v;
+        v.x = ((float)in[3 * i + 0] - 127.5f) / 127.5f;
+        v.y = ((float)in[3 * i + 1] - 127.5f) / 127.5f;
+        v.z = ((float)in[3 * i + 2] - 127.5f) / 127.5f;
+        v.w = 0.f;
+        o[i] = v;
+    }
+}
+
 // ---- depthwise k x k conv (stride 1, pad k/2) + per-channel scale/bias (conv bias + folded BN) ----
 // w layout [k*k][C]; 4 channels per thread.
 __global__ void dwconv_kernel(const float *__restrict__ in, const float *__restrict__ w, const float *__restrict__ scale,
@@ -1751,6 +1773,16 @@ extern "C" int mit_ocr_prep(const uint8_t *lines_dev, float *out_dev, int N, int
     hipLaunchKernelGGL(ocr_prep_kernel, dim3(grid_for(npix, 256)), dim3(256), 0, (hipStream_t)stream, lines_dev,
                        reinterpret_cast<float4 *>(out_dev), npix);
     MIT_CHECK_LAUNCH("mit_ocr_prep");
+    return 0;
+}
+
+extern "C" int mit_ocr_prep_ragged(const MitOcrPrepSeg *segs_dev, int nsegs, int64_t total_blocks, float *out_dev, int H, void *stream) {
+    if (!segs_dev || !out_dev) return mit_set_error("mit_ocr_prep_ragged: null pointer");
+    if (nsegs <= 0 || H <= 0 || total_blocks < 0 || total_blocks > 0x7fffffffLL) return mit_set_error("mit_ocr_prep_ragged: bad arguments");
+    if (total_blocks == 0) return 0;
+    hipLaunchKernelGGL(ocr_prep_ragged_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, segs_dev, nsegs,
+                       reinterpret_cast<float4 *>(out_dev), H);
+    MIT_CHECK_LAUNCH("mit_ocr_prep_ragged");
     return 0;
 }
 

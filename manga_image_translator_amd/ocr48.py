@@ -24,7 +24,7 @@ import torch
 from . import lib as _lib
 from . import ops
 from . import textline as TL
-from .lib import MitLinear, MitOcr48DecodeArgs, MitOcr48Decoder, MitXposTables
+from .lib import MIT_OCR_PREP_BLOCK, MitLinear, MitOcr48DecodeArgs, MitOcr48Decoder, MitOcrPrepSeg, MitXposTables
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU, bn_params, launch_conv_gemm, conv_gemm_desc, tensor_map
 
 EMBD, HEADS, HEAD_DIM, FF = 320, 4, 80, 2048
@@ -226,6 +226,7 @@ class Ocr48Engine(ops.Engine):
         d.dict_size = dict_size
         self.dec = d
         self.lines_attention_max_len = int(_lib.load().mit_attention_lines_xpos_max_len(HEAD_DIM))   # longest line of the one-launch form
+        self.grouped_convs = True          # False: the stem / downsampling convs and the input conversion chunk by chunk (A/B runs, tests)
         self.per_chunk_attention = False   # True: the encoder's attention chunk by chunk (rotate q, rotate k, attention): the reference form for tests
 
     # -- ConvNext_FeatureExtractor.forward (:262-276) -----------------------------------------
@@ -264,6 +265,15 @@ class Ocr48Engine(ops.Engine):
             g += n * h * ((w + 3) // 4)
         stage_tabs.append((bytes(segs), g))
 
+    def _conv_chunks(self, conv, xs, outs):
+        """A spatial convolution over the chunks of a group: one grouped launch (``mit_conv_gemm_group``: the chunks' grids back to
+        back), or with ``grouped_convs = False`` one launch per chunk.  Same bits either way."""
+        if self.grouped_convs:
+            ops.launch_conv_gemm_group([conv.desc(xi, oi) for xi, oi in zip(xs, outs)])
+        else:
+            for xi, oi in zip(xs, outs):
+                conv(xi, out=oi)
+
     @torch.no_grad()
     def encode_group(self, regions: Sequence[torch.Tensor], klen_all: torch.Tensor, Lmax: int, mem_k: Optional[torch.Tensor] = None,
                      mem_v: Optional[torch.Tensor] = None, first_lines: Optional[Sequence[int]] = None):
@@ -273,8 +283,9 @@ class Ocr48Engine(ops.Engine):
         lines [first_lines[c], first_lines[c] + N_c) (default: back to back from 0) of the pooled outputs
         mem_k / mem_v [5, n_lines, Lmax, 320] (allocated here when not given).  Every row-wise operator (the
         pointwise convs = 96 % of the backbone FLOPs, LayerNorm, all Linear layers) runs ONCE over the rows of all
-        chunks; only the spatial ops (stem / downsampling convs, XPOS rotation, attention) are launched per chunk and
-        the depthwise conv through its ragged form.  Row results do not depend on which other rows share a launch, so
+        chunks; the spatial ops run once per group too: the stem / downsampling convs as grouped launches (the chunks'
+        grids back to back, ``grouped_convs``), the input conversion, the depthwise conv and the attention through their
+        ragged forms.  Row results do not depend on which other rows share a launch, so
         this is bitwise identical to encode() chunk by chunk.  Returns (mem_k, mem_v, keep) when it allocated the pooled
         tensors, else the staging buffers to keep alive."""
         lib = _lib.load()
@@ -282,31 +293,45 @@ class Ocr48Engine(ops.Engine):
         nc = len(regions)
         Ns = [int(r.shape[0]) for r in regions]
         Wps = [int(r.shape[2]) for r in regions]
-        # ---- stem, per chunk (7x7 s1, 2x2 s2, 3x3 s1) ----
+        # ---- shapes of every layer, then the tables of the whole group (uploaded in one pinned copy): the ragged tables of the four
+        # stages and the segment table of the input conversion ----
         sh0 = [(n, 48, wp) for n, wp in zip(Ns, Wps)]
-        _, x_in, _ = self._cat_views("g.in", sh0, 4)
-        for r, xi in zip(regions, x_in):
-            _lib.check(lib.mit_ocr_prep(r.contiguous().data_ptr(), xi.data_ptr(), xi.shape[0], 48, xi.shape[2], st), "mit_ocr_prep")
-        cur, cur_sh = x_in, sh0
-        for ci, conv in enumerate(self.stem):
-            sh = [(n, *conv.out_hw(h, w)) for n, h, w in cur_sh]
-            flat, views, starts = self._cat_views(f"g.s{ci}", sh, conv.Cout)
-            for xi, oi in zip(cur, views):
-                conv(xi, out=oi)
-            cur, cur_sh = views, sh
-        # ---- ragged tables for the four stages (uploaded in one pinned copy) ----
+        in_flat, x_in, in_starts = self._cat_views("g.in", sh0, 4)
+        stem_shapes, sh = [], sh0
+        for conv in self.stem:
+            sh = [(n, *conv.out_hw(h, w)) for n, h, w in sh]
+            stem_shapes.append(sh)
         stage_shapes, tabs = [], []
-        sh = cur_sh
         for down in self.downs:
             stage_shapes.append(sh)
             rows = [n * h * w for n, h, w in sh]
             self._ragged_table(sh, np.concatenate([[0], np.cumsum(rows)]), tabs)
             sh = [(n, *down.out_hw(h, w)) for n, h, w in sh]
+        regions = [r.contiguous() for r in regions]
+        if self.grouped_convs:
+            segs, nblk = (MitOcrPrepSeg * nc)(), 0
+            for i, (r, (n, h, wp)) in enumerate(zip(regions, sh0)):
+                segs[i].src, segs[i].pixel_start, segs[i].block_start, segs[i].N, segs[i].Wp = r.data_ptr(), int(in_starts[i]), nblk, n, wp
+                nblk += -(-n * h * wp // MIT_OCR_PREP_BLOCK)
+            tabs.append((bytes(segs), nblk))
         blob = b"".join(t for t, _ in tabs)
         stage = torch.empty(len(blob), dtype=torch.uint8, pin_memory=True)
         stage.copy_(torch.frombuffer(bytearray(blob), dtype=torch.uint8))
         tab_dev = stage.to(self.device, non_blocking=True)
         tab_off = np.concatenate([[0], np.cumsum([len(t) for t, _ in tabs])])
+        # ---- input conversion and stem (7x7 s1, 2x2 s2, 3x3 s1): one launch each for the whole group ----
+        if self.grouped_convs:
+            _lib.check(lib.mit_ocr_prep_ragged(tab_dev.data_ptr() + int(tab_off[4]), nc, tabs[4][1], in_flat.data_ptr(), 48, st),
+                       "mit_ocr_prep_ragged")
+        else:
+            for r, xi in zip(regions, x_in):
+                _lib.check(lib.mit_ocr_prep(r.data_ptr(), xi.data_ptr(), xi.shape[0], 48, xi.shape[2], st), "mit_ocr_prep")
+        cur, cur_sh = x_in, sh0
+        for ci, conv in enumerate(self.stem):
+            sh = stem_shapes[ci]
+            flat, views, starts = self._cat_views(f"g.s{ci}", sh, conv.Cout)
+            self._conv_chunks(conv, cur, views)
+            cur, cur_sh = views, sh
         # ---- ConvNeXt stages ----
         for si, (blocks, down) in enumerate(zip(self.stages, self.downs)):
             sh = stage_shapes[si]
@@ -325,8 +350,7 @@ class Ocr48Engine(ops.Engine):
                 blk.mlp(t_flat, h_flat, x_flat, rows)
             nsh = [(n, *down.out_hw(h, w)) for n, h, w in sh]
             flat, views, starts = self._cat_views(f"g.d{si}", nsh, down.Cout)
-            for xi, oi in zip(cur, views):
-                down(xi, out=oi)
+            self._conv_chunks(down, cur, views)
             cur, cur_sh = views, nsh
         # ---- transformer encoder over the concatenated memory [sum N_c * L_c, 320] ----
         Ls = [w for _, _, w in cur_sh]

@@ -20,11 +20,11 @@ import torch
 
 from . import lib as _lib
 from .lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_SIGMOID, ACT_SILU, MIT_MAX_TAPS, PAD_REFLECT,
-                  PAD_ZERO, MitConvGemm, MitPGemm, MitRdbConv, MitTensorMap)
+                  PAD_ZERO, MitConvGemm, MitConvGemmMember, MitPGemm, MitRdbConv, MitTensorMap)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "ACT_LEAKY", "ACT_SILU", "ACT_SIGMOID", "ACT_GELU", "ACT_POST_FIRST", "PAD_ZERO", "PAD_REFLECT",
-    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "pack_rdb_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "current_stream",
+    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "pack_rdb_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "launch_conv_gemm_group", "conv_gemm_group_plan", "current_stream",
 ]
 
 
@@ -207,6 +207,39 @@ def launch_conv_gemm(desc: MitConvGemm, cfg: int = -1, stream: Optional[int] = N
     lib = _lib.load()
     s = current_stream() if stream is None else stream
     _lib.check(lib.mit_conv_gemm_cfg(C.byref(desc), cfg, C.c_void_p(s)), "mit_conv_gemm")
+
+
+def conv_gemm_members(descs: Sequence[MitConvGemm]):
+    """Member records of ``mit_conv_gemm_group`` from descriptors of the same layer over different images: ``descs[0]`` is the base
+    (weights, taps, strides, epilogue), every descriptor contributes its operand and result pointers, sizes and image / row strides."""
+    mem = (MitConvGemmMember * len(descs))()
+    for m, d in zip(mem, descs):
+        m.a, m.c = d.a, d.c.base
+        m.a_bs, m.a_ys, m.c_bs, m.c_ys = d.a_bs, d.a_ys, d.c.bs, d.c.ys
+        m.NB, m.Hi, m.Wi, m.Ho, m.Wo = d.NB, d.Hi, d.Wi, d.Ho, d.Wo
+    return mem
+
+
+def launch_conv_gemm_group(descs: Sequence[MitConvGemm], stream: Optional[int] = None) -> None:
+    """One layer over several images (``descs``: the layer's descriptor per image, equal but for the image) as ONE launch
+    (``mit_conv_gemm_group``); every image gets the bits of ``launch_conv_gemm`` on its descriptor alone."""
+    lib = _lib.load()
+    s = current_stream() if stream is None else stream
+    mem = conv_gemm_members(descs)
+    _lib.check(lib.mit_conv_gemm_group(C.byref(descs[0]), mem, len(descs), C.c_void_p(s)), "mit_conv_gemm_group")
+
+
+def conv_gemm_group_plan(descs: Sequence[MitConvGemm]):
+    """What ``launch_conv_gemm_group(descs)`` would do (no GPU needed): ``(tile name or None, launch, first_tile, ntiles)`` with one list
+    entry per member; ``launch[i]`` is -1 when the group runs member by member."""
+    lib = _lib.load()
+    n = len(descs)
+    tile = C.c_int32(-1)
+    launch, first, ntiles = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_int32 * n)()
+    _lib.check(lib.mit_conv_gemm_group_plan(C.byref(descs[0]), conv_gemm_members(descs), n, C.byref(tile), launch, first, ntiles),
+               "mit_conv_gemm_group_plan")
+    name = lib.mit_conv_gemm_config_name(tile.value) if tile.value >= 0 else None
+    return (name.decode() if name else None), list(launch), list(first), list(ntiles)
 
 
 def fold_bn(gamma: torch.Tensor, beta: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, eps: float,
