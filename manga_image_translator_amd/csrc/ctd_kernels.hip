@@ -186,8 +186,9 @@ __global__ void axpy_kernel(float4 *__restrict__ out, float a, const float4 *__r
 extern "C" int mit_maxpool2d_nhwc(const float *in_dev, float *out_dev, int B, int H, int W, int C, int k, int s, int p, void *stream) {
     if (!in_dev || !out_dev) return mit_set_error("mit_maxpool2d_nhwc: null pointer");
     if ((C & 3) || k <= 0 || s <= 0 || p < 0 || 2 * p > k) return mit_set_error("mit_maxpool2d_nhwc: bad geometry");
+    // a window that does not fit has no output pixel ((H + 2p - k) / s truncates towards zero: -1 / 2 + 1 would be 1)
+    if (B <= 0 || H + 2 * p < k || W + 2 * p < k) return mit_set_error("mit_maxpool2d_nhwc: empty output");
     const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
-    if (B <= 0 || Ho <= 0 || Wo <= 0) return mit_set_error("mit_maxpool2d_nhwc: empty output");
     const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(maxpool2d_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, B, H, W, C / 4,
                        Ho, Wo, k, s, p);
@@ -225,7 +226,8 @@ extern "C" int mit_ctd_prep(const uint8_t *img_dev, int B, int H, int W, int nh,
 extern "C" int mit_maxpool_nhwc(const float *in_dev, int64_t in_pixstride, float *out_dev, int64_t out_pixstride, int B,
                                 int H, int W, int C, int k, void *stream) {
     if (!in_dev || !out_dev) return mit_set_error("mit_maxpool_nhwc: null pointer");
-    if ((C & 3) || (in_pixstride & 3) || (out_pixstride & 3) || !(k & 1)) return mit_set_error("mit_maxpool_nhwc: C/strides %% 4, odd k");
+    if ((C & 3) || (in_pixstride & 3) || (out_pixstride & 3) || k < 1 || !(k & 1)) return mit_set_error("mit_maxpool_nhwc: C/strides %% 4, odd k >= 1");
+    if (in_pixstride < C || out_pixstride < C) return mit_set_error("mit_maxpool_nhwc: pixel stride smaller than C");
     const int64_t total = (int64_t)B * H * W * (C / 4);
     hipLaunchKernelGGL(maxpool_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, in_pixstride,
                        out_dev, out_pixstride, B, H, W, C / 4, k);
@@ -237,6 +239,7 @@ extern "C" int mit_avgpool2_nhwc(const float *in_dev, int64_t in_pixstride, floa
                                  int Ho, int Wo, int C, void *stream) {
     if (!in_dev || !out_dev) return mit_set_error("mit_avgpool2_nhwc: null pointer");
     if ((C & 3) || (in_pixstride & 3) || (out_pixstride & 3)) return mit_set_error("mit_avgpool2_nhwc: C/strides %% 4");
+    if (in_pixstride < C || out_pixstride < C) return mit_set_error("mit_avgpool2_nhwc: pixel stride smaller than C");
     const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(avgpool2_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, in_pixstride,
                        out_dev, out_pixstride, B, Ho, Wo, C / 4);
@@ -248,6 +251,7 @@ extern "C" int mit_copy_channels(const float *in_dev, int64_t in_pixstride, floa
                                  int64_t npix, int C, void *stream) {
     if (!in_dev || !out_dev) return mit_set_error("mit_copy_channels: null pointer");
     if ((C & 3) || (in_pixstride & 3) || (out_pixstride & 3)) return mit_set_error("mit_copy_channels: C/strides %% 4");
+    if (in_pixstride < C || out_pixstride < C) return mit_set_error("mit_copy_channels: pixel stride smaller than C");
     hipLaunchKernelGGL(copy_channels_kernel, dim3(grid_for(npix * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, in_dev,
                        in_pixstride, out_dev, out_pixstride, npix, C / 4);
     MIT_CHECK_LAUNCH("mit_copy_channels");
@@ -256,6 +260,7 @@ extern "C" int mit_copy_channels(const float *in_dev, int64_t in_pixstride, floa
 
 extern "C" int mit_map_to_u8(const float *in_dev, uint8_t *out_dev, int64_t n, int mode, float thr, void *stream) {
     if (!in_dev || !out_dev) return mit_set_error("mit_map_to_u8: null pointer");
+    if (mode < 0 || mode > 2) return mit_set_error("mit_map_to_u8: bad mode %d", mode);
     hipLaunchKernelGGL(map_to_u8_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, n, mode, thr);
     MIT_CHECK_LAUNCH("mit_map_to_u8");
     return 0;

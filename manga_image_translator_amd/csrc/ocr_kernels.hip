@@ -1871,8 +1871,9 @@ extern "C" int mit_avgpool_nhwc(const float *in_dev, float *out_dev, int B, int 
     if (!in_dev || !out_dev) return mit_set_error("mit_avgpool_nhwc: null pointer");
     if ((C & 3) || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 || 2 * ph > kh || 2 * pw > kw)
         return mit_set_error("mit_avgpool_nhwc: bad geometry (C %% 4 == 0, pad <= kernel / 2)");
+    // a window that does not fit has no output pixel ((H + 2p - k) / s truncates towards zero: -1 / 2 + 1 would be 1)
+    if (B <= 0 || H + 2 * ph < kh || W + 2 * pw < kw) return mit_set_error("mit_avgpool_nhwc: empty output");
     const int Ho = (H + 2 * ph - kh) / sh + 1, Wo = (W + 2 * pw - kw) / sw + 1;
-    if (B <= 0 || Ho <= 0 || Wo <= 0) return mit_set_error("mit_avgpool_nhwc: empty output");
     const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
     hipLaunchKernelGGL(avgpool_general_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, B, H, W,
                        C / 4, Ho, Wo, kh, kw, sh, sw, ph, pw);
@@ -1884,6 +1885,7 @@ extern "C" int mit_affine_act_nhwc(const float *in_dev, int64_t in_pixstride, co
                                    float *out_dev, int64_t out_pixstride, int64_t npix, int C, int relu, void *stream) {
     if (!in_dev || !scale_dev || !bias_dev || !out_dev) return mit_set_error("mit_affine_act_nhwc: null pointer");
     if ((C & 3) || (in_pixstride & 3) || (out_pixstride & 3)) return mit_set_error("mit_affine_act_nhwc: C and pixel strides must be multiples of 4");
+    if (in_pixstride < C || out_pixstride < C) return mit_set_error("mit_affine_act_nhwc: pixel stride smaller than C");
     if (npix <= 0) return 0;
     hipLaunchKernelGGL(affine_act_kernel, dim3(grid_for(npix * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, in_dev, in_pixstride,
                        scale_dev, bias_dev, out_dev, out_pixstride, npix, C / 4, relu);
@@ -1948,6 +1950,7 @@ extern "C" int mit_xpos_rotate(const float *in_dev, int64_t in_rs, int64_t in_ts
                                void *stream) {
     if (!in_dev || !out_dev) return mit_set_error("mit_xpos_rotate: null pointer");
     if (R <= 0 || T <= 0) return 0;
+    if (i0 < 0) return mit_set_error("mit_xpos_rotate: XPOS position out of table range (i0 %d < 0)", i0);  // check_tables bounds the upper end
     if (check_tables(tables, i0 + T, p0, p0 + T - 1, "mit_xpos_rotate")) return 1;
     ocrk_xpos_rotate(in_dev, in_rs, in_ts, out_dev, out_rs, out_ts, R, T, i0, p0, downscale, *tables, (hipStream_t)stream);
     MIT_CHECK_LAUNCH("mit_xpos_rotate");
