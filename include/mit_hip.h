@@ -804,6 +804,28 @@ int mit_mask_assign_lines_dev(uint8_t *mask_dev, int H, int W, const int32_t *bo
  * i64 [n_jobs] ascending, total = bytes of all crops; out_dev is the packed crop buffer mit_densecrf_refine reads as mask_dev. */
 int mit_mask_line_crops_dev(const void *ws_dev, int64_t ws_bytes, int H, int W, const int32_t *jobs_dev, const int64_t *offsets_dev,
                             int n_jobs, int64_t total, uint8_t *out_dev, void *stream);
+/* The --ignore-bubble stage of mask_refinement.dispatch (mask_refinement/__init__.py:31-50, utils/bubble.py:28-84) on the DEVICE
+ * (csrc/bubble.hip): mask_dev u8 [H,W] (the refined mask at page size) is dilated by a k x k square (k = int(max(H, W) * 0.025), anchor
+ * k / 2, 0 copies), and every external contour of the result — an 8-connected component of the dilated mask with its holes filled — whose
+ * page rectangle (its bounding rectangle, one pixel larger to the right and below, clamped) is_ignore() rejects is cleared: when
+ * lo <= total - bright <= hi, bright = the elements > 127 of page_dev u8 [H,W,3] inside the rectangle AND inside the 2-pixel frame of
+ * the whole page, total = the frame's elements, or when more than 10 of the rectangle's pixels are coloured (sum_c (1000 c - G)^2 >
+ * 10^8, G = 299 r + 587 g + 114 b: the reference's float64 rule on every colour).  [lo, hi] is the integer form of the reference's
+ * `ignore_bubble <= round(v / total, 6) * 100 <= 100 - ignore_bubble` (mask_refinement.bubble_interval); lo > hi switches that rule off.
+ * out_dev u8 [H,W] receives the bytes of mask_refinement.bubble_filter and may be mask_dev.  ws_dev: 4-byte aligned,
+ * mit_bubble_filter_workspace_bytes(H, W) bytes (planes of H*W entries: no cap on the number of components); negative for H or W < 4
+ * or H * W >= 2^31.  Asynchronous on the stream; no allocation, no synchronisation, no host round trip. */
+int64_t mit_bubble_filter_workspace_bytes(int H, int W);
+int mit_bubble_filter(const uint8_t *mask_dev, const uint8_t *page_dev, int H, int W, int k, int lo, int hi, uint8_t *out_dev, void *ws_dev,
+                      int64_t ws_bytes, void *stream);
+/* is_ignore() (utils/bubble.py:28-84) on the lines of a rectified chunk, where the OCR models call it per crop
+ * (ocr/model_48px_ctc.py:90, ocr/model_32px.py:84, manga_translator.py:1358): region_dev u8 [n,h,wp,3], lines_dev i32 [n,3] = (w, lo, hi)
+ * per line, 2 <= w <= wp.  Line j is rejected when lo <= dark <= hi, dark = the elements <= 127 of the crop's 2-pixel frame counted
+ * slice by slice ([0:2, 0:w], [h-2:h, 0:w], [2:h-2, 0:2], [2:h-2, w-2:w]: the last two overlap for w < 4), or when more than 10 of
+ * its pixels are coloured (the rule above).  flags_dev u8 [n]: 1 rejected — all h*wp*3 bytes of the line are then set to zero, as the
+ * reference's `continue` leaves its row of the chunk —, 0 kept, 2 for a width outside 2..wp (nothing read or written).  Columns >= w
+ * are never read.  One workgroup per line; asynchronous on the stream. */
+int mit_bubble_crop_flags(uint8_t *region_dev, int n, int h, int wp, const int32_t *lines_dev, uint8_t *flags_dev, void *stream);
 /* merge_mask_list of the ctd detector's refine_mask (detection/ctd_utils/textmask.py:74-132; filter_with_lines False), HOST
  * pointers: n_cands candidate masks [n_cands][h*w] (0 / 255) with their xor scores, the network's mask window pred_mask [h*w];
  * merged [h*w] receives the result.  Candidates in ascending score, their 8-connected components in raster order of the first

@@ -292,8 +292,10 @@ class CoupledPageEngine:
 
     # ---- stages 3 + 4: text-line merge, mask refinement -------------------------------------------------------------------
     def merge_and_refine(self, pages_u8: torch.Tensor, textlines: List[List[Quadrilateral]], mask_raw: torch.Tensor,
-                         given: Optional[Sequence] = None, dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE):
-        """``given``: per page None or the request's final mask (u8 [H,W], host or device): that page skips merge + refinement."""
+                         given: Optional[Sequence] = None, dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE,
+                         ignore_bubble: int = 0):
+        """``given``: per page None or the request's final mask (u8 [H,W], host or device): that page skips merge + refinement.
+        ``ignore_bubble`` in 1..50: the refinement's bubble stage (``MR.dispatch_device``), on the device like the rest."""
         B, H, W, _ = pages_u8.shape
         given = list(given) if given is not None else [None] * B
         main = torch.cuda.current_stream()
@@ -327,7 +329,7 @@ class CoupledPageEngine:
             torch.cuda.set_device(dev_index)
             with torch.no_grad(), torch.cuda.stream(side):
                 m = MR.dispatch_device(regions[b], pages_u8[b], mask_raw[b], dilation_offset=dilation_offset, kernel_size=kernel_size,
-                                       backend=self._mask_backend())
+                                       backend=self._mask_backend(), ignore_bubble=ignore_bubble)
                 final[b] = m
                 return True
 
@@ -353,7 +355,8 @@ class CoupledPageEngine:
             inject=None, group: Optional[int] = 16, textlines: Optional[Sequence] = None, mask_raw: Optional[Sequence] = None,
             mask: Optional[Sequence] = None, mask_dilation_offset: int = MASK_DILATION_OFFSET, kernel_size: int = KERNEL_SIZE,
             inpainting_size: Optional[int] = None, precision: str = "fp32", detect_size: int = DETECT_SIZE,
-            text_threshold: float = TEXT_THRESHOLD, box_threshold: float = DET_BOX_THRESHOLD, unclip_ratio: float = UNCLIP_RATIO) -> CoupledResult:
+            text_threshold: float = TEXT_THRESHOLD, box_threshold: float = DET_BOX_THRESHOLD, unclip_ratio: float = UNCLIP_RATIO,
+            ignore_bubble: int = 0) -> CoupledResult:
         """``group``: pages per pipeline slot.  A batch larger than one group flows through three stage threads (detector + boxes +
         refine_mask | OCR | merge + mask refinement + LaMa), each working on a different group at a time, so the host phases of one
         group run while the kernels of its neighbours execute; every stage sees the groups in order and owns its engines, and each
@@ -368,7 +371,9 @@ class CoupledPageEngine:
         ``detect_size`` / ``text_threshold`` / ``box_threshold`` / ``unclip_ratio``: the detector's parameters (DetectorConfig,
         config.py:274-290), for a DBNet engine; the ctd engine ignores them as the reference's ctd does (fixed 1024, 0.3, 0.6, 1.5).
         With a DBNet engine a request's ``mask_raw`` may be page-sized or of the detector's mask size; ``CoupledResult.mask_raw`` is
-        then a list when the sizes differ between pages."""
+        then a list when the sizes differ between pages.  ``ignore_bubble`` (``--ignore-bubble``, 1..50; 0 = off): mask refinement
+        ends with the bubble stage (mask_refinement/__init__.py:31-50), on the device; a page whose ``mask`` the request brings skips
+        it with the rest of the refinement.  (The OCR models' crop test of the same option belongs to the ctc / 32px models.)"""
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"CoupledPageEngine.run: precision must be 'fp32' or 'bf16' (got {precision!r})")
         if pages_u8.dtype != torch.uint8 or pages_u8.dim() != 4 or pages_u8.shape[-1] != 3 or not pages_u8.is_cuda:
@@ -378,6 +383,7 @@ class CoupledPageEngine:
             if v is not None and len(v) != B:
                 raise ValueError(f"CoupledPageEngine.run: {name} must have one entry per page ({len(v)} for {B} pages)")
         req = {"textlines": textlines, "mask_raw": mask_raw, "mask": mask, "offset": int(mask_dilation_offset), "kernel": int(kernel_size),
+               "ignore_bubble": int(ignore_bubble),
                "inpainting_size": inpainting_size, "precision": precision,
                "det": {"detect_size": int(detect_size), "text_threshold": float(text_threshold), "box_threshold": float(box_threshold),
                        "unclip_ratio": float(unclip_ratio)}}
@@ -391,7 +397,7 @@ class CoupledPageEngine:
         tl = self.recognize(pages_u8, tl, max_seq_length, suppress_eos, prob_threshold)
         sec["ocr"] = time.perf_counter() - t
         t = time.perf_counter()
-        regions, final = self.merge_and_refine(pages_u8, tl, mraw, mask, req["offset"], req["kernel"])
+        regions, final = self.merge_and_refine(pages_u8, tl, mraw, mask, req["offset"], req["kernel"], req["ignore_bubble"])
         sec["textline_merge+mask_refinement"] = time.perf_counter() - t
         t = time.perf_counter()
         inpainted = torch.empty_like(pages_u8)
@@ -480,7 +486,7 @@ class CoupledPageEngine:
         def st_tail(a, b, f_ocr):
             tl, mraw = f_ocr.result()
             given = None if req["mask"] is None else req["mask"][a:b]
-            regions, m = timed("textline_merge+mask_refinement", self.merge_and_refine, pages_u8[a:b], tl, mraw, given, req["offset"], req["kernel"])
+            regions, m = timed("textline_merge+mask_refinement", self.merge_and_refine, pages_u8[a:b], tl, mraw, given, req["offset"], req["kernel"], req["ignore_bubble"])
             with torch.cuda.stream(st["tail"]):
                 mask[a:b] = m
                 if mask_raw_all is not None:

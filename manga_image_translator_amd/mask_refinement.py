@@ -10,7 +10,9 @@ dilation-size arithmetic, elliptical dilation, the final merge.  On the GPU (def
 (``text_mask_utils.refine_mask`` -> pydensecrf), all lines of the page in ONE batched call (``mit_densecrf_refine``) on the
 filtered page that never leaves the device — and, when the raw mask is a device tensor (``dispatch_device``, the serving path), the
 component labelling, the line assignment and the crops as well (``GpuMaskBackend.assign_lines_device``, csrc/mask_assign.hip: the same
-decisions as the host code, only the line rectangles come back).  There is no CPU substitute: without the HIP library / a GPU the default backend
+decisions as the host code, only the line rectangles come back) and the ``--ignore-bubble`` stage that ends ``dispatch``
+(``GpuMaskBackend.bubble_filter``, csrc/bubble.hip: the bytes of ``bubble_filter`` below, which stays as the statement of the stage and as
+the path of callable backends).  There is no CPU substitute: without the HIP library / a GPU the default backend
 raises.  ``refine=`` / ``bilateral=`` still inject per-crop / per-page callables (the reference's own, or the stubs the pin uses).
 Pinned against the reference's Python, run with stand-ins for cv2 / shapely and the same two callables stubbed on both sides
 (tests/golden/mask_refinement.npz, oracle/make_golden.py); the GPU steps are checked against oracle/densecrf.py and
@@ -67,6 +69,7 @@ class GpuMaskBackend:
         self.gpu_assign = gpu_assign
         self.device_assigns = 0
         self._assign_ws = None
+        self._bubble_ws = None
         self._rects_pinned = None
         lib.load()  # fails loudly without the HIP library
         if device is None:
@@ -216,9 +219,43 @@ class GpuMaskBackend:
         line_rects = [None if rects[4 * i] < 0 else [int(v) for v in rects[4 * i:4 * i + 4]] for i in range(M)]
         return line_rects, (lambda i, x, y, w, h: crops([(i, x, y, w, h)])[0]), crops, packed
 
+    def bubble_filter(self, mask_dev, page_dev, ignore_bubble: int):
+        """``bubble_filter`` (the ``--ignore-bubble`` stage, mask_refinement/__init__.py:31-50) on the device: u8 [H, W] mask and u8
+        [H, W, 3] page device tensors of one size, both sides at least 4 -> the stage's mask as a new device tensor, byte for byte the
+        host routine's (``mit_bubble_filter``, csrc/bubble.hip).  Nothing crosses PCIe: the frame rule goes down as the integer
+        interval ``bubble_interval`` finds on the host once per page."""
+        import ctypes as C
+
+        import torch
+
+        from . import lib as _lib, ops
+
+        L = _lib.load()
+        if not 1 <= ignore_bubble <= 50:
+            raise ValueError(f"bubble_filter: ignore_bubble {ignore_bubble} outside 1..50")
+        for t, shape in ((mask_dev, 2), (page_dev, 3)):
+            if t.dtype != torch.uint8 or t.dim() != shape or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("bubble_filter: contiguous uint8 device tensors [H, W] (mask) and [H, W, 3] (page) are required")
+        H, W = mask_dev.shape
+        if tuple(page_dev.shape) != (H, W, 3):
+            raise ValueError(f"bubble_filter: page {tuple(page_dev.shape)} does not match the {H}x{W} mask")
+        need = int(L.mit_bubble_filter_workspace_bytes(H, W))
+        if need < 0:
+            raise ValueError(f"bubble_filter: bad mask shape {H}x{W}")
+        if self._bubble_ws is None or self._bubble_ws.numel() < need:
+            self._bubble_ws = None
+            self._bubble_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        lo, hi = bubble_interval((H * W - (H - 4) * (W - 4)) * 3, ignore_bubble)
+        out = torch.empty_like(mask_dev)
+        _lib.check(L.mit_bubble_filter(mask_dev.data_ptr(), page_dev.data_ptr(), H, W, int(max(H, W) * 0.025), lo, hi, out.data_ptr(),
+                                       self._bubble_ws.data_ptr(), self._bubble_ws.numel(), C.c_void_p(ops.current_stream())),
+                   "mit_bubble_filter")
+        return out
+
     def release_workspace(self):
         self._crf.release_workspace()
         self._assign_ws = None
+        self._bubble_ws = None
 
 
 _DEFAULT_BACKEND = None
@@ -521,6 +558,32 @@ def HG_area(pts: np.ndarray) -> float:
     return float(abs(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1))) / 2)
 
 
+def bubble_interval(total: int, ignore_bubble: int):
+    """The integers v in 0..total for which ``ignore_bubble <= round(v / total, 6) * 100 <= 100 - ignore_bubble`` — the frame rule of
+    ``is_ignore`` / ``bubble_filter``, Python's decimal ``round`` included — as an inclusive interval (lo, hi); lo > hi when no v
+    qualifies.  The expression is evaluated as it stands and only searched: ``round(v / total, 6) * 100`` does not decrease with v, so
+    the v that reach the lower bound and the v that stay under the upper one are each found by bisection.  The device kernels compare
+    counts against this interval and never restate the rounding."""
+    total, ignore_bubble = int(total), int(ignore_bubble)
+    if total <= 0:
+        raise ValueError("bubble_interval: the frame has no elements")
+    ratio = lambda v: round(v / total, 6) * 100
+
+    def first(pred):   # smallest v in 0..total + 1 with pred(v); pred is False ... False True ... True over 0..total
+        a, b = 0, total + 1
+        while a < b:
+            m = (a + b) // 2
+            if pred(m):
+                b = m
+            else:
+                a = m + 1
+        return a
+
+    lo = first(lambda v: ratio(v) >= ignore_bubble)
+    hi = first(lambda v: ratio(v) > 100 - ignore_bubble) - 1
+    return lo, hi
+
+
 def bubble_filter(final_mask: np.ndarray, raw_image: np.ndarray, ignore_bubble: int) -> np.ndarray:
     """The ``--ignore-bubble`` stage of mask_refinement.dispatch (:34-50): dilate the mask by a square of 2.5 % of the longer page side,
     and for every outer contour of the result look at the page inside the contour's bounding rectangle (one pixel larger to the right /
@@ -558,16 +621,19 @@ def dispatch_sync(text_regions, raw_image: np.ndarray, raw_mask: np.ndarray, met
                   bilateral: Optional[BilateralFn] = None, backend=None, device_result: bool = False) -> np.ndarray:
     """mask_refinement.dispatch (:9-50) for ``method='fit_text'``; ``ignore_bubble`` in 1..50 adds the bubble stage (``bubble_filter``).
     With the GPU backend ``raw_image`` / ``raw_mask`` may be device tensors (a batch engine keeps pages and masks resident), and
-    ``device_result`` returns the final mask as a device tensor (no bubble stage then: it needs the page on the host)."""
-    if device_result and 1 <= ignore_bubble <= 50:
-        raise NotImplementedError("mask refinement: the --ignore-bubble stage runs on the host (device_result=False)")
+    ``device_result`` returns the final mask as a device tensor.  The bubble stage runs where the mask is: on the device
+    (``GpuMaskBackend.bubble_filter``) right after the resize back to page size whenever the backend's tail left the mask there, in
+    numpy for callable backends, a host tail, a page with a side below 4 pixels or one that is not [H, W, 3] — the same bytes."""
     if method != "fit_text":
         raise NotImplementedError("mask refinement: only method='fit_text' is native (the reference's 'fill' path references an unset variable)")
+    bubble = 1 <= ignore_bubble <= 50
     h, w = raw_image.shape[:2]
     scale = max(min((raw_mask.shape[0] - h / 3) / raw_mask.shape[0], 1), 0.5)
     size = (int(w * scale), int(h * scale))
     be = _backend_for(refine, bilateral, backend)
-    img_small = be.resize_image(raw_image, size)  # a device tensor with the GPU backend: it never comes back to the host
+    # device backend: the page goes up once, for the resize and for the bubble stage
+    page = be._dev(raw_image) if hasattr(be, "bubble_filter") else raw_image
+    img_small = be.resize_image(page, size)  # a device tensor with the GPU backend: it never comes back to the host
     if hasattr(be, "resize_binarize"):  # device backend: resize and "> 0 -> 255" there; complete_mask labels it where it is
         mask_small = be.resize_binarize(be._dev(raw_mask), size)
     else:
@@ -578,20 +644,24 @@ def dispatch_sync(text_regions, raw_image: np.ndarray, raw_mask: np.ndarray, met
                           device_result=True)
     if final is None:
         final = np.zeros((h, w), dtype=np.uint8)
+        bubble = False   # the stage applied to the zero mask: nothing to dilate, no contour, the zero mask
     elif isinstance(final, np.ndarray):
         final = be.resize_mask(final, (w, h)).copy()
         final[final > 0] = 255
-    else:  # device tensor from the GPU tail: resize and binarise there, one download
+    else:  # device tensor from the GPU tail: resize and binarise there, the bubble stage too, one download
         final = be.resize_binarize(final, (w, h))
-        if device_result:
+        if bubble and min(h, w) >= 4 and tuple(page.shape[2:]) == (3,):
+            final = be.bubble_filter(final, page.contiguous(), ignore_bubble)
+            bubble = False
+        if device_result and not bubble:
             return final
         final = final.cpu().numpy()
+    if bubble:
+        final = bubble_filter(final, raw_image if isinstance(raw_image, np.ndarray) else raw_image.cpu().numpy(), ignore_bubble)
     if device_result:
         import torch
 
         return torch.from_numpy(final).to(be.device)
-    if 1 <= ignore_bubble <= 50:
-        final = bubble_filter(final, np.asarray(raw_image), ignore_bubble)
     return final
 
 
@@ -600,8 +670,9 @@ async def dispatch(text_regions, raw_image: np.ndarray, raw_mask: np.ndarray, me
     return dispatch_sync(text_regions, raw_image, raw_mask, method, dilation_offset, ignore_bubble, verbose, kernel_size, **kw)
 
 
-def dispatch_device(text_regions, page_dev, mask_dev, dilation_offset: int = 0, kernel_size: int = 3, backend=None):
+def dispatch_device(text_regions, page_dev, mask_dev, dilation_offset: int = 0, kernel_size: int = 3, backend=None, ignore_bubble: int = 0):
     """``dispatch`` for a device-resident page (u8 [H,W,3]) and raw mask (u8 [H,W]); returns the refined mask on the device.  Only the
-    line rectangles cross PCIe (the components are labelled, assigned and cropped on the device: ``GpuMaskBackend.assign_lines_device``)."""
-    return dispatch_sync(text_regions, page_dev, mask_dev, "fit_text", dilation_offset, 0, False, kernel_size, backend=backend or default_backend(),
-                         device_result=True)
+    line rectangles cross PCIe (the components are labelled, assigned and cropped on the device: ``GpuMaskBackend.assign_lines_device``);
+    ``ignore_bubble`` in 1..50 adds the bubble stage, on the device as well."""
+    return dispatch_sync(text_regions, page_dev, mask_dev, "fit_text", dilation_offset, ignore_bubble, False, kernel_size,
+                         backend=backend or default_backend(), device_result=True)

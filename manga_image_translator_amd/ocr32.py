@@ -226,18 +226,20 @@ class Ocr32Engine(ops.Engine):
         return out
 
     @torch.no_grad()
-    def recognize_lines(self, page_u8: torch.Tensor, quads, directions, max_seq_length: int = 255, reject=None):
+    def recognize_lines(self, page_u8: torch.Tensor, quads, directions, max_seq_length: int = 255, reject=None, ignore_bubble: int = 0):
         """page_u8 [1,H,W,3] u8 (device); quads = textline.Quadrilateral list, directions per quad.  Every line is rectified on the GPU
         at height 32 straight into its chunk tensor, chunks (sorted by crop width, 16 lines, padded to max + 7) are encoded one by one and
         all lines decoded in one pooled beam search.  ``reject(crop u8 [32, w, 3] ndarray) -> bool`` (optional): a rejected line's rows
-        are zeroed before encoding and it is still decoded, as the reference's ``continue`` leaves it (:84-86).
+        are zeroed before encoding and it is still decoded, as the reference's ``continue`` leaves it (:84-86).  ``ignore_bubble`` in
+        1..50 (and no ``reject``): the reference's own rule, ``textline.is_ignore``, judged on the device without fetching a crop.
         Returns decode()'s dict plus ``order`` (quad index per result row)."""
         if page_u8.dtype != torch.uint8 or page_u8.dim() != 4 or page_u8.shape[0] != 1 or page_u8.shape[-1] != 3:
             raise ValueError(f"recognize_lines expects u8 [1,H,W,3], got {page_u8.dtype} {tuple(page_u8.shape)}")
         if len(quads) == 0:
             return dict(order=[], tokens=None)
         order, enc = [], []
-        for idx, ws, region in TL.rectified_chunks(page_u8.contiguous(), quads, directions, TEXT_HEIGHT, reject=reject):
+        for idx, ws, region in TL.rectified_chunks(page_u8.contiguous(), quads, directions, TEXT_HEIGHT, reject=reject,
+                                                      ignore_bubble=ignore_bubble):
             enc.append(self.encode(region, ws))
             order += list(idx)
         out = self.decode_chunks(enc, max_seq_length)

@@ -176,8 +176,9 @@ def _ocr_options(config, default_threshold: float) -> Tuple[float, int]:
 
 
 def _bubble_reject(ignore_bubble: int) -> Optional[Callable]:
-    """``textline.is_ignore`` at this setting as the ``reject`` of ``textline.rectified_chunks``; None where the filter is off (outside
-    1..50), so that no crop is fetched to the host for it."""
+    """``textline.is_ignore`` at this setting as a ``reject`` of ``textline.rectified_chunks`` — the host form of the rule, for callers
+    that inject or wrap one (the plugins themselves pass ``ignore_bubble=`` and the test runs on the device); None where the filter is
+    off (outside 1..50), so that no crop is fetched to the host for it."""
     from . import textline as TL
 
     return (lambda crop: TL.is_ignore(crop, ignore_bubble)) if 1 <= ignore_bubble <= 50 else None
@@ -517,7 +518,8 @@ class HipModel48pxCTCOCR(HipModel48pxOCR):
         """Same contract as the 48px plugin; chunks are padded to max_w + 7 + 128 (:84), the line probability is
         exp(mean log-prob) against a 0.5 default threshold (:66,:124), colours average over non-space characters (:116-123).
         ``config.ignore_bubble`` in 1..50 applies the reference's frame / colour heuristic to every rectified crop (:91-93, utils/bubble.py):
-        a rejected line's row of the chunk stays zero and is recognised as such, exactly as the reference's ``continue`` leaves it."""
+        a rejected line's row of the chunk stays zero and is recognised as such, exactly as the reference's ``continue`` leaves it.  The
+        test runs on the device, where the chunk is (``textline.bubble_crop_flags``)."""
         from . import ocr_ctc, textline as TL
 
         threshold, ignore_bubble = _ocr_options(config, 0.5)
@@ -525,8 +527,8 @@ class HipModel48pxCTCOCR(HipModel48pxOCR):
         if not quads:
             return []
         out = []
-        for idx, _, region in TL.rectified_chunks(self._page_on_device(image), own, dirs, 48, ocr_ctc.CHUNK_EXTRA, _bubble_reject(ignore_bubble),
-                                                  self._rectify):
+        for idx, _, region in TL.rectified_chunks(self._page_on_device(image), own, dirs, 48, ocr_ctc.CHUNK_EXTRA, None, self._rectify,
+                                                  ignore_bubble=ignore_bubble):
             logits, colors = self.engine.forward(region)
             for j, line in enumerate(self.engine.decode(logits, colors, 0)):
                 q = quads[idx[j]]
@@ -571,7 +573,7 @@ class HipModel32pxOCR(HipModel48pxOCR):
         quads, dirs, own = self._prepare(textlines)
         if not quads:
             return []
-        r = self.engine.recognize_lines(self._page_on_device(image), own, dirs, max_seq_length=max_seq_length, reject=_bubble_reject(ignore_bubble))
+        r = self.engine.recognize_lines(self._page_on_device(image), own, dirs, max_seq_length=max_seq_length, ignore_bubble=ignore_bubble)
         toks, lens = r["tokens"].cpu().numpy(), r["length"].cpu().numpy()
         probs, cols = r["prob"].cpu().numpy(), r["colors"].cpu().numpy()
         out = []

@@ -619,11 +619,48 @@ def rectify(page_u8: torch.Tensor, records, height: int, wp: int) -> torch.Tenso
     return region
 
 
-def rectified_chunks(page_u8: torch.Tensor, quads, directions, height: int, extra: int = 0, reject=None, rectify_fn=None):
+def crop_frame_total(height: int, width: int) -> int:
+    """Number of elements ``is_ignore`` puts into the frame ratio of a [height, width, 3] crop: the summed sizes of its four slices
+    (rows 0:2 and h-2:h over the whole width, columns 0:2 and w-2:w over the rows between, overlapping for widths below 4)."""
+    return 3 * (2 * 2 * width + 2 * 2 * max(height - 4, 0))
+
+
+def bubble_crop_flags(region: torch.Tensor, widths, ignore_bubble: int) -> torch.Tensor:
+    """``is_ignore`` on every line of a rectified chunk u8 [n, height, wp, 3] where it lies (mit_bubble_crop_flags): a rejected line's
+    rows are zeroed in place; returns the flags u8 [n] (1 rejected) on the device.  The frame rule goes down as the integer interval
+    of dark counts ``mask_refinement.bubble_interval`` finds, once per distinct line width; no crop comes to the host."""
+    from .mask_refinement import bubble_interval
+
+    n, height, wp = int(region.shape[0]), int(region.shape[1]), int(region.shape[2])
+    if region.dtype != torch.uint8 or region.dim() != 4 or region.shape[3] != 3 or not region.is_cuda or not region.is_contiguous():
+        raise ValueError("bubble_crop_flags: a contiguous uint8 device chunk [n, height, wp, 3] is required")
+    if not 1 <= ignore_bubble <= 50:
+        raise ValueError(f"bubble_crop_flags: ignore_bubble {ignore_bubble} outside 1..50")
+    if len(widths) != n or any(not 2 <= int(w) <= wp for w in widths):
+        raise ValueError(f"bubble_crop_flags: {n} line widths in 2..{wp} are required, got {list(widths)}")
+    intervals = {}
+    lines = np.empty((n, 3), dtype=np.int32)
+    for j, w in enumerate(widths):
+        w = int(w)
+        if w not in intervals:
+            intervals[w] = bubble_interval(crop_frame_total(height, w), ignore_bubble)
+        lines[j] = (w, *intervals[w])
+    table = torch.from_numpy(lines).to(region.device)
+    flags = torch.empty(n, dtype=torch.uint8, device=region.device)
+    _lib.check(_lib.load().mit_bubble_crop_flags(region.data_ptr(), n, height, wp, table.data_ptr(), flags.data_ptr(),
+                                                 ctypes.c_void_p(ops.current_stream())), "mit_bubble_crop_flags")
+    return flags
+
+
+def rectified_chunks(page_u8: torch.Tensor, quads, directions, height: int, extra: int = 0, reject=None, rectify_fn=None,
+                     ignore_bubble: int = 0):
     """The chunk loop of the reference's ``_infer`` for one page u8 [1,H,W,3]: ``warp_plans`` -> ``chunk_plan`` (+ ``extra`` padding
-    columns) -> ``rectify`` -> ``reject``.  ``reject(crop u8 [height, w, 3] ndarray) -> bool`` (optional): a rejected line's rows are
-    zeroed and it stays in its chunk, as the reference's ``continue`` leaves it.  ``rectify_fn(page, quads, directions, indices,
-    records, wp)`` (optional) stands in for ``rectify`` (a host twin in tests).  Yields (indices, widths, region u8 [n, height, wp, 3])."""
+    columns) -> ``rectify`` -> the ``--ignore-bubble`` crop test.  ``ignore_bubble`` in 1..50 runs ``is_ignore`` on the device
+    (``bubble_crop_flags``; on the host for a chunk that a ``rectify_fn`` made there).  ``reject(crop u8 [height, w, 3] ndarray) ->
+    bool`` (optional, for callers with a rule of their own) takes precedence and judges every crop on the host.  Either way a
+    rejected line's rows are zeroed and it stays in its chunk, as the reference's ``continue`` leaves it.  ``rectify_fn(page, quads,
+    directions, indices, records, wp)`` (optional) stands in for ``rectify`` (a host twin in tests).  Yields (indices, widths, region
+    u8 [n, height, wp, 3])."""
     rec = warp_plans(quads, list(directions), int(page_u8.shape[1]), int(page_u8.shape[2]), height)
     widths = np.where(rec["vertical"] != 0, rec["dh"], rec["dw"]).tolist()
     for idx, ws, wp in chunk_plan(widths):
@@ -632,11 +669,15 @@ def rectified_chunks(page_u8: torch.Tensor, quads, directions, height: int, extr
             region = rectify(page_u8, rec[idx], height, wp)
         else:
             region = rectify_fn(page_u8, quads, directions, idx, rec[idx].copy(), wp)
+        if reject is None and 1 <= ignore_bubble <= 50 and not region.is_cuda:   # a host twin's chunk: the host statement judges it
+            reject = lambda crop: is_ignore(crop, ignore_bubble)
         if reject is not None:
             host = region.cpu().numpy()
             for j, w_line in enumerate(ws):
                 if reject(host[j, :, :w_line]):
                     region[j] = 0
+        elif 1 <= ignore_bubble <= 50:
+            bubble_crop_flags(region, ws, ignore_bubble)
         yield idx, ws, region
 
 
