@@ -826,6 +826,28 @@ int mit_bubble_filter(const uint8_t *mask_dev, const uint8_t *page_dev, int H, i
  * reference's `continue` leaves its row of the chunk —, 0 kept, 2 for a width outside 2..wp (nothing read or written).  Columns >= w
  * are never read.  One workgroup per line; asynchronous on the stream. */
 int mit_bubble_crop_flags(uint8_t *region_dev, int n, int h, int wp, const int32_t *lines_dev, uint8_t *flags_dev, void *stream);
+/* The page filters of CommonDetector.detect (detection/common.py:18-35) on the DEVICE (csrc/det_filters.hip), for dense pages
+ * u8 [B,H,W,3].  The filtered frame is (W, H) when rotated (np.rot90(image, k=-1), :101-102), else (H, W); `side` > 0 adds the zero
+ * border of _add_border (:71-79) — the frame at the top left of a side x side square, side >= max(H, W) — and 0 adds none.  The order is
+ * the reference's: rotation, border, inversion (cv2.bitwise_not, :115-116), gamma (:118-124), so the border is inverted, counted in the
+ * gamma mean and sent through the gamma table like every other pixel.
+ * mit_det_filter_gray_sum: sums_dev u64 [B] (8-byte aligned) receives, per page, the sum over the filtered pre-gamma image of the 8-bit
+ * gray value cv2.cvtColor(image, COLOR_BGR2GRAY) (:119) in the fixed-point form (c0*1868 + c1*9617 + c2*4899 + 8192) >> 14 — the
+ * numerator of np.mean(gray) (:121), exact (integer partial sums and 64-bit atomics: no order dependence).  The rotation does not change
+ * it, so there is no rotate argument; a border pixel adds 0, or 255 under `invert`.
+ * mit_det_filter_apply: dst_dev u8 [B,fh,fw,3] (not src_dev) receives lut[b][inv(v)] for every byte v of the rotated, bordered page,
+ * inv(v) = 255 - v when `invert`; lut_dev u8 [B,256] is the per-page table np.power(...).clip(0, 255).astype(np.uint8) (:123) takes on
+ * the 256 byte values (det_filters.gamma_lut), NULL for no gamma.  Rotated: out[i, j] = src[H - 1 - j, i] through a padded LDS tile,
+ * reads and writes along image rows; any H and W.
+ * Arguments are checked before any HIP call (null pointers, non-positive sizes, a side smaller than the frame).  Asynchronous on the
+ * stream; no allocation, no synchronisation. */
+int mit_det_filter_gray_sum(const uint8_t *pages_dev, int B, int H, int W, int side, int invert, uint64_t *sums_dev, void *stream);
+int mit_det_filter_apply(const uint8_t *src_dev, int B, int H, int W, int rotate, int side, int invert, const uint8_t *lut_dev,
+                         uint8_t *dst_dev, void *stream);
+/* _remove_border's crop and _remove_rotation's np.rot90 (detection/common.py:84,87,105-107) on u8 maps [B,h,w] in one pass:
+ * out_dev u8 [B,cw,ch] (not maps_dev) = np.rot90(m[:ch, :cw]), i.e. out[i, j] = m[j, cw - 1 - i]; ch <= h, cw <= w (a crop outside the
+ * map is refused).  The same LDS tile as above.  Asynchronous on the stream. */
+int mit_det_unrotate_u8(const uint8_t *maps_dev, int B, int h, int w, int ch, int cw, uint8_t *out_dev, void *stream);
 /* merge_mask_list of the ctd detector's refine_mask (detection/ctd_utils/textmask.py:74-132; filter_with_lines False), HOST
  * pointers: n_cands candidate masks [n_cands][h*w] (0 / 255) with their xor scores, the network's mask window pred_mask [h*w];
  * merged [h*w] receives the result.  Candidates in ascending score, their 8-connected components in raster order of the first

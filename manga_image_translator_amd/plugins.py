@@ -159,6 +159,49 @@ class _EnginePlugin:
         return torch.from_numpy(np.ascontiguousarray(image)).to(self.engine.device)[None]
 
 
+class _FilteredDetector(_EnginePlugin):
+    """``CommonDetector.detect`` (detection/common.py:12-64) for the detector plugins, in both forms — it stands before the reference's
+    ``OfflineDetector`` in the method order, so it replaces the numpy ``detect`` the plugins would inherit there, and it gives the
+    stand-alone mirror the method it lacks.  The page is uploaded once and filtered on the device (``det_filters.apply``: rotate, the
+    border for pages under 400 px, invert, gamma), the network and the box extraction run where the filtered page is
+    (``_infer_device``), both masks are un-rotated and cropped on the device (``det_filters.undo``) and come down once.  The text lines
+    go the reference's way on the host, quirks included (``det_filters``).  ``infer`` / ``_infer`` are what they were."""
+
+    async def detect(self, image: np.ndarray, detect_size: int, text_threshold: float, box_threshold: float, unclip_ratio: float,
+                     invert: bool, gamma_correct: bool, rotate: bool, auto_rotate: bool = False, verbose: bool = False):
+        """-> (textlines, raw_mask, mask), the reference's signature and results."""
+        from . import det_filters as DF
+
+        if not self.is_loaded():
+            raise Exception(f"{self._key}: Tried to forward pass without having loaded the model.")
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise ValueError(f"expected uint8 RGB [H,W,3], got {image.dtype} {image.shape}")
+
+        if torch.device(self.engine.device).type != "cuda":   # a stand-in engine that lives on the host (tests/boundary_checks.py): the
+            # page never was on a device, so the numpy statements go around ``infer``, as the reference's own detect would
+            return await DF.detect(self.infer, image, detect_size, text_threshold, box_threshold, unclip_ratio, invert, gamma_correct,
+                                   rotate, auto_rotate, verbose)
+
+        async def net(filtered, *args):
+            return await self._infer_device(filtered[None], *args)
+
+        textlines, raw_mask, mask = await DF.detect(net, self._page_on_device(image)[0], detect_size, text_threshold, box_threshold,
+                                                    unclip_ratio, invert, gamma_correct, rotate, auto_rotate, verbose,
+                                                    apply_fn=DF.apply, undo_masks_fn=DF.undo)
+        down = lambda m: None if m is None else m.contiguous().cpu().numpy()   # noqa: E731
+        return textlines, down(raw_mask), down(mask)
+
+    async def _infer_device(self, page: torch.Tensor, detect_size: int, text_threshold: float, box_threshold: float,
+                            unclip_ratio: float, verbose: bool = False):
+        """``_infer`` for a page u8 [1,H,W,3] that is already on the device -> (textlines, raw_mask, mask), the masks device tensors.
+        This form is the one for every case a plugin has no device route for (an injected host step, a webtoon strip whose stitched mask
+        is finished on the host): the page goes through ``_infer`` on the host and the masks come back up."""
+        textlines, raw_mask, mask = await self._infer(np.ascontiguousarray(page[0].cpu().numpy()), detect_size, text_threshold,
+                                                      box_threshold, unclip_ratio, verbose)
+        up = lambda m: None if m is None else torch.from_numpy(np.ascontiguousarray(m)).to(page.device)   # noqa: E731
+        return textlines, up(raw_mask), up(mask)
+
+
 def _gpu_device(device: str) -> torch.device:
     """The reference passes 'cpu' | 'cuda' | 'mps' | 'xpu' (ROCm = 'cuda').  This backend has no CPU path."""
     if not str(device).startswith("cuda"):
@@ -192,7 +235,7 @@ def _accept(q, text: str, prob: float, fg, bg):
     return q
 
 
-class HipComicTextDetector(_EnginePlugin, _DetBase):
+class HipComicTextDetector(_FilteredDetector, _DetBase):
     """``--detector ctd`` on the HIP engine."""
     _KEY = _key = "ctd_hip"
     # the torch checkpoint of the reference's own mapping (detection/ctd.py:63-74; its ONNX twin is the reference's CPU path)
@@ -226,10 +269,23 @@ class HipComicTextDetector(_EnginePlugin, _DetBase):
         unclip_ratio (fixed 1024, 0.3, 0.6, 1.5: ctd.py:84,102,157)."""
         if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
             raise ValueError(f"expected uint8 RGB [H,W,3], got {image.dtype} {image.shape}")
-        im_h, im_w = image.shape[:2]
-        page = self._page_on_device(image)
+        textlines, mask = self._detect_page(self._page_on_device(image), image)
+        return textlines, mask if isinstance(mask, np.ndarray) else mask.cpu().numpy(), None
+
+    async def _infer_device(self, page: torch.Tensor, detect_size: int, text_threshold: float, box_threshold: float,
+                            unclip_ratio: float, verbose: bool = False):
+        """``_infer`` on a device page [1,H,W,3]: the refined mask stays on the device (an injected ``refine=`` works on the host)."""
+        textlines, mask = self._detect_page(page, None)
+        return textlines, torch.from_numpy(mask).to(page.device) if isinstance(mask, np.ndarray) else mask, None
+
+    @torch.no_grad()
+    def _detect_page(self, page: torch.Tensor, image: Optional[np.ndarray]):
+        """The body of ``_infer`` for the page on the device [1,H,W,3] -> (textlines, refined mask: a device tensor, or the host array
+        of an injected ``refine=``).  ``image``: the same page on the host when the caller has it; the host steps that can be injected
+        fetch it otherwise."""
         from . import hostglue, imgproc, rearrange
 
+        im_h, im_w = int(page.shape[1]), int(page.shape[2])
         S = self.input_size[0]
         strip = rearrange.plan(im_h, im_w, S) is not None    # webtoon strip: det_rearrange_forward (ctd.py:137, generic.py:876-997)
         if strip and self._boxes is None and self._refine is None and torch.device(self.engine.device).type == "cuda":
@@ -242,6 +298,7 @@ class HipComicTextDetector(_EnginePlugin, _DetBase):
             lines, (_, mask_u8) = rearrange.forward_gpu(page[0], net, S, mask_u8=True)
             mask_u8, lines_map = mask_u8[0], None
         elif strip:
+            image = image if image is not None else page[0].cpu().numpy()
             lines_map, mask_f = rearrange.forward(image, self._tiles_forward, S)
             mask_u8 = torch.from_numpy((mask_f.squeeze() * 255).astype(np.uint8)).to(self.engine.device)[None]  # postprocess_mask (:155)
         else:
@@ -261,9 +318,10 @@ class HipComicTextDetector(_EnginePlugin, _DetBase):
         boxes, scores = boxes[keep], scores[keep]
         textlines = [_RefQuadrilateral(pts.astype(int), "", float(s)) for pts, s in zip(boxes, scores)]
         if self._refine is not None:                         # injected resize + refine_mask (e.g. the reference's OpenCV one)
-            return textlines, self._refine(image, mask_u8[0].cpu().numpy(), textlines, im_h, im_w), None
+            image = image if image is not None else page[0].cpu().numpy()
+            return textlines, self._refine(image, mask_u8[0].cpu().numpy(), textlines, im_h, im_w)
         # refine_mask(image, mask, textlines, refine_mode=None) (:177): page and mask are already on the device (csrc/ctd_refine.hip)
-        return textlines, hostglue.refine_mask_gpu(page[0], mask_full, textlines, None).cpu().numpy(), None
+        return textlines, hostglue.refine_mask_gpu(page[0], mask_full, textlines, None)
 
 
     def _tiles_forward(self, squares: np.ndarray):
@@ -280,7 +338,7 @@ class HipComicTextDetector(_EnginePlugin, _DetBase):
         return lines.cpu().numpy(), self.engine.last_mask_f32.cpu().numpy()[:, None]
 
 
-class HipDefaultDetector(_EnginePlugin, _DetBase):
+class HipDefaultDetector(_FilteredDetector, _DetBase):
     """``--detector default`` (DBNet on ResNet-34) on the HIP engine."""
     _KEY = _key = "default_hip"
     _MODEL_MAPPING: Dict = {  # detection/default.py:28-34
@@ -375,6 +433,20 @@ class HipDefaultDetector(_EnginePlugin, _DetBase):
         elif pad_w > 0:
             mask_resized = mask_resized[:, :-pad_w]
         return textlines, np.clip(mask_resized * 255, 0, 255).astype(np.uint8), None
+
+
+    @torch.no_grad()
+    async def _infer_device(self, page: torch.Tensor, detect_size: int, text_threshold: float, box_threshold: float,
+                            unclip_ratio: float, verbose: bool = False):
+        """``_infer`` on a device page [1,H,W,3]: with nothing injected and no webtoon strip, ``dbnet_detect_pages`` on the page where
+        it is, its mask left on the device; everything else through the host form."""
+        from . import rearrange
+
+        injected = self._pre is not None or self._boxes is not None or self._resize2x is not None
+        if injected or page.device.type != "cuda" or rearrange.plan(int(page.shape[1]), int(page.shape[2]), detect_size) is not None:
+            return await super()._infer_device(page, detect_size, text_threshold, box_threshold, unclip_ratio, verbose)
+        tls, masks = dbnet_detect_pages(self.engine, page, detect_size, text_threshold, box_threshold, unclip_ratio, micro_batch=1)
+        return tls[0], masks[0], None
 
 
 class HipDBConvNextDetector(HipDefaultDetector):

@@ -103,12 +103,21 @@ def _field(section, name):
     return getattr(v, "value", v)
 
 
-def stage_keys(config) -> Tuple[str, str, str]:
+def detector_filter_options(config) -> Tuple[bool, bool, bool, bool]:
+    """(invert, gamma_correct, rotate, auto_rotate) of a request — ``detector.det_invert`` / ``det_gamma_correct`` / ``det_rotate`` /
+    ``det_auto_rotate`` (config.py:280-286), false where absent — in the order ``CommonDetector.detect`` takes them."""
+    det = _as_dict(config).get("detector")
+    return tuple(bool(_field(det, opt)) for opt in ("det_invert", "det_gamma_correct", "det_rotate", "det_auto_rotate"))
+
+
+def stage_keys(config, detector_filters: bool = False) -> Tuple[str, str, str]:
     """(detector, ocr, inpainter) a request's ``Config`` names: ``config.detector.detector``, ``config.ocr.ocr``,
     ``config.inpainter.inpainter``, each the reference's default where the field (or its section, or the config) is absent.  Raises
     ValueError, naming the key and the supported set, for a model this worker has no HIP plugin for (craft, paddle, none, mocr, sd,
     original, …) and for a detector filter option that is set (rotate / auto-rotate / invert / gamma-correct run inside the reference's
-    ``CommonDetector.detect``, which the worker does not go through): a request is never served by something else silently."""
+    ``CommonDetector.detect``, which the worker does not go through): a request is never served by something else silently.
+    ``detector_filters``: the worker goes through the plugins' ``detect`` (``DenseStages(params={"detector_filters": True})``), so the
+    four options are served and accepted."""
     cfg = _as_dict(config)
     out = []
     for (section, name), default in zip(SUPPORTED_STAGE_KEYS, DEFAULT_STAGE_KEYS):
@@ -118,7 +127,7 @@ def stage_keys(config) -> Tuple[str, str, str]:
             raise ValueError(f"{section}.{name} = {v!r} is not served by this worker (supported: {', '.join(SUPPORTED_STAGE_KEYS[(section, name)])})")
         out.append(v)
     for opt in DETECTOR_FILTER_OPTIONS:
-        if _field(cfg.get("detector"), opt):
+        if not detector_filters and _field(cfg.get("detector"), opt):
             raise ValueError(f"detector.{opt} is set, and this worker does not apply it (supported: {opt} unset / false; the detector "
                              "runs on the page as it is)")
     return tuple(out)
@@ -138,6 +147,16 @@ class DenseStages:
         self.stages = str(self.params.get("stages") or os.environ.get("MIT_SERVE_STAGES") or "fixed").strip().lower()
         if self.stages not in STAGE_MODES:
             raise ValueError(f"stages must be one of {STAGE_MODES} (params['stages'], --stages or MIT_SERVE_STAGES; got {self.stages!r})")
+        # detector filters (off by default): the detector is called through the plugin's ``detect`` — CommonDetector.detect's rotate /
+        # auto-rotate / invert / gamma-correct options and its border for pages with a side under 400 px — instead of ``infer``
+        flag = self.params.get("detector_filters")
+        if flag is None:
+            flag = os.environ.get("MIT_SERVE_DETECTOR_FILTERS", "").strip().lower() in ("1", "true", "yes", "on")
+        self.detector_filters = bool(flag)
+        if self.detector_filters and self.stages != "config":
+            raise ValueError("detector_filters needs stages='config' (params['detector_filters'], --detector-filters or "
+                             "MIT_SERVE_DETECTOR_FILTERS with params['stages'], --stages or MIT_SERVE_STAGES = config): a worker in "
+                             "'fixed' mode serves no request option of the detector")
         self._plugins: Dict[Tuple[str, str], object] = {}     # config mode: (stage, key) -> the loaded plugin
         # the stages self.det / self.ocr / self.inp are (to be) loaded for: ``_select`` sets them from each request
         self._keys = DEFAULT_STAGE_KEYS if self.stages == "config" else FIXED_STAGE_KEYS
@@ -173,7 +192,7 @@ class DenseStages:
     def _select(self, config) -> Tuple[str, str, str]:
         """The stages that serve a request with this config — ``FIXED_STAGE_KEYS`` in "fixed" mode, ``stage_keys(config)`` in
         "config" mode — noted for ``_load`` (which brings ``self.det`` / ``self.ocr`` / ``self.inp`` to them) and in ``last_stage_keys``."""
-        self._keys = stage_keys(config) if self.stages == "config" else FIXED_STAGE_KEYS
+        self._keys = stage_keys(config, self.detector_filters) if self.stages == "config" else FIXED_STAGE_KEYS
         self.last_stage_keys = self._keys
         return self._keys
 
@@ -255,7 +274,10 @@ class DenseStages:
             up = await self._load_upscaler()
             page = np.ascontiguousarray(up.engine.upscale(torch.from_numpy(page).to(up.engine.device)[None], ratio)[0].cpu().numpy())
         H, W = page.shape[:2]
-        tls, mask_raw, _ = await self.det.infer(page, *self._detector_args(cfg))
+        if self.detector_filters:   # CommonDetector.detect (detection/common.py:12-64): the request's filters, the small-page border
+            tls, mask_raw, _ = await self.det.detect(page, *self._detector_args(cfg), *detector_filter_options(cfg))
+        else:
+            tls, mask_raw, _ = await self.det.infer(page, *self._detector_args(cfg))
         raw_in = cfg.get("mask_raw")        # a request may bring the raw text mask ([H, W] uint8) instead of the detector's: unlike "mask"
         if raw_in is not None:              # it goes through text-line merge + mask refinement
             mask_raw = np.ascontiguousarray(np.asarray(raw_in, dtype=np.uint8))
@@ -365,6 +387,8 @@ class DenseStages:
             return "not HxWx3"
         if self._upscale_options(cfg)[0]:
             return "upscale"
+        if self.detector_filters and (any(detector_filter_options(cfg)) or min(page.shape[:2]) < 400):
+            return "detector filters"      # the coupled engine calls the network on the page as it is
         if self._keys[1] != "48px":     # (config mode only) the coupled engine is written around the 48px model's pooled beam search
             return f"ocr.ocr = {self._keys[1]} is not in the coupled engine"
         # a strip is one at the size its detector tiles at: 1024 for ctd whatever the request says (ctd.py:84), detection_size for DBNet
@@ -846,12 +870,16 @@ def _main(argv=None) -> int:
     w.add_argument("--stages", choices=STAGE_MODES, default=None,
                    help="fixed: ctd + 48px + lama_mpe whatever a request names (default); config: the detector / ocr / inpainter the request's "
                         "Config names, loaded at first use (MIT_SERVE_STAGES sets the default)")
+    w.add_argument("--detector-filters", action="store_true", default=None,
+                   help="with --stages config: call the detector through CommonDetector.detect's filters (det_rotate / det_auto_rotate / "
+                        "det_invert / det_gamma_correct and the border for pages under 400 px); off by default "
+                        "(MIT_SERVE_DETECTOR_FILTERS=1 sets the default)")
     w.add_argument("--lazy", action="store_true", help="load the plugins at the first request instead of before listening (default: before, so "
                                                       "that a worker without its GPU or its checkpoints never reports ready)")
     w.add_argument("--preload", action="store_true", help=argparse.SUPPRESS)   # the default since round 6
     a = ap.parse_args(argv)
     params = {"host": a.host, "port": a.port, "nonce": a.nonce, "model_dir": a.model_dir, "dict_size": a.dict_size, "esrgan_blocks": a.esrgan_blocks,
-              "use_gpu": True, "stages": a.stages}
+              "use_gpu": True, "stages": a.stages, "detector_filters": a.detector_filters}
     worker = make_worker(params)
     loop = asyncio.new_event_loop()
     asyncio.set_event_loop(loop)

@@ -33,8 +33,12 @@ def main() -> int:
     ap.add_argument("--stages", choices=serve.STAGE_MODES, default=None,
                     help="fixed: every worker serves ctd + 48px + lama_mpe (default); config: the detector / ocr / inpainter each request's "
                          "Config names (MIT_SERVE_STAGES sets the default)")
+    ap.add_argument("--detector-filters", action="store_true",
+                    help="with --stages config: the detector runs inside CommonDetector.detect's filters (det_rotate / det_auto_rotate / "
+                         "det_invert / det_gamma_correct, the border for pages under 400 px); off by default")
     a = ap.parse_args()
     wargs = (["--model-dir", a.model_dir] if a.model_dir else []) + (["--preload"] if a.preload else []) + (["--stages", a.stages] if a.stages else [])
+    wargs += ["--detector-filters"] if a.detector_filters else []
     pool = serve.WorkerPool(host=a.host, base_port=a.base_port, nonce=a.nonce, worker_args=wargs)
     signal.signal(signal.SIGTERM, lambda *_: (pool.stop(), sys.exit(0)))
     try:
