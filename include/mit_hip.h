@@ -631,7 +631,9 @@ int mit_aot_blend(float *x_dev, int64_t x_bs, int64_t x_ps, const float *fuse_de
 /* The last gated layer's pair (tail[8], 3 signal + 3 gate channels at pixel stride pre_pixstride) -> signal * sigmoid(gate) * 1.8
  * -> clip(-1, 1) (:274) -> ((x + 1) * 127.5f) truncated to u8 (inpainting_lama_mpe.py:114), composited with the page through
  * mask >= 127 (:57-61,117).  composite == 0 stops after the truncation (``img_inpainted``, every pixel from the network), as in
- * mit_lama_post.  preclip_dev (NULL = off): the value before the clip, [B,H,W,3]. */
+ * mit_lama_post.  preclip_dev (NULL = off): the value before the clip, [B,H,W,3], on every pixel (also where the composite hands
+ * back the page).  A NaN product (NaN or inf * 0 in the pair) has no defined byte in the reference (astype(uint8) of NaN); here
+ * fmaxf(NaN, -1) clips it to -1, so its byte is 0, and preclip_dev receives the NaN. */
 int mit_aot_post(const float *pre_dev, int64_t pre_pixstride, const uint8_t *img_dev, const uint8_t *mask_dev, uint8_t *out_dev,
                  float *preclip_dev, int B, int H, int W, int composite, void *stream);
 
@@ -651,7 +653,9 @@ int mit_grouped_conv3x3(const float *in_dev, int64_t in_bs, int64_t in_ps, int B
 int64_t mit_grouped_conv3x3_lds_bytes(int stride, int dilation, int cpg);
 
 /* Squeeze of Selayer (global_avgpool, networks/models.py:88-106): double partial sums per (sample, fixed 256-pixel chunk, channel)
- * of x [B, hw, C] (batch / pixel strides in floats) into the workspace; C a power of two in [4, 1024]. */
+ * of x [B, hw, C] (batch / pixel strides in floats) into the workspace [B][ceil(hw / 256)][C]; C a power of two in [4, 1024].
+ * The strides must be multiples of 4 and x 16-byte aligned (checked); the caller sees to pixstride >= C and
+ * batch stride >= hw * pixstride (not checked: with smaller strides pixels or planes overlap and the sums count them twice). */
 int64_t mit_se_squeeze_ws(int B, int hw, int C);
 int mit_se_squeeze(const float *x_dev, int64_t bs, int64_t ps, int B, int hw, int C, void *ws_dev, int64_t ws_bytes, void *stream);
 /* Excite, one workgroup per sample: mean = (sum of the chunks in index order) / hw, s = sigmoid(w2 relu(w1 mean + b1) + b2) with
@@ -675,7 +679,9 @@ int mit_mc2_ffd_unpack(const uint8_t *img_dev, int B, int H, int W, int Cin, con
 /* Generator input (utils/utils.py:27-38, ToTensor, manga_colorization_v2.py:58-59): u8 plane [B,h,w] -> fp32 [B,Hp,Wp,4] =
  * (v / 255, 0, 0, 0) with np.pad(.., 'maximum') on the one padded side (rows: column max; columns: row max). */
 int mit_mc2_gen_in(const uint8_t *plane_dev, int B, int h, int w, float *out_dev, int Hp, int Wp, void *stream);
-/* Generator output (manga_colorization_v2.py:61-74): tanh(pre) * 0.5 + 0.5, crop to h x w, * 255 truncated -> u8 RGB [B,h,w,3]. */
+/* Generator output (manga_colorization_v2.py:61-74): tanh(pre) * 0.5 + 0.5, crop to h x w, * 255 truncated -> u8 RGB [B,h,w,3].
+ * Evaluated in double, so the byte is floor((tanh(x) * 0.5 + 0.5) * 255) of the exact value; the reference's float32 evaluation
+ * can differ by one only within float32 rounding of a truncation boundary (it rounds x = 9 up to 255; the exact value is 254.999996). */
 int mit_mc2_post(const float *pre_dev, int64_t pre_pixstride, int B, int Hp, int Wp, uint8_t *out_dev, int h, int w, void *stream);
 
 /* Text-detection stage (dbconvnext): the norms of DBNet on ConvNeXt ---------------------------

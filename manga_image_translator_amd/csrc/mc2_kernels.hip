@@ -277,6 +277,10 @@ __global__ void gen_in_kernel(const uint8_t *__restrict__ plane, int h, int w, f
 }
 
 // ---- (8) exit: tanh, * 0.5 + 0.5, crop, * 255 truncated to u8 RGB ----
+// Evaluated in double: the byte is the floor of the exact value wherever float64 resolves it.  In float32 the sum tanh * 0.5 + 0.5
+// rounds up to 1.0 from tanh = 1 - 2^-24 on (x = 9 gives 255 where the exact value is 254.999996); the reference's own float32 bytes
+// differ from these only within float32 rounding (1.5e-5 of a byte) of a truncation boundary.  Three double tanh per pixel are far
+// below what the 12-byte load and 3-byte store of that pixel cost.
 __global__ void post_kernel(const float *__restrict__ pre, int64_t pre_ps, int Hp, int Wp, uint8_t *__restrict__ out, int h, int w, int B) {
     const int64_t total = (int64_t)B * h * w;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -287,8 +291,8 @@ __global__ void post_kernel(const float *__restrict__ pre, int64_t pre_ps, int H
         const float *p = pre + (((int64_t)b * Hp + y) * Wp + x) * pre_ps;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float v = tanhf(p[c]) * 0.5f + 0.5f;
-            out[3 * i + c] = (uint8_t)fminf(fmaxf(v * 255.f, 0.f), 255.f);
+            const double v = tanh((double)p[c]) * 0.5 + 0.5;
+            out[3 * i + c] = (uint8_t)fmin(fmax(v * 255.0, 0.0), 255.0);
         }
     }
 }
