@@ -1159,6 +1159,55 @@ int mit_rdb_conv3x3_bf16(const MitRdbConv *d, void *stream);
 int mit_cast_f32_bf16(const float *src_dev, int64_t s_bs, int64_t s_ys, int64_t s_xs, uint16_t *dst_dev, int64_t d_bs, int64_t d_ys,
                       int64_t d_xs, int B, int H, int W, int Cn, void *stream);
 
+/* AOT blocks on bf16-resident convolution operands (additive in ABI 26) -------------------------------------------------------------
+ * mit_aot_conv3x3_bf16 — the 3x3, stride 1 convolutions of an AOTBlock (inpainting/inpainting_aot.py:170-193) for the AOT inpainter's
+ * bf16 precision: dilation r in 1 .. MIT_AOT_MAX_RATE with ReflectionPad2d(r), on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.
+ * One launch runs 1 .. MIT_AOT_MAX_GROUPS convolutions ("groups") of the SAME input that differ in rate, weight, bias and the channel
+ * offset of their N-column slice in the output(s): the four dilated branches of a block are one launch that fills the 128-channel
+ * concatenation; fuse and gate are launches of one group.  A workgroup owns MIT_AOT_TILE_H x MIT_AOT_TILE_W output pixels of one
+ * (image, group).  Per 32-channel chunk the chunk's 9 x 32 weight rows go to LDS; the activations take one of two forms, chosen per
+ * group by its rate alone: staged — the reflected region the nine windows touch goes to LDS once and serves all taps (regions of up to
+ * 640 pixels: rates 1 .. 4) — or direct — a lane loads its A fragments (8 channels of one reflected tap pixel, 16 contiguous bytes)
+ * straight from the input (larger rates, whose nine windows do not overlap).  Both forms add the same products in the same order:
+ * the same bits.  Nothing is rounded or split on the way to the MFMA.
+ *
+ *   refl(p, L) = p < 0 ? -p : (p >= L ? 2 (L - 1) - p : p)
+ *   acc[n] = sum_{tap = (ky, kx)} sum_{c < Cin} in[b, refl(y + (ky - 1) r, H), refl(x + (kx - 1) r, W), c] * w[g][(tap * Cin + c) * N + n]
+ *            (fp32, exact products; order: 32-channel chunk, tap, channel — the same for every pixel, batch and grid)
+ *   v      = acc + bias[g][n]                               bias[g] NULL = 0
+ *   v      = act == MIT_ACT_RELU ? max(v, 0) : v
+ *   out_f32[b, y, x, out_c0[g] + n]  = v                    when out_f32  != NULL
+ *   out_bf16[b, y, x, out_c0[g] + n] = bf16(v)              when out_bf16 != NULL: round to nearest even of the fp32 value
+ * A pixel's result depends on nothing but its own window: not on B, the tile it falls in, the other groups or the other images.
+ *
+ * Requirements (anything else is refused before any HIP call): 1 <= groups <= MIT_AOT_MAX_GROUPS; Cin % 32 == 0, 32 <= Cin <= 512;
+ * N 32 or 128; act NONE or RELU; at least one output; every used w[g] non-NULL; 1 <= rate[g] <= MIT_AOT_MAX_RATE and rate[g] < H, W;
+ * B, H, W > 0; input x stride >= Cin; out_c0[g] >= 0 and out_c0[g] + N <= the x stride of every output (a slice stays inside its pixel),
+ * the slices of two groups disjoint; y stride >= x stride, batch stride >= 0; in and every w[g] 16-byte aligned and the input strides
+ * multiples of 8 elements; one image of every tensor spans fewer than 2^31 elements (image bases are 64-bit); ceil(H / MIT_AOT_TILE_H)
+ * and B * groups <= 65535 (grid y / z); out_bf16 must not overlap the input.  All strides are element counts of the tensor's own type. */
+#define MIT_AOT_TILE_H 8
+#define MIT_AOT_TILE_W 32
+#define MIT_AOT_MAX_GROUPS 4
+#define MIT_AOT_MAX_RATE 16
+typedef struct MitAotConv {
+    const uint16_t *in;               /* bf16 bits, NHWC */
+    int64_t in_bs, in_ys, in_xs;
+    int32_t B, H, W, Cin;
+    int32_t N;                        /* columns of every group */
+    int32_t act;
+    int32_t groups;
+    int32_t rate[MIT_AOT_MAX_GROUPS];
+    int32_t out_c0[MIT_AOT_MAX_GROUPS];
+    const uint16_t *w[MIT_AOT_MAX_GROUPS];     /* [9 * Cin][N] bf16 bits, k = (ky * 3 + kx) * Cin + c */
+    const float *bias[MIT_AOT_MAX_GROUPS];     /* [N] */
+    float *out_f32;
+    int64_t of_bs, of_ys, of_xs;
+    uint16_t *out_bf16;
+    int64_t ob_bs, ob_ys, ob_xs;
+} MitAotConv;
+int mit_aot_conv3x3_bf16(const MitAotConv *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

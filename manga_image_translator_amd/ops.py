@@ -20,11 +20,11 @@ import torch
 
 from . import lib as _lib
 from .lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_SIGMOID, ACT_SILU, MIT_MAX_TAPS, PAD_REFLECT,
-                  PAD_ZERO, MitConvGemm, MitConvGemmMember, MitPGemm, MitRdbConv, MitTensorMap)
+                  PAD_ZERO, MitAotConv, MitConvGemm, MitConvGemmMember, MitPGemm, MitRdbConv, MitTensorMap)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "ACT_LEAKY", "ACT_SILU", "ACT_SIGMOID", "ACT_GELU", "ACT_POST_FIRST", "PAD_ZERO", "PAD_REFLECT",
-    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "pack_rdb_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "launch_conv_gemm_group", "conv_gemm_group_plan", "current_stream",
+    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "AotConv3x3", "pack_rdb_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "launch_conv_gemm_group", "conv_gemm_group_plan", "current_stream",
 ]
 
 
@@ -802,6 +802,47 @@ class RdbConv3x3:
 
     def __call__(self, x: torch.Tensor, **kw) -> None:
         _lib.check(_lib.load().mit_rdb_conv3x3_bf16(C.byref(self.desc(x, **kw)), C.c_void_p(current_stream())), "mit_rdb_conv3x3_bf16")
+
+
+class AotConv3x3:
+    """1 .. 4 3x3, stride 1, reflect-padded convolutions ("groups") of ONE bf16 NHWC input that differ in dilation, weight and bias, as
+    one ``mit_aot_conv3x3_bf16`` launch: the four dilated branches of an AOTBlock (group g writes channels ``g * N .. g * N + N`` of
+    the output), or a block's fuse / gate (one group).  The result goes to an fp32 view, a bf16 view, or both; each has
+    ``groups * N`` channels.  weights: [N, Cin, 3, 3] each, N = 32 or 128."""
+
+    def __init__(self, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]], rates: Sequence[int], *,
+                 act: int = ACT_NONE, device="cuda"):
+        if not (1 <= len(weights) <= _lib.MIT_AOT_MAX_GROUPS) or len(biases) != len(weights) or len(rates) != len(weights):
+            raise ValueError(f"AotConv3x3: 1 .. {_lib.MIT_AOT_MAX_GROUPS} groups with one weight, bias and rate each")
+        if len({tuple(w.shape) for w in weights}) != 1:
+            raise ValueError("AotConv3x3: the groups of a launch share one weight shape")
+        self.Cout, self.Cin = int(weights[0].shape[0]), int(weights[0].shape[1])
+        self.rates, self.act = [int(r) for r in rates], act
+        self.w = [pack_rdb_weight(w).to(device) for w in weights]
+        self.bias = [None if b is None else b.detach().to(torch.float32).to(device).contiguous() for b in biases]
+
+    def desc(self, x: torch.Tensor, *, out_bf16: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None) -> MitAotConv:
+        B, H, W, Cx = x.shape
+        _check_nhwc_as(x, torch.bfloat16, (B, H, W, self.Cin), "AotConv3x3 input")
+        G = len(self.w)
+        d = MitAotConv()
+        d.B, d.H, d.W, d.Cin, d.N, d.act, d.groups = B, H, W, self.Cin, self.Cout, self.act, G
+        d.in_bs, d.in_ys, d.in_xs = x.stride(0), x.stride(1), x.stride(2)
+        setattr(d, "in", x.data_ptr())   # ``in`` is a keyword
+        for g in range(G):
+            d.rate[g], d.out_c0[g] = self.rates[g], g * self.Cout
+            d.w[g], d.bias[g] = self.w[g].data_ptr(), _ptr(self.bias[g])
+        for t, dtype, ptr, pre in ((out_f32, torch.float32, "out_f32", "of"), (out_bf16, torch.bfloat16, "out_bf16", "ob")):
+            if t is None:
+                continue
+            _check_nhwc_as(t, dtype, (B, H, W, G * self.Cout), f"AotConv3x3 {ptr}")
+            setattr(d, ptr, t.data_ptr())
+            for ax, nm in enumerate(("bs", "ys", "xs")):
+                setattr(d, f"{pre}_{nm}", t.stride(ax))
+        return d
+
+    def __call__(self, x: torch.Tensor, **kw) -> None:
+        _lib.check(_lib.load().mit_aot_conv3x3_bf16(C.byref(self.desc(x, **kw)), C.c_void_p(current_stream())), "mit_aot_conv3x3_bf16")
 
 
 class ConvTranspose2d:

@@ -909,7 +909,10 @@ class HipAotInpainter(HipLamaMPEInpainter):
     """``--inpainter default``: the AOT generator (inpainting_aot.py:11-33).  Like the reference's AotInpainter it subclasses the
     LaMa-MPE plugin and reuses its ``_infer`` unchanged (input / 127.5 - 1, output (x + 1) * 127.5 truncated: the model is not a
     LamaFourier, inpainting_lama_mpe.py:84,114); only the model and its checkpoint differ.  ``weights``: {"aot": state_dict}.
-    The ``precision`` option is accepted, and the AOT engine runs in fp32 whatever it says: its bf16 form is not built."""
+    ``aot_precision``: "fp32" (default), "bf16" (the blocks on bf16-resident convolution operands, ``AotEngine``), or "config" = what
+    the call's ``config.inpainting_precision`` says, as in the reference (``resolve_lama_precision``: bf16 and fp16 -> bf16); None =
+    ``aot_precision_default()`` (``MIT_AOT_PRECISION``).  The inherited ``precision`` option and ``MIT_LAMA_PRECISION`` are LaMa's:
+    here they are validated and have no effect."""
     _KEY = _key = "default_hip"
     _MODEL_MAPPING: Dict = {  # inpainting/inpainting_aot.py:12-18
         "model": {
@@ -921,17 +924,34 @@ class HipAotInpainter(HipLamaMPEInpainter):
     CKPT = "inpainting.ckpt"
     MB = 4   # pages per micro-batch of the engine: 16 full 2048 x 1456 pages run as four of them within one workspace
 
+    def __init__(self, *args, aot_precision: Optional[str] = None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.aot_precision = aot_precision_default() if aot_precision is None else aot_precision
+        if self.aot_precision not in LAMA_PRECISIONS:    # a bad value raises here, not at the first page
+            raise ValueError(f"AOT precision must be one of {LAMA_PRECISIONS} (got {self.aot_precision!r})")
+
     def precision_for(self, config=None) -> str:
-        resolve_lama_precision(self.precision, config)   # the option is validated like the parent's
-        return "fp32"
+        """The engine precision of a call with this ``config``: what ``aot_precision`` resolves to, "fp32" or "bf16"."""
+        resolve_lama_precision(self.precision, config)   # the inherited option is validated like the parent's
+        return resolve_lama_precision(self.aot_precision, config)
 
     async def _load(self, device: str):
         from . import aot
 
         dev = _gpu_device(device)
         w = self._weights or _load_aot_checkpoint(self)
-        self.engine = aot.AotEngine(w["aot"], device=dev, mb=self.MB)
+        # a plugin fixed to bf16 packs the bf16 weights at load; "config" decides per call, so they are packed at the first bf16 call
+        self.engine = aot.AotEngine(w["aot"], device=dev, mb=self.MB, precision="bf16" if self.aot_precision == "bf16" else "fp32")
         self.device = device
+
+
+def aot_precision_default() -> str:
+    """The ``aot_precision`` of an AOT plugin created without one (``register()``, ``serve.py``): ``MIT_AOT_PRECISION`` in the
+    environment ("fp32" | "bf16" | "config"), else "fp32"."""
+    v = os.environ.get("MIT_AOT_PRECISION", "").strip().lower() or "fp32"
+    if v not in LAMA_PRECISIONS:
+        raise ValueError(f"MIT_AOT_PRECISION must be one of {LAMA_PRECISIONS} (got {v!r})")
+    return v
 
 
 ESRGAN_PRECISIONS = ("fp32", "bf16")
