@@ -3,17 +3,13 @@
 // fuse / gate convolutions 128 -> 128 (rate 1), on bf16-RESIDENT operands, v_mfma_f32_32x32x16_bf16, fp32 accumulation and epilogue
 // (mit_hip.h has the arithmetic).
 //
-// Workgroup = 256 lanes = 4 waves, one tile of TH x TW = 8 x 32 output pixels of one (image, group); wave w owns rows 2w, 2w + 1 (two
-// 32-pixel MFMA row blocks) and all N columns: 2 x N / 32 accumulators of 16 registers.  The K loop walks chunks of 32 input channels:
-//   W  image [9 taps x 4 k-groups][N] cells of 16 bytes = 8 consecutive k of one output column (the B fragment of a lane), a k-group's
-//      row of N cells followed by 16 bytes of pad: the layout, the in-register 8 x 8 transposition and the bank argument of
-//      rdb_bf16.hip.  36 * (N * 16 + 16) bytes: 19008 at N = 32, 74304 at N = 128.  The next chunk's weight rows are requested before
-//      the MFMAs of the current one and written to LDS after them.
+// The tile (256 lanes, 8 x 32 output pixels of one (image, group), chunks of 32 input channels), the W image, the MFMA step and the
+// epilogue's stores are conv3x3_bf16_tile.h's.  The W image is 36 * (N * 16 + 16) bytes: 19008 at N = 32, 74304 at N = 128; the next
+// chunk's weight rows are requested before the MFMAs of the current one and written to LDS after them.  This kernel's A operand:
 //   A  one of two forms, chosen per workgroup from its group's rate alone (so a launch of four groups mixes them):
 //      staged   the region the nine windows of the tile touch — columns tx0 - rate .. tx0 + 31 + rate of the rows ty0 - rate ..
-//               ty0 + 7 + rate (rate <= 8) or of three 8-row bands (larger rates) — goes to LDS once per chunk, reflected, 80 bytes a
-//               pixel (64 of data + 16 of pad: the 16 lanes of a ds_read_b128 group fall on 16 different 16-byte slots, as in
-//               rdb_bf16.hip), and serves all nine taps.  The global loads are whole 64-byte pixel chunks by four neighbouring lanes.
+//               ty0 + 7 + rate (rate <= 8) or of three 8-row bands (larger rates) — goes to LDS once per chunk, reflected, 80 padded
+//               bytes a pixel, and serves all nine taps.  The global loads are whole 64-byte pixel chunks by four neighbouring lanes.
 //               The A image holds AR * 64 = 640 pixels (51200 bytes): rates 1 .. 4 (a 16 x 40 region at rate 4).  The regions of
 //               rates 8 and 16 (24 x 48 and 24 x 64 pixels: 92 and 123 KB) fit the LDS only at one workgroup a CU and were measured
 //               slower there than the direct form.
@@ -25,48 +21,28 @@
 //               current one (a ring of three).
 // 70208 bytes of static LDS at N = 32 (two workgroups a CU), 125504 at N = 128 (one).
 // Accumulation order of a pixel: chunk, tap, channel — fixed, whatever the form, the batch, the group count or the tile.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <type_traits>
-#include "../../include/mit_hip.h"
-#include "bf16_split.h"
-#include "common.h"
+#include "conv3x3_bf16_tile.h"
 
 namespace {
 
-using mitcg::bf16x8;
-using mitcg::u32x4;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace conv3x3;
 
-constexpr int TH = MIT_AOT_TILE_H, TW = MIT_AOT_TILE_W;
-constexpr int CK = 32;                                     // input channels a chunk
-constexpr int THREADS = 256;
-constexpr int KG = 9 * CK / 8;                             // k-groups (8 rows) of a chunk's weights: 36
 constexpr int PF = 3;                                      // taps the A fragments are requested ahead (direct form)
 constexpr int AR = 10;                                     // rounds of 256 16-byte units the staged form's A image holds: 640 region pixels
-constexpr int PIX_B = 80;                                  // LDS bytes a region pixel (staged form): 64 of data + 16 of pad, as in rdb_bf16.hip
-static_assert(TW == 32 && TH == 8, "a wave owns two 32-pixel rows of the tile");
 static_assert(9 % PF == 0, "a tap keeps its ring slot from chunk to chunk");
-
-__device__ __forceinline__ unsigned short bf16_bits(float v) {   // round to nearest even (v_cvt_pk_bf16_f32)
-    return (unsigned short)(mitcg::pack_bf16(v, 0.0f) & 0xffffu);
-}
 
 // ReflectionPad2d: p in [-rate, L - 1 + rate] with rate <= L - 1
 __device__ __forceinline__ int reflect(int p, int L) { return p < 0 ? -p : (p >= L ? 2 * (L - 1) - p : p); }
 
-// VEC: the epilogue goes through LDS so that a lane owns four consecutive channels of a pixel (16-byte stores of the fp32 output, 8-byte
-// stores of the bf16 output); the host takes it when every output is aligned for that.  Otherwise a lane keeps the column the
-// accumulator layout gives it (4- and 2-byte stores).  Same expression sequence: the same bits.
+// VEC: the wide form of the epilogue (store_tile).
 template <int N, bool VEC>
 __global__ __launch_bounds__(THREADS, N == 32 ? 2 : 1) void aot_conv3x3_kernel(const MitAotConv d) {
-    constexpr int NB = N / 32, NG = N / 8, W_ROW = N * 16 + 16;                          // bytes of a k-group's row of cells, padded
-    constexpr int SLOTS = (KG + 7) / 8 * 8 * NG, W_ROUNDS = (SLOTS + THREADS - 1) / THREADS;   // task slots: 8 k-groups x NG column groups a block
-    constexpr int A_BYTES = AR * (THREADS / 4) * PIX_B;                                  // room for AR * 64 region pixels
-    constexpr int W_BYTES = KG * W_ROW, E_BYTES = 4 * 32 * N * 4;
-    __shared__ u32x4 lds[(A_BYTES + W_BYTES > E_BYTES ? A_BYTES + W_BYTES : E_BYTES) / 16];
+    constexpr int NB = N / 32;
+    constexpr int A_BYTES = AR * (THREADS / 4) * PIX_B;   // room for AR * 64 region pixels
+    constexpr int K_BYTES = A_BYTES + WImage<N>::BYTES, E_BYTES = store_tile_bytes<N>();
+    __shared__ u32x4 lds[(K_BYTES > E_BYTES ? K_BYTES : E_BYTES) / 16];
     unsigned char *ldsA = reinterpret_cast<unsigned char *>(lds);
-    unsigned char *ldsW = ldsA + A_BYTES;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -118,52 +94,10 @@ __global__ __launch_bounds__(THREADS, N == 32 ? 2 : 1) void aot_conv3x3_kernel(c
 #pragma unroll
         for (int t = 0; t < 3; ++t) col_off[t] = (t * rate + r) * PIX_B + h * 16;
     }
-    // W image: a task = (k-group, column group): rows (tap * Cin + c8 .. + 7), columns ng * 8 .. + 7; k-group fastest over the lanes
-    int w_off[W_ROUNDS], w_cell[W_ROUNDS];
-#pragma unroll
-    for (int i = 0; i < W_ROUNDS; ++i) {
-        const int task = tid + i * THREADS;
-        const int kg = (task & 7) + 8 * (task / (8 * NG)), ng = (task >> 3) % NG;
-        const int tap = kg >> 2, c8 = (kg & 3) * 8;
-        w_off[i] = kg < KG ? (tap * Cin + c8) * N + ng * 8 : -1;
-        w_cell[i] = kg * W_ROW + ng * 128;
-    }
-
-    u32x4 w_reg[W_ROUNDS][8];
-    auto fetch_w = [&](int c0) {
-#pragma unroll
-        for (int i = 0; i < W_ROUNDS; ++i)
-            if (w_off[i] >= 0) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) w_reg[i][j] = *reinterpret_cast<const u32x4 *>(wt + w_off[i] + (c0 + j) * N);
-            }
-    };
-    auto stage_w = [&]() {
-#pragma unroll
-        for (int i = 0; i < W_ROUNDS; ++i)
-            if (w_off[i] >= 0) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {   // column c of the 8 x 8 block: rows 2q, 2q + 1 share dword q of the cell
-                    u32x4 cell;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const unsigned lo = w_reg[i][2 * q][c >> 1], hi = w_reg[i][2 * q + 1][c >> 1];
-                        cell[q] = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-                    }
-                    *reinterpret_cast<u32x4 *>(ldsW + w_cell[i] + c * 16) = cell;
-                }
-            }
-    };
+    WImage<N> wi(ldsA + A_BYTES, Cin);
 
     f32x16 acc[2][NB];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][nb][e] = 0.0f;
-
-    const unsigned char *w_base = ldsW + h * W_ROW + r * 16;   // this lane's B fragment at tap 0, k-step 0
+    clear(acc);
 
     // The K loop, once per form (two bodies, so that neither carries the other's registers); st: std::true_type = staged.
     auto k_loop = [&](auto st) {
@@ -192,7 +126,7 @@ __global__ __launch_bounds__(THREADS, N == 32 ? 2 : 1) void aot_conv3x3_kernel(c
                     ring[ST ? 0 : slot][m][s] = *reinterpret_cast<const bf16x8 *>(in + row_off[m][dy] + col_off[dx] + c0 + s * 16);
         };
 
-        fetch_w(0);
+        wi.fetch(wt, 0);
         if (ST) {
             fetch_region(0);
         } else {
@@ -201,11 +135,11 @@ __global__ __launch_bounds__(THREADS, N == 32 ? 2 : 1) void aot_conv3x3_kernel(c
         }
         for (int c0 = 0; c0 < Cin; c0 += CK) {
             __syncthreads();   // the previous chunk's fragments have been read
-            stage_w();
+            wi.stage();
             if (ST) stage_region();
             __syncthreads();
             const bool more = c0 + CK < Cin;
-            if (more) fetch_w(c0 + CK);
+            if (more) wi.fetch(wt, c0 + CK);
             if (ST && more) fetch_region(c0 + CK);
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
@@ -228,17 +162,7 @@ __global__ __launch_bounds__(THREADS, N == 32 ? 2 : 1) void aot_conv3x3_kernel(c
                         fetch_a(tap % PF, c0 + CK, tap + PF - 9);
                 }
 #pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    bf16x8 fb[NB];
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb)
-                        fb[nb] = *reinterpret_cast<const bf16x8 *>(w_base + (tap * 4 + 2 * s) * W_ROW + nb * 512);
-#pragma unroll
-                    for (int m = 0; m < 2; ++m)
-#pragma unroll
-                        for (int nb = 0; nb < NB; ++nb)
-                            acc[m][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m][s], fb[nb], acc[m][nb], 0, 0, 0);
-                }
+                for (int s = 0; s < 2; ++s) mfma_step(acc, wi, tap, s, fa[0][s], fa[1][s]);
             }
         }
     };
@@ -247,95 +171,44 @@ __global__ __launch_bounds__(THREADS, N == 32 ? 2 : 1) void aot_conv3x3_kernel(c
     else
         k_loop(std::false_type{});
 
-    const bool relu = d.act == MIT_ACT_RELU;
+    const int act = d.act;
     const int oc0 = d.out_c0[g];
     const float *bias = d.bias[g];
     float *of = d.out_f32 ? d.out_f32 + b * d.of_bs + oc0 : nullptr;
     uint16_t *ob = d.out_bf16 ? d.out_bf16 + b * d.ob_bs + oc0 : nullptr;
-    if (VEC) {
-        // one row of the wave's two at a time: 32 pixels x N fp32 of LDS a wave (pixel rows of N floats: the ds_read_b128 lane groups
-        // fall on 16 different slots without padding), then lane = (pixel, four channels)
-        constexpr int Q = N / 4, PX_IT = 64 / Q;
-        float *tile = reinterpret_cast<float *>(lds) + wave * (32 * N);
-        const int q = lane % Q, pl = lane / Q;
-        float bi[4];
+    auto chan = [=](int n) { return bias ? bias[n] : 0.0f; };
+    // bias, then ReLU: in this order in both forms
+    auto fin = [=](auto &v, const auto &k, int, int, int) {
+        if constexpr (VEC) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) bi[j] = bias ? bias[4 * q + j] : 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            __syncthreads();   // the W image (m = 0) or the previous row (m = 1) has been read
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) tile[((e & 3) + 8 * (e >> 2) + 4 * h) * N + nb * 32 + r] = acc[m][nb][e];
-            __syncthreads();
-            const int y = ty0 + wave * 2 + m;
-            if (y >= H) continue;
-#pragma unroll
-            for (int it = 0; it < 32 / PX_IT; ++it) {
-                const int xi = it * PX_IT + pl, x = tx0 + xi;
-                if (x >= W) continue;
-                const f32x4 a4 = *reinterpret_cast<const f32x4 *>(tile + xi * N + 4 * q);
-                float v[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[j] = v[j] + bi[j];
-                    if (relu) v[j] = fmaxf(v[j], 0.0f);
-                }
-                if (of) *reinterpret_cast<f32x4 *>(of + (int)(y * d.of_ys + x * d.of_xs) + 4 * q) = f32x4{v[0], v[1], v[2], v[3]};
-                if (ob)
-                    *reinterpret_cast<mitcg::u32x2 *>(ob + (int)(y * d.ob_ys + x * d.ob_xs) + 4 * q) =
-                        mitcg::u32x2{mitcg::pack_bf16(v[0], v[1]), mitcg::pack_bf16(v[2], v[3])};
+            for (int j = 0; j < 4; ++j) {
+                v[j] = v[j] + k[j];
+                if (act == MIT_ACT_RELU) v[j] = fmaxf(v[j], 0.0f);
             }
+        } else {
+            v = v + k;
+            if (act == MIT_ACT_RELU) v = fmaxf(v, 0.0f);
         }
-        return;
-    }
-    // the lane holds column n = nb * 32 + r of the pixels x = tx0 + (e & 3) + 8 (e >> 2) + 4 h of its two rows
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int n = nb * 32 + r;
-        const float bi = bias ? bias[n] : 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int y = ty0 + wave * 2 + m;
-            if (y >= H) continue;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int x = tx0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (x >= W) continue;
-                float v = acc[m][nb][e] + bi;
-                if (relu) v = fmaxf(v, 0.0f);
-                if (of) of[(int)(y * d.of_ys + x * d.of_xs) + n] = v;
-                if (ob) ob[(int)(y * d.ob_ys + x * d.ob_xs) + n] = bf16_bits(v);
-            }
-        }
-    }
+    };
+    store_tile<N, VEC>(acc, lds, TileOut{H, W, ty0, tx0, of, d.of_ys, d.of_xs, ob, d.ob_ys, d.ob_xs}, chan, fin);
 }
 
-// [lo, hi) element extent of a strided NHWC tensor with C channels addressed
-int64_t extent(int B, int H, int W, int64_t C, int64_t bs, int64_t ys, int64_t xs) {
-    return (int64_t)(B - 1) * bs + (int64_t)(H - 1) * ys + (int64_t)(W - 1) * xs + C;
-}
-
-// strides of one tensor whose pixels hold C addressed channels: x stride >= C, y stride >= x stride, batch stride >= 0, one image below
-// 2^31 elements
-const char *bad_strides(int H, int W, int64_t C, int64_t bs, int64_t ys, int64_t xs) {
-    if (xs < C) return "x stride smaller than the channels addressed";
-    if (ys < xs || bs < 0) return "y stride smaller than the x stride, or a negative batch stride";
-    if (ys > INT32_MAX || extent(1, H, W, xs, 0, ys, xs) > INT32_MAX) return "one image spans 2^31 elements or more (32-bit offsets inside an image)";
-    return nullptr;
+// a tensor whose pixels hold C addressed channels; its span is counted in whole pixels
+const char *bad_strides(const MitAotConv &d, int64_t C, int64_t bs, int64_t ys, int64_t xs) {
+    return conv3x3::bad_strides(d.H, d.W, C, xs, bs, ys, xs, "x stride smaller than the channels addressed");
 }
 
 }  // namespace
 
 extern "C" int mit_aot_conv3x3_bf16(const MitAotConv *dp, void *stream) {
+    const char *fn = "mit_aot_conv3x3_bf16";
     if (!dp) return mit_set_error("mit_aot_conv3x3_bf16: null descriptor");
     const MitAotConv &d = *dp;
     if (!d.in) return mit_set_error("mit_aot_conv3x3_bf16: null pointer (in)");
-    if (!d.out_f32 && !d.out_bf16) return mit_set_error("mit_aot_conv3x3_bf16: null pointer (no output: out_f32 and out_bf16 are both NULL)");
+    if (check_outputs(fn, d)) return 1;
     if (d.groups < 1 || d.groups > MIT_AOT_MAX_GROUPS)
         return mit_set_error("mit_aot_conv3x3_bf16: groups must be in [1, %d] (got %d)", MIT_AOT_MAX_GROUPS, d.groups);
-    if (d.B <= 0 || d.H <= 0 || d.W <= 0) return mit_set_error("mit_aot_conv3x3_bf16: sizes must be positive (B %d, H %d, W %d)", d.B, d.H, d.W);
+    if (check_sizes(fn, d)) return 1;
     if (d.Cin % CK != 0 || d.Cin < 32 || d.Cin > 512)
         return mit_set_error("mit_aot_conv3x3_bf16: Cin must be a multiple of 32 in [32, 512] (got %d)", d.Cin);
     if (d.N != 32 && d.N != 128) return mit_set_error("mit_aot_conv3x3_bf16: N must be 32 or 128 (got %d)", d.N);
@@ -355,27 +228,16 @@ extern "C" int mit_aot_conv3x3_bf16(const MitAotConv *dp, void *stream) {
         if (top < (int64_t)d.out_c0[g] + d.N) top = (int64_t)d.out_c0[g] + d.N;
     }
     const char *why;
-    if ((why = bad_strides(d.H, d.W, d.Cin, d.in_bs, d.in_ys, d.in_xs))) return mit_set_error("mit_aot_conv3x3_bf16: input strides: %s", why);
-    if (d.out_f32 && (why = bad_strides(d.H, d.W, top, d.of_bs, d.of_ys, d.of_xs)))
+    if ((why = bad_strides(d, d.Cin, d.in_bs, d.in_ys, d.in_xs))) return mit_set_error("mit_aot_conv3x3_bf16: input strides: %s", why);
+    if (d.out_f32 && (why = bad_strides(d, top, d.of_bs, d.of_ys, d.of_xs)))
         return mit_set_error("mit_aot_conv3x3_bf16: out_f32 slice overruns its buffer or bad strides: %s", why);
-    if (d.out_bf16 && (why = bad_strides(d.H, d.W, top, d.ob_bs, d.ob_ys, d.ob_xs)))
+    if (d.out_bf16 && (why = bad_strides(d, top, d.ob_bs, d.ob_ys, d.ob_xs)))
         return mit_set_error("mit_aot_conv3x3_bf16: out_bf16 slice overruns its buffer or bad strides: %s", why);
-    if (reinterpret_cast<uintptr_t>(d.in) % 16 || d.in_xs % 8 || d.in_ys % 8 || d.in_bs % 8)
-        return mit_set_error("mit_aot_conv3x3_bf16: in must be 16-byte aligned and the input strides multiples of 8 elements");
-    if (mit_div_up(d.H, TH) > 65535 || (int64_t)d.B * d.groups > 65535)
-        return mit_set_error("mit_aot_conv3x3_bf16: at most 65535 tile rows and 65535 (image, group) pairs a launch (grid y / z)");
-    if (d.out_bf16) {
-        // byte addresses as integers
-        const int64_t din = (int64_t)(reinterpret_cast<intptr_t>(d.out_bf16) - reinterpret_cast<intptr_t>(d.in)) / 2;
-        if (din < extent(d.B, d.H, d.W, d.Cin, d.in_bs, d.in_ys, d.in_xs) && -din < extent(d.B, d.H, d.W, top, d.ob_bs, d.ob_ys, d.ob_xs))
-            return mit_set_error("mit_aot_conv3x3_bf16: out_bf16 overlaps the input");
-    }
+    if (check_alignment_and_grid(fn, d, nullptr, (int64_t)d.B * d.groups, "(image, group) pairs")) return 1;
+    if (d.out_bf16 && extents_overlap(d, out_bf16_offset(d), top)) return mit_set_error("mit_aot_conv3x3_bf16: out_bf16 overlaps the input");
     const dim3 grid((unsigned)mit_div_up(d.W, TW), (unsigned)mit_div_up(d.H, TH), (unsigned)(d.B * d.groups));
     const double px = (double)d.B * d.H * d.W;
-    // the wide epilogue: the fp32 output on 16 bytes, the bf16 output on 8, every stride and channel offset a multiple of four elements
-    auto wide = [&](const void *p, int64_t bs, int64_t ys, int64_t xs, int align) {
-        return !p || (reinterpret_cast<uintptr_t>(p) % align == 0 && bs % 4 == 0 && ys % 4 == 0 && xs % 4 == 0);
-    };
+    // the wide epilogue: every channel offset a multiple of four elements as well
     bool vec = wide(d.out_f32, d.of_bs, d.of_ys, d.of_xs, 16) && wide(d.out_bf16, d.ob_bs, d.ob_ys, d.ob_xs, 8);
     for (int g = 0; g < d.groups; ++g) vec = vec && d.out_c0[g] % 4 == 0;
     const auto kern = d.N == 128 ? (vec ? aot_conv3x3_kernel<128, true> : aot_conv3x3_kernel<128, false>)

@@ -6,57 +6,36 @@
 // re-reads its fp32 activations from cache and re-rounds them; here a dense block's activations live in HBM as bf16 (every consumer of
 // x, x1 .. x4 is a convolution that would round them anyway), and a workgroup stages each input element to LDS ONCE per launch.
 //
-// Workgroup = 256 lanes = 4 waves, one tile of TH x TW = 8 x 32 output pixels; wave w owns rows 2w, 2w + 1 (two 32-pixel MFMA row
-// blocks) and all N columns: 2 x N / 32 accumulators of 16 registers.  The K loop walks chunks of 32 input channels:
-//   A image  [10 x 34 halo pixels][32 ch] bf16, 80 bytes a pixel (64 of data + 16 of pad: the 16 lanes of a ds_read_b128 group then
-//            fall on 16 different 16-byte bank slots — 5 r mod 16 is a bijection over each group's rows);
-//   W image  [9 taps x 4 k-groups][N] cells of 16 bytes = 8 consecutive k of one output column, which is the B fragment of a lane; a
-//            k-group's row of N cells is followed by 16 bytes of pad.  The packed weight is [9 * Cin][N] row-major, so a lane takes
-//            8 rows x 8 columns (eight 16-byte loads), transposes them in registers and writes eight cells.  Eight consecutive lanes
-//            (one ds_write_b128 group) hold eight k-groups of the same columns: with the pad their cells fall on eight different
-//            16-byte slots (the same k-group in neighbouring lanes would put all eight on one slot), while a load instruction of
-//            the wave still reads whole 128-byte weight rows.
+// The tile (256 lanes, 8 x 32 output pixels, chunks of 32 input channels), the W image, the MFMA step and the epilogue's stores are
+// conv3x3_bf16_tile.h's.  This kernel's A operand is the zero-padded halo of the tile:
+//   A image  [10 x 34 halo pixels][32 ch] bf16, 80 bytes a pixel.
 // 27200 + 36 * (N * 16 + 16) bytes = 64640 at N = 64: static LDS, two workgroups a CU.  The next chunk's global loads are issued before the
 // MFMAs of the current one and written to LDS after them, so the loads travel under 18 k-steps of 2 x N / 32 MFMAs.
 // Accumulation order of a pixel: chunk, tap, channel — fixed, whatever the batch or the tile.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/mit_hip.h"
-#include "bf16_split.h"
-#include "common.h"
+#include "conv3x3_bf16_tile.h"
 
 namespace {
 
-using mitcg::bf16x8;
-using mitcg::u32x4;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace conv3x3;
 
-constexpr int TH = MIT_RDB_TILE_H, TW = MIT_RDB_TILE_W;
 constexpr int HH = TH + 2, HW = TW + 2, HALO = HH * HW;   // 10 x 34 = 340 halo pixels
-constexpr int CK = 32;                                     // input channels a chunk
-constexpr int PIX_B = 80;                                  // LDS bytes a halo pixel
 constexpr int A_BYTES = HALO * PIX_B;                      // 27200
-constexpr int THREADS = 256;
 constexpr int A_UNITS = HALO * (CK / 8);                   // 16-byte units of the A image: 1360
 constexpr int A_ROUNDS = (A_UNITS + THREADS - 1) / THREADS;
-constexpr int KG = 9 * CK / 8;                             // k-groups (8 rows) of a chunk's weights: 36
-static_assert(TW == 32 && TH == 8, "a wave owns two 32-pixel rows of the tile");
 static_assert(A_BYTES % 16 == 0, "the W image starts on a 16-byte boundary");
+static_assert(A_BYTES + WImage<32>::BYTES >= store_tile_bytes<32>() && A_BYTES + WImage<64>::BYTES >= store_tile_bytes<64>(),
+              "the epilogue's tile fits the K loop's images");
 
-__device__ __forceinline__ unsigned short bf16_bits(float v) {   // round to nearest even (v_cvt_pk_bf16_f32)
-    return (unsigned short)(mitcg::pack_bf16(v, 0.0f) & 0xffffu);
-}
+struct ChanConst {
+    float sc, bi;
+};
 
-// VEC: the epilogue goes through LDS so that a lane owns four consecutive channels of a pixel (16-byte loads and stores of the fp32
-// operands, 8-byte stores of the bf16 output); the host takes it when every epilogue tensor is aligned for that.  Otherwise a lane
-// keeps the column the accumulator layout gives it (4- and 2-byte accesses).  Same expression sequence: the same bits.
+// VEC: the wide form of the epilogue (store_tile), which also reads post and post2 with 16-byte loads.
 template <int N, bool VEC>
 __global__ __launch_bounds__(THREADS, 2) void rdb_conv3x3_kernel(const MitRdbConv d) {
-    constexpr int NB = N / 32, NG = N / 8, W_ROW = N * 16 + 16;                          // bytes of a k-group's row of cells, padded
-    constexpr int SLOTS = (KG + 7) / 8 * 8 * NG, W_ROUNDS = (SLOTS + THREADS - 1) / THREADS;   // task slots: 8 k-groups x NG column groups a block
-    __shared__ u32x4 lds[(A_BYTES + KG * W_ROW) / 16];
+    constexpr int NB = N / 32;
+    __shared__ u32x4 lds[(A_BYTES + WImage<N>::BYTES) / 16];
     unsigned char *ldsA = reinterpret_cast<unsigned char *>(lds);
-    unsigned char *ldsW = ldsA + A_BYTES;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -64,7 +43,6 @@ __global__ __launch_bounds__(THREADS, 2) void rdb_conv3x3_kernel(const MitRdbCon
     const int64_t b = blockIdx.z;
     const int H = d.H, W = d.W, Cin = d.Cin;
     const uint16_t *in = d.in + b * d.in_bs;
-    const uint16_t *wt = d.w;
 
     // what this lane stages of every chunk.  A image: unit u = pixel * 4 + part; offset -1 = outside the image (zeros), -2 = no unit
     int a_off[A_ROUNDS];
@@ -77,30 +55,16 @@ __global__ __launch_bounds__(THREADS, 2) void rdb_conv3x3_kernel(const MitRdbCon
         const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
         a_off[i] = u >= A_UNITS ? -2 : (inside ? (int)(gy * d.in_ys + gx * d.in_xs) + part * 8 : -1);
     }
-    // W image: a task = (k-group, column group): rows (tap * Cin + c8 .. + 7), columns ng * 8 .. + 7; k-group fastest over the lanes
-    int w_off[W_ROUNDS], w_cell[W_ROUNDS];
-#pragma unroll
-    for (int i = 0; i < W_ROUNDS; ++i) {
-        const int task = tid + i * THREADS;
-        const int kg = (task & 7) + 8 * (task / (8 * NG)), ng = (task >> 3) % NG;
-        const int tap = kg >> 2, c8 = (kg & 3) * 8;
-        w_off[i] = kg < KG ? (tap * Cin + c8) * N + ng * 8 : -1;
-        w_cell[i] = kg * W_ROW + ng * 128;
-    }
+    WImage<N> wi(ldsA + A_BYTES, Cin);
 
-    u32x4 a_reg[A_ROUNDS], w_reg[W_ROUNDS][8];
+    u32x4 a_reg[A_ROUNDS];
     auto fetch = [&](int c0) {
 #pragma unroll
         for (int i = 0; i < A_ROUNDS; ++i) {
             a_reg[i] = u32x4{0u, 0u, 0u, 0u};
             if (a_off[i] >= 0) a_reg[i] = *reinterpret_cast<const u32x4 *>(in + a_off[i] + c0);
         }
-#pragma unroll
-        for (int i = 0; i < W_ROUNDS; ++i)
-            if (w_off[i] >= 0) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) w_reg[i][j] = *reinterpret_cast<const u32x4 *>(wt + w_off[i] + (c0 + j) * N);
-            }
+        wi.fetch(d.w, c0);
     };
     auto stage = [&]() {
 #pragma unroll
@@ -108,33 +72,13 @@ __global__ __launch_bounds__(THREADS, 2) void rdb_conv3x3_kernel(const MitRdbCon
             const int u = tid + i * THREADS;
             if (a_off[i] != -2) *reinterpret_cast<u32x4 *>(ldsA + (u >> 2) * PIX_B + (u & 3) * 16) = a_reg[i];
         }
-#pragma unroll
-        for (int i = 0; i < W_ROUNDS; ++i)
-            if (w_off[i] >= 0) {
-#pragma unroll
-                for (int c = 0; c < 8; ++c) {   // column c of the 8 x 8 block: rows 2q, 2q + 1 share dword q of the cell
-                    u32x4 cell;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const unsigned lo = w_reg[i][2 * q][c >> 1], hi = w_reg[i][2 * q + 1][c >> 1];
-                        cell[q] = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-                    }
-                    *reinterpret_cast<u32x4 *>(ldsW + w_cell[i] + c * 16) = cell;
-                }
-            }
+        wi.stage();
     };
 
     f32x16 acc[2][NB];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][nb][e] = 0.0f;
+    clear(acc);
 
-    // this lane's fragment addresses at tap (0, 0), k-step 0
-    const unsigned char *a_base = ldsA + ((wave * 2) * HW + r) * PIX_B + h * 16;
-    const unsigned char *w_base = ldsW + h * W_ROW + r * 16;
+    const unsigned char *a_base = ldsA + ((wave * 2) * HW + r) * PIX_B + h * 16;   // this lane's A fragment at tap (0, 0), k-step 0
 
     fetch(0);
     for (int c0 = 0; c0 < Cin; c0 += CK) {
@@ -147,97 +91,49 @@ __global__ __launch_bounds__(THREADS, 2) void rdb_conv3x3_kernel(const MitRdbCon
             const int dy = tap / 3, dx = tap - dy * 3;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                bf16x8 fa[2], fb[NB];
+                bf16x8 fa[2];
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
                     fa[m] = *reinterpret_cast<const bf16x8 *>(a_base + ((m + dy) * HW + dx) * PIX_B + s * 32);
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb)
-                    fb[nb] = *reinterpret_cast<const bf16x8 *>(w_base + (tap * 4 + 2 * s) * W_ROW + nb * 512);
-#pragma unroll
-                for (int m = 0; m < 2; ++m)
-#pragma unroll
-                    for (int nb = 0; nb < NB; ++nb) acc[m][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[m], fb[nb], acc[m][nb], 0, 0, 0);
+                mfma_step(acc, wi, tap, s, fa[0], fa[1]);
             }
         }
     }
 
-    const bool leaky = d.act == MIT_ACT_LEAKY;
+    // the epilogue's operands as locals, which the functors below copy (store_tile says why)
+    const int act = d.act;
+    const float alpha = d.act_alpha, s2 = d.s2;
+    const float *scale = d.scale, *bias = d.bias;
     const float *post = d.post ? d.post + b * d.post_bs : nullptr;
     const float *post2 = d.post2 ? d.post2 + b * d.post2_bs : nullptr;
+    const int64_t p_ys = d.post_ys, p_xs = d.post_xs, p2_ys = d.post2_ys, p2_xs = d.post2_xs;
     float *of = d.out_f32 ? d.out_f32 + b * d.of_bs : nullptr;
     uint16_t *ob = d.out_bf16 ? d.out_bf16 + b * d.ob_bs : nullptr;
-    if (VEC) {
-        // one row of the wave's two at a time: 32 pixels x N fp32 of LDS a wave (pixel rows of N floats: the ds_read_b128 lane groups
-        // fall on 16 different slots without padding), then lane = (pixel, four channels)
-        constexpr int Q = N / 4, PX_IT = 64 / Q;
-        float *tile = reinterpret_cast<float *>(lds) + wave * (32 * N);
-        const int q = lane % Q, pl = lane / Q;
-        float sc[4], bi[4];
+    auto chan = [=](int n) { return ChanConst{scale ? scale[n] : 1.0f, bias ? bias[n] : 0.0f}; };
+    // scale, bias, LeakyReLU, post, then * s2 + post2: one rounded operation after the other, in this order in both forms
+    auto fin = [=](auto &v, const auto &k, int n, int y, int x) {
+        if constexpr (VEC) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            sc[j] = d.scale ? d.scale[4 * q + j] : 1.0f;
-            bi[j] = d.bias ? d.bias[4 * q + j] : 0.0f;
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            __syncthreads();   // the images (m = 0) or the previous row (m = 1) have been read
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) tile[((e & 3) + 8 * (e >> 2) + 4 * h) * N + nb * 32 + r] = acc[m][nb][e];
-            __syncthreads();
-            const int y = ty0 + wave * 2 + m;
-            if (y >= H) continue;
-#pragma unroll
-            for (int it = 0; it < 32 / PX_IT; ++it) {
-                const int xi = it * PX_IT + pl, x = tx0 + xi;
-                if (x >= W) continue;
-                const f32x4 a4 = *reinterpret_cast<const f32x4 *>(tile + xi * N + 4 * q);
-                float v[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v[j] = v[j] * sc[j] + bi[j];
-                    if (leaky) v[j] = v[j] >= 0.0f ? v[j] : v[j] * d.act_alpha;
-                }
-                if (post) {
-                    const f32x4 p4 = *reinterpret_cast<const f32x4 *>(post + (int)(y * d.post_ys + x * d.post_xs) + 4 * q);
-                    v[0] = v[0] + p4.x, v[1] = v[1] + p4.y, v[2] = v[2] + p4.z, v[3] = v[3] + p4.w;
-                }
-                if (post2) {
-                    const f32x4 p4 = *reinterpret_cast<const f32x4 *>(post2 + (int)(y * d.post2_ys + x * d.post2_xs) + 4 * q);
-                    v[0] = v[0] * d.s2 + p4.x, v[1] = v[1] * d.s2 + p4.y, v[2] = v[2] * d.s2 + p4.z, v[3] = v[3] * d.s2 + p4.w;
-                }
-                if (of) *reinterpret_cast<f32x4 *>(of + (int)(y * d.of_ys + x * d.of_xs) + 4 * q) = f32x4{v[0], v[1], v[2], v[3]};
-                if (ob)
-                    *reinterpret_cast<mitcg::u32x2 *>(ob + (int)(y * d.ob_ys + x * d.ob_xs) + 4 * q) =
-                        mitcg::u32x2{mitcg::pack_bf16(v[0], v[1]), mitcg::pack_bf16(v[2], v[3])};
+            for (int j = 0; j < 4; ++j) {
+                v[j] = v[j] * k[j].sc + k[j].bi;
+                if (act == MIT_ACT_LEAKY) v[j] = v[j] >= 0.0f ? v[j] : v[j] * alpha;
             }
-        }
-        return;
-    }
-    // the lane holds column n = nb * 32 + r of the pixels x = tx0 + (e & 3) + 8 (e >> 2) + 4 h of its two rows
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int n = nb * 32 + r;
-        const float sc = d.scale ? d.scale[n] : 1.0f, bi = d.bias ? d.bias[n] : 0.0f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            const int y = ty0 + wave * 2 + m;
-            if (y >= H) continue;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int x = tx0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-                if (x >= W) continue;
-                float v = acc[m][nb][e] * sc + bi;
-                if (leaky) v = v >= 0.0f ? v : v * d.act_alpha;
-                if (post) v = v + post[(int)(y * d.post_ys + x * d.post_xs) + n];
-                if (post2) v = v * d.s2 + post2[(int)(y * d.post2_ys + x * d.post2_xs) + n];
-                if (of) of[(int)(y * d.of_ys + x * d.of_xs) + n] = v;
-                if (ob) ob[(int)(y * d.ob_ys + x * d.ob_xs) + n] = bf16_bits(v);
+            if (post) {
+                const f32x4 p4 = *reinterpret_cast<const f32x4 *>(post + (int)(y * p_ys + x * p_xs) + n);
+                v[0] = v[0] + p4.x, v[1] = v[1] + p4.y, v[2] = v[2] + p4.z, v[3] = v[3] + p4.w;
             }
+            if (post2) {
+                const f32x4 p4 = *reinterpret_cast<const f32x4 *>(post2 + (int)(y * p2_ys + x * p2_xs) + n);
+                v[0] = v[0] * s2 + p4.x, v[1] = v[1] * s2 + p4.y, v[2] = v[2] * s2 + p4.z, v[3] = v[3] * s2 + p4.w;
+            }
+        } else {
+            v = v * k.sc + k.bi;
+            if (act == MIT_ACT_LEAKY) v = v >= 0.0f ? v : v * alpha;
+            if (post) v = v + post[(int)(y * p_ys + x * p_xs) + n];
+            if (post2) v = v * s2 + post2[(int)(y * p2_ys + x * p2_xs) + n];
         }
-    }
+    };
+    store_tile<N, VEC>(acc, lds, TileOut{H, W, ty0, tx0, of, d.of_ys, d.of_xs, ob, d.ob_ys, d.ob_xs}, chan, fin);
 }
 
 constexpr int CAST_BLOCK = 256;
@@ -270,58 +166,40 @@ __global__ __launch_bounds__(CAST_BLOCK) void cast_f32_bf16_kernel(const float *
     }
 }
 
-// [lo, hi) element extent of a strided NHWC tensor with C channels addressed
-int64_t extent(int B, int H, int W, int C, int64_t bs, int64_t ys, int64_t xs) {
-    return (int64_t)(B - 1) * bs + (int64_t)(H - 1) * ys + (int64_t)(W - 1) * xs + C;
-}
-
-// strides of one tensor: x stride >= channels, y stride >= x stride, batch stride >= 0, one image below 2^31 elements
-const char *bad_strides(int H, int W, int C, int64_t bs, int64_t ys, int64_t xs) {
-    if (xs < C) return "x stride smaller than the channel count";
-    if (ys < xs || bs < 0) return "y stride smaller than the x stride, or a negative batch stride";
-    if (ys > INT32_MAX || extent(1, H, W, C, 0, ys, xs) > INT32_MAX) return "one image spans 2^31 elements or more (32-bit offsets inside an image)";
-    return nullptr;
+const char *bad_strides(const MitRdbConv &d, int C, int64_t bs, int64_t ys, int64_t xs) {
+    return conv3x3::bad_strides(d.H, d.W, C, C, bs, ys, xs, "x stride smaller than the channel count");
 }
 
 }  // namespace
 
 extern "C" int mit_rdb_conv3x3_bf16(const MitRdbConv *dp, void *stream) {
+    const char *fn = "mit_rdb_conv3x3_bf16";
     if (!dp) return mit_set_error("mit_rdb_conv3x3_bf16: null descriptor");
     const MitRdbConv &d = *dp;
     if (!d.in || !d.w) return mit_set_error("mit_rdb_conv3x3_bf16: null pointer (in / w)");
-    if (!d.out_f32 && !d.out_bf16) return mit_set_error("mit_rdb_conv3x3_bf16: null pointer (no output: out_f32 and out_bf16 are both NULL)");
-    if (d.B <= 0 || d.H <= 0 || d.W <= 0) return mit_set_error("mit_rdb_conv3x3_bf16: sizes must be positive (B %d, H %d, W %d)", d.B, d.H, d.W);
+    if (check_outputs(fn, d) || check_sizes(fn, d)) return 1;
     if (d.Cin % CK != 0 || d.Cin < 64 || d.Cin > 192)
         return mit_set_error("mit_rdb_conv3x3_bf16: Cin must be a multiple of 32 in [64, 192] (got %d)", d.Cin);
     if (d.N != 32 && d.N != 64) return mit_set_error("mit_rdb_conv3x3_bf16: N must be 32 or 64 (got %d)", d.N);
     if (d.act != MIT_ACT_NONE && d.act != MIT_ACT_LEAKY) return mit_set_error("mit_rdb_conv3x3_bf16: act must be none or leaky (got %d)", d.act);
     const char *why;
-    if ((why = bad_strides(d.H, d.W, d.Cin, d.in_bs, d.in_ys, d.in_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: input strides: %s", why);
-    if (d.post && (why = bad_strides(d.H, d.W, d.N, d.post_bs, d.post_ys, d.post_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: post strides: %s", why);
-    if (d.post2 && (why = bad_strides(d.H, d.W, d.N, d.post2_bs, d.post2_ys, d.post2_xs)))
-        return mit_set_error("mit_rdb_conv3x3_bf16: post2 strides: %s", why);
-    if (d.out_f32 && (why = bad_strides(d.H, d.W, d.N, d.of_bs, d.of_ys, d.of_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: out_f32 strides: %s", why);
-    if (d.out_bf16 && (why = bad_strides(d.H, d.W, d.N, d.ob_bs, d.ob_ys, d.ob_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: out_bf16 strides: %s", why);
-    if (reinterpret_cast<uintptr_t>(d.in) % 16 || reinterpret_cast<uintptr_t>(d.w) % 16 || d.in_xs % 8 || d.in_ys % 8 || d.in_bs % 8)
-        return mit_set_error("mit_rdb_conv3x3_bf16: in and w must be 16-byte aligned and the input strides multiples of 8 elements");
-    if (mit_div_up(d.H, TH) > 65535 || d.B > 65535)
-        return mit_set_error("mit_rdb_conv3x3_bf16: at most 65535 tile rows and 65535 images a launch (grid y / z)");
+    if ((why = bad_strides(d, d.Cin, d.in_bs, d.in_ys, d.in_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: input strides: %s", why);
+    if (d.post && (why = bad_strides(d, d.N, d.post_bs, d.post_ys, d.post_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: post strides: %s", why);
+    if (d.post2 && (why = bad_strides(d, d.N, d.post2_bs, d.post2_ys, d.post2_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: post2 strides: %s", why);
+    if (d.out_f32 && (why = bad_strides(d, d.N, d.of_bs, d.of_ys, d.of_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: out_f32 strides: %s", why);
+    if (d.out_bf16 && (why = bad_strides(d, d.N, d.ob_bs, d.ob_ys, d.ob_xs))) return mit_set_error("mit_rdb_conv3x3_bf16: out_bf16 strides: %s", why);
+    if (check_alignment_and_grid(fn, d, d.w, d.B, "images")) return 1;
     if (d.out_bf16) {
-        // byte addresses as integers: the two may be one buffer (the dense block's) or two
-        const int64_t din = (int64_t)(reinterpret_cast<intptr_t>(d.out_bf16) - reinterpret_cast<intptr_t>(d.in)) / 2;
+        const int64_t din = out_bf16_offset(d);   // the two may be one buffer (the dense block's) or two
         bool overlap;
         if (d.ob_bs == d.in_bs && d.ob_ys == d.in_ys && d.ob_xs == d.in_xs && din > -d.in_xs && din < d.in_xs)
             overlap = din > -(int64_t)d.N && din < d.Cin;   // one buffer, same pixel grid: the channel ranges [0, Cin) and [din, din + N)
         else
-            overlap = din < extent(d.B, d.H, d.W, d.Cin, d.in_bs, d.in_ys, d.in_xs) && -din < extent(d.B, d.H, d.W, d.N, d.ob_bs, d.ob_ys, d.ob_xs);
+            overlap = extents_overlap(d, din, d.N);
         if (overlap) return mit_set_error("mit_rdb_conv3x3_bf16: out_bf16 overlaps the input channels it is computed from");
     }
     const dim3 grid((unsigned)mit_div_up(d.W, TW), (unsigned)mit_div_up(d.H, TH), (unsigned)d.B);
     const double px = (double)d.B * d.H * d.W;
-    // the wide epilogue: fp32 tensors on 16 bytes, the bf16 output on 8, every stride a multiple of four elements
-    auto wide = [](const void *p, int64_t bs, int64_t ys, int64_t xs, int align) {
-        return !p || (reinterpret_cast<uintptr_t>(p) % align == 0 && bs % 4 == 0 && ys % 4 == 0 && xs % 4 == 0);
-    };
     const bool vec = wide(d.post, d.post_bs, d.post_ys, d.post_xs, 16) && wide(d.post2, d.post2_bs, d.post2_ys, d.post2_xs, 16) &&
                      wide(d.out_f32, d.of_bs, d.of_ys, d.of_xs, 16) && wide(d.out_bf16, d.ob_bs, d.ob_ys, d.ob_xs, 8);
     MitProbeScope probe(d.N == 64 ? "rdb_conv3x3_kernel<64>" : "rdb_conv3x3_kernel<32>", (hipStream_t)stream,

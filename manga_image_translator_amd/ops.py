@@ -748,6 +748,18 @@ def _check_nhwc_as(t: torch.Tensor, dtype, shape, what: str) -> None:
         raise ValueError(f"{what}: expected {dtype} {tuple(shape)} with channel stride 1, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
 
 
+def _bind_nhwc_views(d, who: str, shape, views) -> None:
+    """Optional NHWC views of ``shape`` into a descriptor; views: (tensor or None, dtype, pointer field, stride prefix).  A view that is
+    given sets the pointer and ``<prefix>_bs / _ys / _xs``."""
+    for t, dtype, ptr, pre in views:
+        if t is None:
+            continue
+        _check_nhwc_as(t, dtype, shape, f"{who} {ptr}")
+        setattr(d, ptr, t.data_ptr())
+        for ax, nm in enumerate(("bs", "ys", "xs")):
+            setattr(d, f"{pre}_{nm}", t.stride(ax))
+
+
 def cast_bf16(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     """``dst[...] = src.to(bfloat16)`` for NHWC views (channel slices allowed on both sides) through ``mit_cast_f32_bf16``."""
     _check_nhwc(src, "cast_bf16 source")
@@ -783,21 +795,15 @@ class RdbConv3x3:
         """``post``: fp32, added after the activation; ``post2`` with ``s2``: then ``y * s2 + post2`` (MitRdbConv)."""
         B, H, W, Cx = x.shape
         _check_nhwc_as(x, torch.bfloat16, (B, H, W, self.Cin), "RdbConv3x3 input")
-        oshape = (B, H, W, self.Cout)
         d = MitRdbConv()
         d.B, d.H, d.W, d.Cin, d.N = B, H, W, self.Cin, self.Cout
         d.in_bs, d.in_ys, d.in_xs = x.stride(0), x.stride(1), x.stride(2)
         setattr(d, "in", x.data_ptr())   # ``in`` is a keyword
         d.w, d.scale, d.bias = self.w.data_ptr(), _ptr(self.scale), _ptr(self.bias)
         d.act, d.act_alpha, d.s2 = self.act, self.alpha, s2
-        for t, dtype, ptr, pre in ((post, torch.float32, "post", "post"), (post2, torch.float32, "post2", "post2"),
-                                   (out_f32, torch.float32, "out_f32", "of"), (out_bf16, torch.bfloat16, "out_bf16", "ob")):
-            if t is None:
-                continue
-            _check_nhwc_as(t, dtype, oshape, f"RdbConv3x3 {ptr}")
-            setattr(d, ptr, t.data_ptr())
-            for ax, nm in enumerate(("bs", "ys", "xs")):
-                setattr(d, f"{pre}_{nm}", t.stride(ax))
+        _bind_nhwc_views(d, "RdbConv3x3", (B, H, W, self.Cout),
+                         ((post, torch.float32, "post", "post"), (post2, torch.float32, "post2", "post2"),
+                          (out_f32, torch.float32, "out_f32", "of"), (out_bf16, torch.bfloat16, "out_bf16", "ob")))
         return d
 
     def __call__(self, x: torch.Tensor, **kw) -> None:
@@ -832,13 +838,8 @@ class AotConv3x3:
         for g in range(G):
             d.rate[g], d.out_c0[g] = self.rates[g], g * self.Cout
             d.w[g], d.bias[g] = self.w[g].data_ptr(), _ptr(self.bias[g])
-        for t, dtype, ptr, pre in ((out_f32, torch.float32, "out_f32", "of"), (out_bf16, torch.bfloat16, "out_bf16", "ob")):
-            if t is None:
-                continue
-            _check_nhwc_as(t, dtype, (B, H, W, G * self.Cout), f"AotConv3x3 {ptr}")
-            setattr(d, ptr, t.data_ptr())
-            for ax, nm in enumerate(("bs", "ys", "xs")):
-                setattr(d, f"{pre}_{nm}", t.stride(ax))
+        _bind_nhwc_views(d, "AotConv3x3", (B, H, W, G * self.Cout),
+                         ((out_f32, torch.float32, "out_f32", "of"), (out_bf16, torch.bfloat16, "out_bf16", "ob")))
         return d
 
     def __call__(self, x: torch.Tensor, **kw) -> None:

@@ -14,26 +14,19 @@ import torch.nn.functional as F
 
 from manga_image_translator_amd import lib, ops
 
+from _conv3x3_bf16_cases import SENT_BF16, SENT_F32, _activations, _bits, _bits32, _check_f32, _padded, _weight
+
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(2, 18, 20), (1, 19, 45), (1, 41, 18)]
 RATES = [1, 2, 4, 8, 16]
-SENT_BF16, SENT_F32 = 777.0, -12345.0
-U = 2.0 ** -24
-
-
-def _padded(B, H, W, Cn, ld, dtype, fill, dev, c0=0):
-    """A [B, H, W, Cn] view (channels c0 .. c0 + Cn) of a [B, H, W + 1, ld] buffer filled with ``fill``: padded x and y strides."""
-    base = torch.full((B, H, W + 1, ld), fill, dtype=dtype, device=dev)
-    return base, base[:, :, :W, c0:c0 + Cn]
 
 
 def _case(B, H, W, Cin, N, G, seed):
     """Operands (CPU): bf16 activations whose images differ in magnitude by 1000x, G weights and biases."""
     g = torch.Generator().manual_seed(seed)
-    a = torch.randn(B, H, W, Cin, generator=g)
-    a = (a * torch.tensor([1.0, 1000.0])[:B].view(B, 1, 1, 1)).to(torch.bfloat16)
-    ws = [torch.randn(N, Cin, 3, 3, generator=g) / (3.0 * Cin ** 0.5) for _ in range(G)]
+    a = _activations(g, B, H, W, Cin)
+    ws = [_weight(g, N, Cin) for _ in range(G)]
     bs = [torch.randn(N, generator=g) for _ in range(G)]
     return a, ws, bs
 
@@ -49,22 +42,6 @@ def _reference(a, w, bias, rate, relu):
     if relu:
         v = v.clamp_min(0.0)
     return v, S + bias.double().abs()
-
-
-def _check_f32(got, ref, mag, Cin, what):
-    err = (got.double() - ref).abs()
-    tol = (9 * Cin + 8) * U * mag
-    worst = (err / tol.clamp_min(1e-300)).max().item()
-    print(f"{what}: max err {err.max().item():.3e}, worst err / tol {worst:.3f}")
-    assert bool((err <= tol).all()), (what, worst)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
-
-
-def _bits32(t):
-    return t.contiguous().view(torch.int32)
 
 
 def test_exported_extents():

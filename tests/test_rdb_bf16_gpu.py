@@ -16,28 +16,20 @@ import torch.nn.functional as F
 
 from manga_image_translator_amd import lib, ops
 
+from _conv3x3_bf16_cases import SENT_BF16, SENT_F32, _activations, _bits, _check_f32, _padded, _weight
+
 pytestmark = pytest.mark.gpu
 
 TH, TW = lib.MIT_RDB_TILE_H, lib.MIT_RDB_TILE_W
 SHAPES = [(1, 1, 1), (2, 3, 5), (1, TH, TW), (2, TH + 1, TW + 1), (1, 2 * TH - 1, TW - 1)]
 CINS = [64, 96, 128, 160, 192]
 LD = 200                      # channels of the dense-block buffer: 192 + 8 of padding that must keep the sentinel
-SENT_BF16, SENT_F32 = 777.0, -12345.0
-U = 2.0 ** -24
-
-
-def _padded(B, H, W, Cn, ld, dtype, fill, dev):
-    """A [B, H, W, Cn] view of a [B, H, W + 1, ld] buffer filled with ``fill``: padded x and y strides."""
-    base = torch.full((B, H, W + 1, ld), fill, dtype=dtype, device=dev)
-    return base, base[:, :, :W, :Cn]
 
 
 def _case(B, H, W, Cin, N, seed):
     """Operands (CPU): bf16 activations whose images differ in magnitude by 1000x, a weight, bias, post tensors."""
     g = torch.Generator().manual_seed(seed)
-    a = torch.randn(B, H, W, Cin, generator=g)
-    a = (a * torch.tensor([1.0, 1000.0])[:B].view(B, 1, 1, 1)).to(torch.bfloat16)
-    w = (torch.randn(N, Cin, 3, 3, generator=g) / (3.0 * Cin ** 0.5))
+    a, w = _activations(g, B, H, W, Cin), _weight(g, N, Cin)
     bias = torch.randn(N, generator=g)
     post = torch.randn(B, H, W, N, generator=g) * 3.0
     post2 = torch.randn(B, H, W, N, generator=g) * 5.0
@@ -61,18 +53,6 @@ def _reference(a, wq, scale, bias_eff, alpha, post, s2, post2):
         s2d = float(np.float32(s2))
         v, mag = v * s2d + post2.double(), mag * abs(s2d) + post2.double().abs()
     return v, mag
-
-
-def _check_f32(got, ref, mag, Cin, what):
-    err = (got.double() - ref).abs()
-    tol = (9 * Cin + 8) * U * mag
-    worst = (err / tol.clamp_min(1e-300)).max().item()
-    print(f"{what}: max err {err.max().item():.3e}, worst err / tol {worst:.3f}")
-    assert bool((err <= tol).all()), (what, worst)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16)
 
 
 @pytest.mark.parametrize("Cin", CINS)
