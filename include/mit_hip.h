@@ -1208,6 +1208,48 @@ typedef struct MitAotConv {
 } MitAotConv;
 int mit_aot_conv3x3_bf16(const MitAotConv *d, void *stream);
 
+/* Plain 3x3 convolution on bf16-resident activations (additive in ABI 26) ------------------------------------------------------------
+ * mit_conv3x3_bf16 — a 3x3, stride 1, zero-pad 1 convolution of a bf16 NHWC input with per-channel scale / bias (a folded eval
+ * BatchNorm) and ReLU / LeakyReLU, on v_mfma_f32_32x32x16_bf16 with fp32 accumulation: the layers of FFDNet (96 features) for the mc2
+ * colorizer's bf16 precision, whose activations live in HBM as bf16 between the layers.  A workgroup owns MIT_CONV3X3_TILE_H x
+ * MIT_CONV3X3_TILE_W output pixels and all N columns: per chunk of 32 input channels it stages the tile plus its one-pixel halo (zeros
+ * outside the image) and the chunk's 9 x 32 weight rows to LDS once and serves all nine taps from there; nothing is rounded or split in
+ * the kernel on the way to the MFMA.  N = 96 takes 83 KB of LDS (one workgroup a CU; N = 32 | 64 fit two): the same 96 columns as
+ * two launches of 64 + 32 columns into channel slices of the output give the same bits.
+ *
+ *   acc[n]  = sum_{tap = (ky, kx)} sum_{c < Cin} in[b, y + ky - 1, x + kx - 1, c] * w[(tap * Cin + c) * N + n]
+ *             (fp32, exact products; order: 32-channel chunk, tap, channel — the same for every pixel, batch and grid)
+ *   v       = acc * scale[n] + bias[n]                  scale NULL = 1, bias NULL = 0; two rounded operations, no FMA
+ *   v       = act == MIT_ACT_RELU ? max(v, 0) : act == MIT_ACT_LEAKY ? (v >= 0 ? v : v * act_alpha) : v
+ *   out_f32[b, y, x, n]  = v                            when out_f32  != NULL
+ *   out_bf16[b, y, x, n] = bf16(v)                      when out_bf16 != NULL: round to nearest even of the fp32 value, the bits of
+ *                                                       torch.Tensor.to(torch.bfloat16)
+ * A pixel's result depends on nothing but its own 3 x 3 x Cin window: not on B, the tile it falls in or the launch's other images.
+ *
+ * Requirements (anything else is refused before any HIP call): Cin % 32 == 0 and 32 <= Cin <= 192; N 32, 64 or 96; act NONE, RELU or
+ * LEAKY; at least one output; B, H, W > 0; every x stride >= the channels addressed through it, y stride >= x stride, batch stride
+ * >= 0; in, w 16-byte aligned and the input strides multiples of 8 elements (16-byte loads); one image of every tensor spans fewer
+ * than 2^31 elements (image bases are 64-bit, offsets inside an image 32-bit); ceil(H / MIT_CONV3X3_TILE_H) and B <= 65535 (grid y /
+ * z); out_bf16 must not overlap the Cin input channels (same strides: disjoint channel ranges; other strides: disjoint extents).
+ * All strides are element counts of the tensor's own type. */
+#define MIT_CONV3X3_TILE_H 8
+#define MIT_CONV3X3_TILE_W 32
+typedef struct MitConv3x3Bf16 {
+    const uint16_t *in;               /* bf16 bits, NHWC */
+    int64_t in_bs, in_ys, in_xs;
+    int32_t B, H, W, Cin;
+    const uint16_t *w;                /* [9 * Cin][N] bf16 bits, k = (ky * 3 + kx) * Cin + c */
+    int32_t N;
+    int32_t act;
+    float act_alpha;
+    const float *scale, *bias;        /* [N] */
+    float *out_f32;
+    int64_t of_bs, of_ys, of_xs;
+    uint16_t *out_bf16;
+    int64_t ob_bs, ob_ys, ob_xs;
+} MitConv3x3Bf16;
+int mit_conv3x3_bf16(const MitConv3x3Bf16 *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

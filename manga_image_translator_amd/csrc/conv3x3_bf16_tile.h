@@ -1,6 +1,8 @@
-// conv3x3_bf16_tile.h — what the bf16-resident 3x3 convolutions (rdb_bf16.hip, aot_bf16.hip) have in common: the tile geometry, the W
-// image, the MFMA step of a (tap, k-step), the two store forms of the epilogue, and the host checks on strided NHWC tensors.  A kernel
-// adds its A operand (where a lane's A fragments come from), its pointwise epilogue and its own argument rules.
+// conv3x3_bf16_tile.h — what the bf16-resident 3x3 convolutions (rdb_bf16.hip, aot_bf16.hip, mc2_bf16.hip) have in common: the tile
+// geometry, the W image, the MFMA step of a (tap, k-step), the two store forms of the epilogue, and the host checks on strided NHWC
+// tensors.  A kernel adds its A operand (where a lane's A fragments come from; HaloImage is mc2_bf16.hip's — rdb_bf16.hip keeps its own
+// copy of the same staging, because rewriting it on the struct changed its device code), its pointwise epilogue and its own argument
+// rules.
 //
 // Workgroup = THREADS = 256 lanes = 4 waves, one tile of TH x TW = 8 x 32 output pixels; wave w owns rows 2w, 2w + 1 (two 32-pixel MFMA
 // row blocks) and all N columns: 2 x N / 32 accumulators of 16 registers.  The K loop walks chunks of CK = 32 input channels, nine taps
@@ -92,6 +94,53 @@ struct WImage {
     }
 };
 
+// A image of a chunk for the plain 3x3 (pad 1, no dilation): the tile plus its one-pixel halo, [10 x 34 halo pixels][32 ch] bf16 at
+// PIX_B bytes a pixel, zeros outside the image.  A lane stages ROUNDS 16-byte units (unit u = pixel * 4 + part); fetch() / stage()
+// split as WImage's do.
+struct HaloImage {
+    static constexpr int HH = TH + 2, HW = TW + 2, HALO = HH * HW;   // 340 halo pixels
+    static constexpr int BYTES = HALO * PIX_B;                       // 27200
+    static constexpr int UNITS = HALO * (CK / 8);                    // 1360
+    static constexpr int ROUNDS = (UNITS + THREADS - 1) / THREADS;
+
+    unsigned char *lds;
+    int off[ROUNDS];   // element offset of the unit in the image at chunk 0; -1 = outside the image (zeros), -2 = no unit
+    u32x4 reg[ROUNDS];
+
+    __device__ __forceinline__ HaloImage(unsigned char *ldsA, int H, int W, int ty0, int tx0, int64_t in_ys, int64_t in_xs) : lds(ldsA) {
+        const int tid = threadIdx.x;
+#pragma unroll
+        for (int i = 0; i < ROUNDS; ++i) {
+            const int u = tid + i * THREADS;
+            const int p = u >> 2, part = u & 3;
+            const int hy = p / HW, hx = p - hy * HW;
+            const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
+            const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
+            off[i] = u >= UNITS ? -2 : (inside ? (int)(gy * in_ys + gx * in_xs) + part * 8 : -1);
+        }
+    }
+    __device__ __forceinline__ void fetch(const uint16_t *in, int c0) {
+#pragma unroll
+        for (int i = 0; i < ROUNDS; ++i) {
+            reg[i] = u32x4{0u, 0u, 0u, 0u};
+            if (off[i] >= 0) reg[i] = *reinterpret_cast<const u32x4 *>(in + off[i] + c0);
+        }
+    }
+    __device__ __forceinline__ void stage() {
+        const int tid = threadIdx.x;
+#pragma unroll
+        for (int i = 0; i < ROUNDS; ++i) {
+            const int u = tid + i * THREADS;
+            if (off[i] != -2) *reinterpret_cast<u32x4 *>(lds + (u >> 2) * PIX_B + (u & 3) * 16) = reg[i];
+        }
+    }
+    // this lane's A fragment of its row m (0 | 1) at tap (dy, dx), k-step s
+    __device__ __forceinline__ bf16x8 frag(int m, int dy, int dx, int s) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        return *reinterpret_cast<const bf16x8 *>(lds + ((wave * 2 + m + dy) * HW + (lane & 31) + dx) * PIX_B + (lane >> 5) * 16 + s * 32);
+    }
+};
+
 template <int NB>
 __device__ __forceinline__ void clear(f32x16 (&acc)[2][NB]) {
 #pragma unroll
@@ -146,6 +195,7 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[2][N / 32], void 
         // one row of the wave's two at a time: 32 pixels x N fp32 of LDS a wave (pixel rows of N floats: the ds_read_b128 lane groups
         // fall on 16 different slots without padding), then lane = (pixel, four channels)
         constexpr int Q = N / 4, PX_IT = 64 / Q;
+        static_assert(32 % PX_IT == 0, "whole iterations over a row's 32 pixels");
         float *tile = reinterpret_cast<float *>(lds) + wave * (32 * N);
         const int q = lane % Q, pl = lane / Q;
         decltype(chan(0)) k[4];
@@ -163,6 +213,9 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[2][N / 32], void 
             if (y >= o.H) continue;
 #pragma unroll
             for (int it = 0; it < 32 / PX_IT; ++it) {
+                if constexpr (64 % Q != 0) {   // N = 96: 24 lane groups x 2 pixels occupy 48 lanes; lanes 48 .. 63 (pl = 2) would
+                    if (pl >= PX_IT) continue;  // address a pixel of the next iteration (past the tile at the last one) and idle
+                }
                 const int xi = it * PX_IT + pl, x = o.tx0 + xi;
                 if (x >= o.W) continue;
                 const f32x4 a4 = *reinterpret_cast<const f32x4 *>(tile + xi * N + 4 * q);

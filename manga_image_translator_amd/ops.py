@@ -20,11 +20,11 @@ import torch
 
 from . import lib as _lib
 from .lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_POST_FIRST, ACT_RELU, ACT_SIGMOID, ACT_SILU, MIT_MAX_TAPS, PAD_REFLECT,
-                  PAD_ZERO, MitAotConv, MitConvGemm, MitConvGemmMember, MitPGemm, MitRdbConv, MitTensorMap)
+                  PAD_ZERO, MitAotConv, MitConv3x3Bf16, MitConvGemm, MitConvGemmMember, MitPGemm, MitRdbConv, MitTensorMap)
 
 __all__ = [
     "ACT_NONE", "ACT_RELU", "ACT_LEAKY", "ACT_SILU", "ACT_SIGMOID", "ACT_GELU", "ACT_POST_FIRST", "PAD_ZERO", "PAD_REFLECT",
-    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "AotConv3x3", "pack_rdb_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "launch_conv_gemm_group", "conv_gemm_group_plan", "current_stream",
+    "Conv2d", "ConvSmallCout", "split_mode", "ensure_split", "set_split_mode", "gemm_mode", "ConvTranspose2d", "UpsampleConv2d", "RdbConv3x3", "Conv3x3Bf16", "AotConv3x3", "pack_rdb_weight", "pad_cin_weight", "cast_bf16", "fold_bn", "conv_gemm_desc", "launch_conv_gemm", "launch_conv_gemm_group", "conv_gemm_group_plan", "current_stream",
 ]
 
 
@@ -808,6 +808,72 @@ class RdbConv3x3:
 
     def __call__(self, x: torch.Tensor, **kw) -> None:
         _lib.check(_lib.load().mit_rdb_conv3x3_bf16(C.byref(self.desc(x, **kw)), C.c_void_p(current_stream())), "mit_rdb_conv3x3_bf16")
+
+
+def pad_cin_weight(weight: torch.Tensor, cin: int) -> torch.Tensor:
+    """[N, Cin, 3, 3] -> [N, cin, 3, 3] with zero input channels appended (``cin`` >= Cin): a layer whose input has fewer channels than
+    the kernel's 32-channel chunk.  The products of the appended rows are exact zeros."""
+    N, Cin, kh, kw = weight.shape
+    if cin < Cin:
+        raise ValueError(f"pad_cin_weight: {cin} channels are fewer than the weight's {Cin}")
+    out = torch.zeros(N, cin, kh, kw, dtype=torch.float32, device=weight.device)
+    out[:, :Cin] = weight.detach().to(torch.float32)
+    return out
+
+
+class Conv3x3Bf16:
+    """A plain 3x3, stride 1, zero-pad 1 convolution (+ folded eval BatchNorm2d + activation) on bf16-resident activations:
+    ``mit_conv3x3_bf16``.  ``x`` is a bf16 NHWC view; the result goes to a bf16 view, an fp32 view, or both (channel slices of wider
+    buffers allowed).  weight: [N, Cin, 3, 3] with Cin % 32 == 0 (``pad_cin_weight``) and N = 32, 64 or 96.  ``split``: column counts
+    that add up to N, e.g. (64, 32) — the layer then runs as one launch per part into the matching channel slices of the outputs,
+    which gives the bits of the one launch (a column's sum does not depend on the other columns)."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, bn=None, act: int = ACT_NONE, alpha: float = 0.0,
+                 split: Optional[Sequence[int]] = None, device="cuda"):
+        self.Cout, self.Cin = int(weight.shape[0]), int(weight.shape[1])
+        self.act, self.alpha = act, alpha
+        self.parts = (self.Cout,) if split is None else tuple(int(n) for n in split)
+        if sum(self.parts) != self.Cout or min(self.parts) <= 0:
+            raise ValueError(f"Conv3x3Bf16: split {self.parts} does not add up to the {self.Cout} output channels")
+        scale = bias_t = None
+        if bn is not None:
+            scale, bias_t = fold_bn(*bn, conv_bias=bias)
+        elif bias is not None:
+            bias_t = bias.detach().to(torch.float32)
+        self.scale = None if scale is None else scale.to(device).contiguous()
+        self.bias = None if bias_t is None else bias_t.to(device).contiguous()
+        self.w, n0 = [], 0
+        for n in self.parts:   # a part's weight is its own contiguous [9 * Cin][n]
+            self.w.append(pack_rdb_weight(weight[n0:n0 + n]).to(device))
+            n0 += n
+
+    def descs(self, x: torch.Tensor, *, out_bf16: Optional[torch.Tensor] = None, out_f32: Optional[torch.Tensor] = None) -> List[MitConv3x3Bf16]:
+        B, H, W, Cx = x.shape
+        _check_nhwc_as(x, torch.bfloat16, (B, H, W, self.Cin), "Conv3x3Bf16 input")
+        for t, dt, nm in ((out_bf16, torch.bfloat16, "out_bf16"), (out_f32, torch.float32, "out_f32")):
+            if t is not None:
+                _check_nhwc_as(t, dt, (B, H, W, self.Cout), f"Conv3x3Bf16 {nm}")
+        out, n0 = [], 0
+        for n, w in zip(self.parts, self.w):
+            d = MitConv3x3Bf16()
+            d.B, d.H, d.W, d.Cin, d.N = B, H, W, self.Cin, n
+            d.in_bs, d.in_ys, d.in_xs = x.stride(0), x.stride(1), x.stride(2)
+            setattr(d, "in", x.data_ptr())   # ``in`` is a keyword
+            d.w = w.data_ptr()
+            d.scale = None if self.scale is None else self.scale.data_ptr() + 4 * n0
+            d.bias = None if self.bias is None else self.bias.data_ptr() + 4 * n0
+            d.act, d.act_alpha = self.act, self.alpha
+            _bind_nhwc_views(d, "Conv3x3Bf16", (B, H, W, n),
+                             ((None if out_f32 is None else out_f32[..., n0:n0 + n], torch.float32, "out_f32", "of"),
+                              (None if out_bf16 is None else out_bf16[..., n0:n0 + n], torch.bfloat16, "out_bf16", "ob")))
+            out.append(d)
+            n0 += n
+        return out
+
+    def __call__(self, x: torch.Tensor, **kw) -> None:
+        lib = _lib.load()
+        for d in self.descs(x, **kw):
+            _lib.check(lib.mit_conv3x3_bf16(C.byref(d), C.c_void_p(current_stream())), "mit_conv3x3_bf16")
 
 
 class AotConv3x3:

@@ -1035,10 +1035,23 @@ class HipESRGANUpscaler(_EnginePlugin, _UpBase):
         return out
 
 
+MC2_PRECISIONS = ("fp32", "bf16")
+
+
+def mc2_precision_default() -> str:
+    """The ``precision`` of an mc2 colorizer plugin created without one (``register()``, ``serve.py``): ``MIT_MC2_PRECISION`` in the
+    environment, fp32 when unset."""
+    v = os.environ.get("MIT_MC2_PRECISION", "").strip().lower() or "fp32"
+    if v not in MC2_PRECISIONS:
+        raise ValueError(f"MIT_MC2_PRECISION must be one of {MC2_PRECISIONS} (got {v!r})")
+    return v
+
+
 class HipMangaColorizer(_EnginePlugin, _ColBase):
     """``--colorizer mc2`` (manga-colorization-v2: FFDNet denoiser + SE-ResNeXt generator) on the HIP engine.  Same ``_infer(image,
     colorization_size, denoise_sigma=25)`` -> RGB ``PIL.Image`` at the network's size, like the reference.  ``weights``:
-    {"generator": state_dict, "denoiser": state_dict}."""
+    {"generator": state_dict, "denoiser": state_dict}.  ``precision``: "fp32" (default) or "bf16" (FFDNet on bf16-resident
+    activations, the generator's dense convolutions on the one-product bf16 tiles, ``Mc2Engine``); None = ``mc2_precision_default()``."""
     _KEY = _key = "mc2_hip"
     _MODEL_SUB_DIR = os.path.join(_ColBase._MODEL_SUB_DIR, "manga-colorization-v2")
     _MODEL_MAPPING: Dict = {  # colorization/manga_colorization_v2.py:15-27
@@ -1054,8 +1067,11 @@ class HipMangaColorizer(_EnginePlugin, _ColBase):
         },
     }
 
-    def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, **kwargs):
+    def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, precision: Optional[str] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        self.precision = mc2_precision_default() if precision is None else precision
+        if self.precision not in MC2_PRECISIONS:         # a bad value raises here, not at the first page
+            raise ValueError(f"mc2 precision must be one of {MC2_PRECISIONS} (got {self.precision!r})")
         self._hand_over(weights)
 
     async def _load(self, device: str):
@@ -1063,7 +1079,7 @@ class HipMangaColorizer(_EnginePlugin, _ColBase):
 
         dev = _gpu_device(device)
         w = self._weights or _load_mc2_checkpoint(self)
-        self.engine = mc2.Mc2Engine(w["generator"], w["denoiser"], device=dev)
+        self.engine = mc2.Mc2Engine(w["generator"], w["denoiser"], device=dev, precision=self.precision)
         self.device = device
 
     @torch.no_grad()

@@ -133,6 +133,23 @@ def stage_keys(config, detector_filters: bool = False) -> Tuple[str, str, str]:
     return tuple(out)
 
 
+SUPPORTED_COLORIZER_KEYS = ("none", "mc2")
+
+
+def colorizer_options(config) -> Tuple[str, int, float]:
+    """(colorizer, colorization_size, denoise_sigma) of a request: ``config.colorizer.colorizer`` / ``colorization_size`` /
+    ``denoise_sigma`` (ColorizerConfig, config.py:301-307), an absent field (or section, or config) at the reference's default
+    ("none", 576, 30).  Raises ValueError, naming the key and the supported set, for a colorizer this worker has no HIP plugin for
+    (mc2 is the only one): a request is never served by something else silently."""
+    col = _as_dict(config).get("colorizer")
+    key = _field(col, "colorizer")
+    key = "none" if key is None else str(key)
+    if key not in SUPPORTED_COLORIZER_KEYS:
+        raise ValueError(f"colorizer.colorizer = {key!r} is not served by this worker (supported: {', '.join(SUPPORTED_COLORIZER_KEYS)})")
+    size, sigma = _field(col, "colorization_size"), _field(col, "denoise_sigma")
+    return key, 576 if size is None else int(size), 30 if sigma is None else float(sigma)
+
+
 # ---- what a worker hosts when the orchestrator itself cannot be imported ---------------------------------------------------------------
 class DenseStages:
     """The three HIP plugins of one GPU, chained as ``MangaTranslator._translate`` chains the stages it owns
@@ -168,6 +185,32 @@ class DenseStages:
         self.last_batch_plan: List[Tuple[List[int], str]] = []
         self.last_coupled_seconds: List[Dict[str, float]] = []
         self.up = None             # the upscaler plugin: loaded by the first request that asks for upscaling
+        self.col = None            # the mc2 colorizer plugin: loaded by the first request (config mode) that names it
+        self.last_colorizer: Optional[str] = None    # the colorizer that served the last request: "mc2" | "none"
+
+    MC2_SYNTH_SEED = 0     # the seed of the synthetic colorizer weights (generator: this seed, FFDNet: this seed + 1)
+
+    async def _load_colorizer(self):
+        """The ``mc2`` plugin, on the first request whose ``config.colorizer.colorizer`` is ``mc2``: from the checkpoint under
+        ``<model_dir>/colorization/manga-colorization-v2``, else seeded synthetic weights of ``mc2_schema`` (``MC2_SYNTH_SEED`` = 0 for
+        the generator, 1 for FFDNet), identical in every worker."""
+        if self.col is None:
+            from . import mc2_schema, plugins as P, synth
+
+            if self.params.get("model_dir"):
+                col = P.HipMangaColorizer()
+            else:
+                seed = self.MC2_SYNTH_SEED
+                col = P.HipMangaColorizer(weights={"generator": synth.synth_state_dict(mc2_schema.generator_schema(), seed=seed),
+                                                   "denoiser": synth.synth_state_dict(mc2_schema.ffdnet_schema(), seed=seed + 1)})
+            await col.load("cuda")
+            self.col = col
+        return self.col
+
+    def _colorizer_options(self, cfg) -> Tuple[str, int, float]:
+        """``colorizer_options`` of a request in "config" mode; a worker in "fixed" mode ignores the section, as it ignores every stage
+        name."""
+        return colorizer_options(cfg) if self.stages == "config" else ("none", 576, 30.0)
 
     async def _load_upscaler(self):
         """The ``4xultrasharp`` plugin, on the first request with ``config["upscale"]["upscale_ratio"]``: from the checkpoint under
@@ -193,6 +236,7 @@ class DenseStages:
         """The stages that serve a request with this config — ``FIXED_STAGE_KEYS`` in "fixed" mode, ``stage_keys(config)`` in
         "config" mode — noted for ``_load`` (which brings ``self.det`` / ``self.ocr`` / ``self.inp`` to them) and in ``last_stage_keys``."""
         self._keys = stage_keys(config, self.detector_filters) if self.stages == "config" else FIXED_STAGE_KEYS
+        self._colorizer_options(config)     # an unknown colorizer is refused here, with the other stage names
         self.last_stage_keys = self._keys
         return self._keys
 
@@ -267,12 +311,23 @@ class DenseStages:
         if page.ndim != 3 or page.shape[2] != 3:
             raise ValueError(f"image must be HxWx3 (got {page.shape})")
         ratio, revert = self._upscale_options(cfg)
-        in_h, in_w = page.shape[:2]
+        in_h, in_w = page.shape[:2]      # ctx.input.size: what revert_upscaling returns to, colorized or not (manga_translator.py:626-629)
+        col_key, col_size, col_sigma = self._colorizer_options(cfg)
+        self.last_colorizer = col_key
+        page_dev = None
+        if col_key == "mc2":   # colorize -> upscale -> detect -> ... (manga_translator.py:437-463): the colorized RGB image, at the
+            import torch       # network's size, is the page of every later stage
+
+            col = await self._load_colorizer()
+            page_dev = col.engine.forward(torch.from_numpy(page).to(col.engine.device)[None], col_size, col_sigma)   # the one upload
+            if not ratio:
+                page = np.ascontiguousarray(page_dev[0].cpu().numpy())
         if ratio:   # the page is upscaled first and every later stage sees the upscaled page (manga_translator.py:453-465, :683)
             import torch
 
             up = await self._load_upscaler()
-            page = np.ascontiguousarray(up.engine.upscale(torch.from_numpy(page).to(up.engine.device)[None], ratio)[0].cpu().numpy())
+            src = page_dev.to(up.engine.device) if page_dev is not None else torch.from_numpy(page).to(up.engine.device)[None]
+            page = np.ascontiguousarray(up.engine.upscale(src, ratio)[0].cpu().numpy())
         H, W = page.shape[:2]
         if self.detector_filters:   # CommonDetector.detect (detection/common.py:12-64): the request's filters, the small-page border
             tls, mask_raw, _ = await self.det.detect(page, *self._detector_args(cfg), *detector_filter_options(cfg))
@@ -385,6 +440,8 @@ class DenseStages:
 
         if page.ndim != 3 or page.shape[2] != 3:
             return "not HxWx3"
+        if self._colorizer_options(cfg)[0] != "none":
+            return "colorizer"      # the coupled engine starts at the detector
         if self._upscale_options(cfg)[0]:
             return "upscale"
         if self.detector_filters and (any(detector_filter_options(cfg)) or min(page.shape[:2]) < 400):
@@ -431,6 +488,7 @@ class DenseStages:
         images = list(images)
         cfgs = self.page_configs(config, len(images))
         self._select(cfgs[0] if cfgs else config)     # (the pages of a request share everything but textlines / mask / mask_raw)
+        self.last_colorizer = self._colorizer_options(cfgs[0] if cfgs else config)[0]
         await self._load()
         pages = [np.ascontiguousarray(np.asarray(im.convert("RGB") if hasattr(im, "convert") else im, dtype=np.uint8)) for im in images]
         plan = self.plan_batches([p.shape[:2] for p in pages], [self._loop_reason(p, c) for p, c in zip(pages, cfgs)], int(batch_size))
@@ -484,7 +542,7 @@ class DenseStages:
 
         return {"device": self.device_name, "visible_devices": os.environ.get("HIP_VISIBLE_DEVICES"), "n_visible": torch.cuda.device_count(),
                 "pid": os.getpid(), "pages_batched": self.pages_batched, "pages_looped": self.pages_looped, "stages": self.stages,
-                "last_stage_keys": self.last_stage_keys}
+                "last_stage_keys": self.last_stage_keys, "last_colorizer": self.last_colorizer}
 
 
 def _as_dict(config) -> dict:
