@@ -1250,6 +1250,76 @@ typedef struct MitConv3x3Bf16 {
 } MitConv3x3Bf16;
 int mit_conv3x3_bf16(const MitConv3x3Bf16 *d, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * manga-ocr recogniser (``--ocr mocr``, additive in ABI 26): reference manga_translator/ocr/model_manga_ocr.py:132-295, whose text comes
+ * from a HuggingFace VisionEncoderDecoderModel (ViT / DeiT encoder, BERT decoder with cross-attention) driven by ``generate``.  The
+ * encoder runs on the Linear / attention entry points above plus the three below; the whole of ``generate`` after the encoder is
+ * mit_mocr_decode.  Every size comes from the model's config: nothing here is fixed to a checkpoint. */
+
+/* nn.LayerNorm over the last dim for any D in 1 .. 8192 (mit_layernorm stops at 512): one wave per row, mean then centred variance. */
+int mit_layernorm_wide(const float *in_dev, int64_t in_rowstride, const float *w_dev, const float *b_dev, float *out_dev,
+                       int64_t out_rowstride, int rows, int D, float eps, void *stream);
+/* Pillow's Image.convert("L").convert("RGB") on u8 RGB pixels: L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 in all three channels. */
+int mit_mocr_gray(const uint8_t *rgb_dev, int64_t npix, uint8_t *out_dev, void *stream);
+/* u8 RGB images [N][S][S][3] -> the ViT patch rows fp32 [N][(S / ps)^2][3 ps ps], column = (c, py, px) as the axes of the patch
+ * projection's weight, value = (u8 * (1 / 255) - 0.5) / 0.5 in fp32 (ViTImageProcessor: rescale, then normalize).  S % ps == 0. */
+int mit_mocr_patches(const uint8_t *img_dev, int N, int S, int ps, float *out_dev, void *stream);
+
+/* One post-LN BertLayer with cross-attention: q = attention.self.query scaled by head_dim**-0.5, kv = attention.self key|value fused
+ * (their rows go straight into the K / V history), out = attention.output.dense, ln1 = attention.output.LayerNorm, q2 (scaled) / out2 /
+ * ln2 = crossattention, ff1 = intermediate.dense (+ erf GELU), ff2 = output.dense, ln3 = output.LayerNorm. */
+typedef struct MitMocrLayer {
+    const float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ln3_w, *ln3_b;
+    MitLinear q, kv, out, q2, out2, ff1, ff2;
+} MitMocrLayer;
+
+typedef struct MitMocrDecoder {
+    const MitMocrLayer *layers;       /* HOST array [n_layers] */
+    int32_t n_layers, hidden, heads, inter, vocab, max_pos;
+    const float *word_emb, *pos_emb, *type_emb; /* [vocab][hidden], [max_pos][hidden], [hidden] (token type 0) */
+    const float *emb_ln_w, *emb_ln_b;
+    MitLinear head_dense;              /* cls.predictions.transform.dense (+ erf GELU) */
+    const float *head_ln_w, *head_ln_b;
+    MitLinear head_out;                /* cls.predictions.decoder: hidden -> vocab, with its bias */
+    float ln_eps;
+    int32_t _pad;
+} MitMocrDecoder;
+
+typedef struct MitMocrDecodeArgs {
+    int32_t N, L;                 /* text lines; encoder tokens per line */
+    const float *mem_k, *mem_v;   /* [n_layers][N][L][hidden] cross-attention keys / values, projected once per line */
+    int32_t num_beams;            /* 1 (greedy) .. 8 */
+    int32_t max_length;           /* tokens of a result, decoder_start_token_id included */
+    int32_t no_repeat_ngram_size; /* 0: off */
+    int32_t early_stopping;       /* 0 | 1 (GenerationConfig.early_stopping False | True) */
+    int32_t eos_token_id, pad_token_id, decoder_start_token_id;
+    int32_t form;                 /* 0: the few-row form of a step where the GEMM mode (6 | 9) and the packed weights allow; 1: tiled */
+    double length_penalty;
+    void *workspace;              /* device scratch of mit_mocr_decode_workspace_bytes() */
+    int64_t workspace_bytes;
+    int32_t *res_tok;             /* [N][max_length], pad_token_id beyond res_len */
+    int32_t *res_len;             /* [N] */
+    float *res_score;             /* [N] sum of log-probabilities / generated length ** length_penalty (sequences_scores) */
+    float *trace_logits;          /* optional [max_length - 1][N * num_beams][vocab]: log-probabilities after the logits processors */
+    int32_t *trace_hist;          /* optional [max_length - 1][N * num_beams][max_length]: running beams after each step */
+    int32_t steps_run;            /* out */
+    int32_t form_run;             /* out: 0 every Linear of a step ran on the tiled GEMM; 1 on the few-row form except the vocabulary Linear
+                                   * (vocab % 8 != 0); 2 on the few-row form throughout */
+} MitMocrDecodeArgs;
+
+/* HuggingFace beam search (transformers generation/utils.py, _beam_search; num_beams == 1: greedy) as one native call: per step
+ * embeddings + LayerNorm -> the decoder layers (self-attention over a K / V history that follows the beams' parent links,
+ * cross-attention over mem_k / mem_v) -> LM head -> log-softmax -> no-repeat-n-gram ban -> top 2 num_beams over beams x vocab ->
+ * running / finished beam bookkeeping.  A line that can no longer change keeps its rows in place and is not touched again.
+ * The workspace holds the K / V history [n_layers][2][N * num_beams][max_length][hidden] in fp32 (the bulk of it): callers with many
+ * lines decode them in chunks (results do not depend on what else is in the call).
+ * Synchronises the stream every four steps to test for the early exit. */
+int64_t mit_mocr_decode_workspace_bytes(int N, int num_beams, int max_length, int hidden, int inter, int vocab, int n_layers);
+int mit_mocr_decode(const MitMocrDecoder *dec, MitMocrDecodeArgs *args, void *stream);
+/* The bookkeeping kernels alone on given log-probability tables logp_dev [steps][N * num_beams][vocab] (before the n-gram ban): fills
+ * res_tok / res_len / res_score and trace_hist of args.  The workspace is sized with hidden = inter = n_layers = 0. */
+int mit_mocr_beam_replay(const float *logp_dev, int steps, int vocab, MitMocrDecodeArgs *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,26 @@ def synthetic_weights(seed: int = 0, lama_blocks: int = 9, dict_size: int = DICT
     return w
 
 
+MOCR_SYNTH_VOCAB = 96
+
+
+def mocr_synthetic(seed: int = 0):
+    """Seeded stand-in for the manga-ocr model directory when there is no checkpoint: (config dict, state dict, GenerationParams, vocab)
+    of a small ViT + BERT (image 64², patch 16, hidden 128, 2 + 2 layers) run with 4 beams and max_length 24.  The sizes are this
+    project's own choice for a synthetic worker, not those of any published checkpoint."""
+    from . import mocr_schema
+
+    cfg = mocr_schema.tiny_config_dict(image_size=64, hidden=128, heads=4, inter=256, vocab=MOCR_SYNTH_VOCAB, max_pos=32)
+    sd = synth.synth_state_dict(mocr_schema.mocr_schema(mocr_schema.config_from_dict(cfg)), seed=seed)
+    b = sd["decoder.cls.predictions.bias"].clone()
+    b[3] += 6.0   # lines end ([SEP] wins now and then) instead of all running to max_length
+    sd["decoder.cls.predictions.bias"] = sd["decoder.cls.predictions.decoder.bias"] = b
+    gen = mocr_schema.GenerationParams(max_length=24, num_beams=4, no_repeat_ngram_size=3, length_penalty=2.0, early_stopping=True,
+                                       eos_token_id=3, pad_token_id=0, decoder_start_token_id=2)
+    vocab = ["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"] + [chr(0x3042 + i) for i in range(MOCR_SYNTH_VOCAB - 5)]
+    return cfg, sd, gen, vocab
+
+
 def synthetic_stage_weights(stage: str, key: str, seed: int = 0, dict_size: int = DICT_SIZE):
     """The ``weights=`` argument of ONE stage plugin, seeded as ``synthetic_weights`` seeds its three: ``stage`` "detector" | "ocr" |
     "inpainter", ``key`` the reference's name of the model (Detector / Ocr / Inpainter of config.py).  The keys ``synthetic_weights``
@@ -54,6 +74,7 @@ def synthetic_stage_weights(stage: str, key: str, seed: int = 0, dict_size: int 
         ("ocr", "48px"): lambda: sd(ocr_schema.ocr48_schema(dict_size)),
         ("ocr", "48px_ctc"): lambda: sd(ocr_ctc_schema.ocr_ctc_schema(dict_size), ocr_ctc_schema.CTC_GAIN),
         ("ocr", "32px"): lambda: sd(ocr32_schema.ocr32_schema(dict_size)),
+        ("ocr", "mocr"): lambda: {"ocr48": sd(ocr_schema.ocr48_schema(dict_size)), "mocr": mocr_synthetic(seed)[1]},
         ("inpainter", "lama_mpe"): lambda: {"lama.gen": sd(lama_schema.lama_generator_schema(9)), "lama.mpe": sd(lama_schema.lama_mpe_schema())},
         ("inpainter", "lama_large"): lambda: {"lama.gen": sd(lama_schema.lama_generator_schema(18))},
         ("inpainter", "default"): lambda: {"aot": sd(aot_schema.aot_generator_schema())},

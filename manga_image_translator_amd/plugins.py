@@ -660,6 +660,140 @@ class HipModel32pxOCR(HipModel48pxOCR):
         return out
 
 
+MOCR_SUBDIR = "manga-ocr-base"   # <model_dir>/ocr/manga-ocr-base/: config.json (+ generation_config.json), weights, vocab.txt
+MOCR_MAX_LENGTH = 300            # manga_ocr calls model.generate(x[None], max_length=300)
+BERT_SPECIAL_TOKENS = ("[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]")
+
+
+def mocr_tokens_to_text(token_ids: Sequence[int], vocab: Sequence[str], special_ids: Sequence[int] = ()) -> str:
+    """BertTokenizer.decode(ids, skip_special_tokens=True) over ``vocab.txt``: special tokens are skipped, the rest joined with blanks and
+    every ``" ##"`` dropped (convert_tokens_to_string)."""
+    skip = set(int(i) for i in special_ids)
+    toks = [vocab[int(t)] for t in token_ids if int(t) not in skip and vocab[int(t)] not in BERT_SPECIAL_TOKENS]
+    return " ".join(toks).replace(" ##", "").strip()
+
+
+def mocr_post_process(text: str) -> str:
+    """``manga_ocr.ocr.post_process``: the package's own function when it imports; otherwise its whitespace / ellipsis part restated
+    (all whitespace removed, "…" -> "...", runs of "・" / "." -> as many "."), WITHOUT the final half-width -> full-width step
+    (``jaconv.h2z(text, ascii=True, digit=True)``), which needs ``jaconv`` and is applied only when that package imports."""
+    try:
+        from manga_ocr.ocr import post_process  # type: ignore
+
+        return post_process(text)
+    except ImportError:
+        pass
+    import re
+
+    text = "".join(text.split())
+    text = text.replace("…", "...")
+    text = re.sub("[・.]{2,}", lambda x: (x.end() - x.start()) * ".", text)
+    try:
+        import jaconv  # type: ignore
+
+        text = jaconv.h2z(text, ascii=True, digit=True)
+    except ImportError:
+        pass
+    return text
+
+
+def mocr_aggregate(groups: Sequence[Sequence[int]], lines: Dict[int, object]):
+    """model_manga_ocr.py:239-275 for every merged group: ``lines`` holds the 48px results (prob, area, fg_*, bg_*) of the line indices
+    that passed prob >= 0.2.  -> [(prob, (fr, fg, fb), (br, bg, bb))]: prob = exp(sum(log(prob_i) * area_i) / sum(area_i)), or 0.0 without
+    area; each colour the rounded mean over the group's lines, 0 without lines."""
+    out = []
+    for nodes in groups:
+        total_logprobs, total_area = 0, 0
+        cols = [[] for _ in range(6)]
+        for idx in nodes:
+            if idx not in lines:
+                continue
+            r = lines[idx]
+            total_logprobs += np.log(r.prob) * r.area
+            total_area += r.area
+            for acc, name in zip(cols, ("fg_r", "fg_g", "fg_b", "bg_r", "bg_g", "bg_b")):
+                acc.append(getattr(r, name))
+        prob = float(np.exp(total_logprobs / total_area)) if total_area > 0 else 0.0
+        c = [round(np.mean(v)) if v else 0 for v in cols]
+        out.append((prob, tuple(c[:3]), tuple(c[3:])))
+    return out
+
+
+class HipModelMangaOCR(HipModel48pxOCR):
+    """``--ocr mocr`` on the HIP engine (ocr/model_manga_ocr.py:132-295): the 48px model for every line's probability and colours (a line
+    under 0.2 contributes none; its text is discarded), the manga-ocr VisionEncoderDecoderModel (``mocr.MocrEngine``) for the text.
+
+    ``weights``: {"ocr48": 48px state dict, "mocr": state dict in mocr_schema's names}; with them ``dictionary`` (48px), ``vocab``
+    (the lines of vocab.txt), ``mocr_config`` (the config.json dict) and ``generation`` (mocr_schema.GenerationParams).  Without them
+    ``_load`` reads ocr_ar_48px.ckpt + alphabet-all-v7.txt and ``<model_dir>/ocr/manga-ocr-base/``.  ``ocr48``: a loaded
+    ``HipModel48pxOCR`` to share instead of loading the 48px model a second time.
+    ``config.use_mocr_merge = True`` is refused: it needs ``merge_bboxes`` with its own tolerances and a minimum rotated rectangle."""
+    _KEY = _key = "mocr_hip"
+
+    def __init__(self, *args, weights: Optional[Dict[str, Dict[str, torch.Tensor]]] = None, dictionary: Optional[Sequence[str]] = None,
+                 vocab: Optional[Sequence[str]] = None, mocr_config: Optional[Dict] = None, generation=None, ocr48=None, **kwargs):
+        self._ocr48_weights = None if weights is None else weights.get("ocr48")
+        self._shared48 = ocr48
+        super().__init__(*args, weights=None if weights is None else weights.get("mocr"), dictionary=dictionary, **kwargs)
+        self.vocab, self.mocr_config, self.generation = vocab, mocr_config, generation
+        have48 = ocr48 is not None or (self._ocr48_weights is not None and dictionary is not None)
+        self._downloaded = self._downloaded if weights is None else all(g is not None for g in (self._weights, vocab, mocr_config, generation)) and have48
+
+    async def _load(self, device: str):
+        from . import mocr, mocr_schema
+
+        dev = _gpu_device(device)
+        if self._shared48 is not None:
+            self.ocr48 = self._shared48
+        else:
+            self.ocr48 = HipModel48pxOCR(weights=self._ocr48_weights, dictionary=self.dictionary if self._ocr48_weights is not None else None)
+        if not self.ocr48.is_loaded():
+            await self.ocr48.load(device)
+        if self._weights is None:
+            self._weights, self.mocr_config, self.generation, self.vocab = _load_mocr_checkpoint(self)
+        self.engine = mocr.MocrEngine(self._weights, self.mocr_config, self.generation, device=dev)
+        if len(self.vocab) != self.engine.cfg.vocab:
+            raise ValueError(f"vocab.txt has {len(self.vocab)} lines, the model's vocabulary is {self.engine.cfg.vocab}")
+        self.device = device
+
+    async def _unload(self):
+        await super()._unload()
+        if self._shared48 is None and getattr(self, "ocr48", None) is not None:
+            await self.ocr48.unload()
+
+    @torch.no_grad()
+    async def _infer(self, image: np.ndarray, textlines: List, config=None, verbose: bool = False, ignore_bubble: int = 0):
+        """Sets text / prob / fg_* / bg_* on the same Quadrilateral objects and returns ALL of them in processing order, as the reference
+        does (no threshold on the result: a line under 0.2 in the 48px model keeps its text with prob 0.0 and black colours)."""
+        if config is not None and getattr(config, "use_mocr_merge", False):
+            raise ValueError("ocr.use_mocr_merge = True is not implemented by the HIP mocr plugin (supported: use_mocr_merge = False)")
+        quads, dirs, own = self._prepare(textlines)
+        if not quads:
+            return []
+        # the 48px pass (:164-237): fixed 0.2 threshold, max_seq_length 255, no ignore_bubble
+        accepted = await self.ocr48._infer(image, quads, None, verbose, 0, 255)
+        passed = {id(q) for q in accepted}
+        lines = {i: _own_stats(q, own[i]) for i, q in enumerate(quads) if id(q) in passed}
+        r = self.engine.recognize_lines(self._page_on_device(image), own, dirs)
+        toks, lens = r["tokens"].cpu().numpy(), r["length"].cpu().numpy()
+        g = self.engine.generation
+        special = [t for t in (g.eos_token_id, g.pad_token_id, g.decoder_start_token_id) if t is not None]
+        agg = mocr_aggregate([[i] for i in range(len(quads))], lines)
+        out = []
+        for i, (q, (prob, fgc, bgc)) in enumerate(zip(quads, agg)):
+            txt = mocr_post_process(mocr_tokens_to_text(toks[i, :int(lens[i])], self.vocab, special))
+            q.assigned_direction = dirs[i]
+            out.append(_accept(q, txt, prob, fgc, bgc))
+        return out
+
+
+def _own_stats(q, own):
+    """What the aggregation reads of a line that passed the 48px threshold: its probability and colours, and the area of its quad."""
+    import types
+
+    return types.SimpleNamespace(prob=q.prob, area=own.area, fg_r=q.fg_r, fg_g=q.fg_g, fg_b=q.fg_b, bg_r=q.bg_r, bg_g=q.bg_g, bg_b=q.bg_b)
+
+
 def decode_32px_line(tokens, colour_history, dictionary: Sequence[str]) -> Tuple[str, Tuple[int, int, int], Tuple[int, int, int]]:
     """Tokens (start symbol included) + the six colour heads over the hypothesis's output history [len, 6] -> (text, fg rgb, bg rgb):
     model_32px.py:104-120.  Each colour is ``(clip(head, 0, 1).mean() * 255)`` truncated, in float32 like the reference, over every
@@ -1278,6 +1412,33 @@ def _load_ocr32_checkpoint(plugin):
     return synth.check_state_dict(sd, ocr32_schema.ocr32_schema(len(dictionary)), "ocr.ckpt"), dictionary
 
 
+def _load_mocr_checkpoint(plugin):
+    """``<model_dir>/ocr/manga-ocr-base/``: config.json (+ generation_config.json), the weights and vocab.txt -> (state dict, config dict,
+    GenerationParams, vocab).  When ``transformers`` imports the weights go through ``VisionEncoderDecoderModel.from_pretrained(dir,
+    local_files_only=True)``, so that the key names of older checkpoints are converted by HuggingFace itself; otherwise
+    ``pytorch_model.bin`` (or ``model.safetensors`` when ``safetensors`` imports) must already hold mocr_schema's names.
+    ``max_length`` is the 300 manga_ocr passes to ``generate``."""
+    from . import mocr_schema, synth
+
+    d = _ckpt_path(plugin, MOCR_SUBDIR)
+    cfg, c, gen = mocr_schema.load_model_dir(d, max_length=MOCR_MAX_LENGTH)
+    with open(os.path.join(d, "vocab.txt"), "r", encoding="utf-8") as fp:
+        vocab = [s.rstrip("\n") for s in fp.readlines()]
+    try:
+        from transformers import VisionEncoderDecoderModel  # type: ignore
+    except ImportError:
+        VisionEncoderDecoderModel = None
+    if VisionEncoderDecoderModel is not None:
+        sd = VisionEncoderDecoderModel.from_pretrained(d, local_files_only=True).state_dict()
+    elif os.path.exists(os.path.join(d, "pytorch_model.bin")):
+        sd = torch.load(os.path.join(d, "pytorch_model.bin"), map_location="cpu")
+    else:
+        from safetensors.torch import load_file  # type: ignore
+
+        sd = load_file(os.path.join(d, "model.safetensors"))
+    return synth.check_state_dict(sd, mocr_schema.mocr_schema(c, pooler=False), MOCR_SUBDIR), cfg, gen, vocab
+
+
 def _load_lama_checkpoint(plugin):
     """{'gen_state_dict', 'str_state_dict'?} (inpainting_lama_mpe.py:818-825)."""
     from . import lama_schema, synth
@@ -1354,7 +1515,7 @@ def register() -> None:
     for reg, enum_name, cls in ((DETECTORS, "Detector", HipComicTextDetector), (DETECTORS, "Detector", HipDefaultDetector),
                                 (DETECTORS, "Detector", HipDBConvNextDetector),
                                 (OCRS, "Ocr", HipModel48pxOCR), (OCRS, "Ocr", HipModel48pxCTCOCR),
-                                (OCRS, "Ocr", HipModel32pxOCR),
+                                (OCRS, "Ocr", HipModel32pxOCR), (OCRS, "Ocr", HipModelMangaOCR),
                                 (INPAINTERS, "Inpainter", HipLamaMPEInpainter), (INPAINTERS, "Inpainter", HipLamaLargeInpainter),
                                 (INPAINTERS, "Inpainter", HipAotInpainter),
                                 (UPSCALERS, "Upscaler", HipESRGANUpscaler), (COLORIZERS, "Colorizer", HipMangaColorizer)):

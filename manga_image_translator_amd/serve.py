@@ -91,6 +91,8 @@ SUPPORTED_STAGE_KEYS = {                                      # (section, field)
     ("ocr", "ocr"): ("48px", "48px_ctc", "32px"),
     ("inpainter", "inpainter"): ("lama_large", "lama_mpe", "default"),
 }
+# what a caller of ``stage_keys`` accepts beside them when it says so (``mocr=True``): a config-mode worker always does
+OPTIONAL_STAGE_KEYS = {("ocr", "ocr"): ("mocr",)}
 DETECTOR_FILTER_OPTIONS = ("det_rotate", "det_auto_rotate", "det_invert", "det_gamma_correct")   # DetectorConfig, config.py:280-286
 
 
@@ -110,21 +112,25 @@ def detector_filter_options(config) -> Tuple[bool, bool, bool, bool]:
     return tuple(bool(_field(det, opt)) for opt in ("det_invert", "det_gamma_correct", "det_rotate", "det_auto_rotate"))
 
 
-def stage_keys(config, detector_filters: bool = False) -> Tuple[str, str, str]:
+def stage_keys(config, detector_filters: bool = False, mocr: bool = False) -> Tuple[str, str, str]:
     """(detector, ocr, inpainter) a request's ``Config`` names: ``config.detector.detector``, ``config.ocr.ocr``,
     ``config.inpainter.inpainter``, each the reference's default where the field (or its section, or the config) is absent.  Raises
     ValueError, naming the key and the supported set, for a model this worker has no HIP plugin for (craft, paddle, none, mocr, sd,
     original, …) and for a detector filter option that is set (rotate / auto-rotate / invert / gamma-correct run inside the reference's
     ``CommonDetector.detect``, which the worker does not go through): a request is never served by something else silently.
     ``detector_filters``: the worker goes through the plugins' ``detect`` (``DenseStages(params={"detector_filters": True})``), so the
-    four options are served and accepted."""
+    four options are served and accepted.  ``mocr``: the caller has the manga-ocr plugin, so ``ocr.ocr = "mocr"``
+    (``OPTIONAL_STAGE_KEYS``) is accepted too — every ``DenseStages`` in "config" mode passes it; the bare call keeps the set it had."""
     cfg = _as_dict(config)
     out = []
     for (section, name), default in zip(SUPPORTED_STAGE_KEYS, DEFAULT_STAGE_KEYS):
         v = _field(cfg.get(section), name)
         v = default if v is None else str(v)
-        if v not in SUPPORTED_STAGE_KEYS[(section, name)]:
-            raise ValueError(f"{section}.{name} = {v!r} is not served by this worker (supported: {', '.join(SUPPORTED_STAGE_KEYS[(section, name)])})")
+        optional = OPTIONAL_STAGE_KEYS.get((section, name), ())
+        if v not in SUPPORTED_STAGE_KEYS[(section, name)] and not (mocr and v in optional):
+            extra = "" if mocr or not optional else f"; {', '.join(optional)} with stage_keys(..., mocr=True), as a config-mode worker calls it"
+            served = SUPPORTED_STAGE_KEYS[(section, name)] + (optional if mocr else ())
+            raise ValueError(f"{section}.{name} = {v!r} is not served by this worker (supported: {', '.join(served)}{extra})")
         out.append(v)
     for opt in DETECTOR_FILTER_OPTIONS:
         if not detector_filters and _field(cfg.get("detector"), opt):
@@ -235,7 +241,7 @@ class DenseStages:
     def _select(self, config) -> Tuple[str, str, str]:
         """The stages that serve a request with this config — ``FIXED_STAGE_KEYS`` in "fixed" mode, ``stage_keys(config)`` in
         "config" mode — noted for ``_load`` (which brings ``self.det`` / ``self.ocr`` / ``self.inp`` to them) and in ``last_stage_keys``."""
-        self._keys = stage_keys(config, self.detector_filters) if self.stages == "config" else FIXED_STAGE_KEYS
+        self._keys = stage_keys(config, self.detector_filters, mocr=True) if self.stages == "config" else FIXED_STAGE_KEYS
         self._colorizer_options(config)     # an unknown colorizer is refused here, with the other stage names
         self.last_stage_keys = self._keys
         return self._keys
@@ -247,18 +253,22 @@ class DenseStages:
 
         classes = {("detector", "ctd"): P.HipComicTextDetector, ("detector", "default"): P.HipDefaultDetector,
                    ("detector", "dbconvnext"): P.HipDBConvNextDetector, ("ocr", "48px"): P.HipModel48pxOCR,
-                   ("ocr", "48px_ctc"): P.HipModel48pxCTCOCR, ("ocr", "32px"): P.HipModel32pxOCR,
+                   ("ocr", "48px_ctc"): P.HipModel48pxCTCOCR, ("ocr", "32px"): P.HipModel32pxOCR, ("ocr", "mocr"): P.HipModelMangaOCR,
                    ("inpainter", "lama_mpe"): P.HipLamaMPEInpainter, ("inpainter", "lama_large"): P.HipLamaLargeInpainter,
                    ("inpainter", "default"): P.HipAotInpainter}
         got = []
         for stage, key in zip(("detector", "ocr", "inpainter"), self._keys):
             if (stage, key) not in self._plugins:
+                shared = {"ocr48": self._plugins[("ocr", "48px")]} if (stage, key) == ("ocr", "mocr") and ("ocr", "48px") in self._plugins else {}
                 if self.params.get("model_dir"):
-                    p = classes[(stage, key)]()
+                    p = classes[(stage, key)](**shared)
                 else:
                     d = int(self.params.get("dict_size", 512))
                     w = pipeline.synthetic_stage_weights(stage, key, dict_size=d)
                     kw = {"dictionary": ["<PAD>", "<S>", "</S>", "<SP>"] + [chr(0x4E00 + i) for i in range(d - 4)]} if stage == "ocr" else {}
+                    if (stage, key) == ("ocr", "mocr"):   # the 48px model (shared where loaded) + the seeded stand-in of the model directory
+                        mcfg, _, mgen, mvocab = pipeline.mocr_synthetic()
+                        kw.update(vocab=mvocab, mocr_config=mcfg, generation=mgen, **shared)
                     p = classes[(stage, key)](weights=w, **kw)
                 await p.load("cuda")
                 self._plugins[(stage, key)] = p
@@ -348,6 +358,7 @@ class DenseStages:
         class _Cfg:   # OcrConfig.prob (config.py): None unless the request sets it — the plugin then keeps the reference's 0.2 (model_48px.py:104)
             prob = None if ocr.get("prob") is None else float(ocr["prob"])
             ignore_bubble = int(ocr.get("ignore_bubble", 0) or 0)     # (the ctc and 32px plugins read it from the config)
+            use_mocr_merge = bool(ocr.get("use_mocr_merge", False))   # (refused by the mocr plugin when set)
 
         steps = int(ocr.get("max_seq_length", 255))
         if keys[1] == "48px":
@@ -357,6 +368,9 @@ class DenseStages:
                 raise ValueError(f"ocr.suppress_eos is set, and ocr.ocr = {keys[1]!r} has no such option (supported: ocr.ocr = '48px')")
             if keys[1] == "48px_ctc" and ocr.get("max_seq_length") is not None:
                 raise ValueError("ocr.max_seq_length is set, and ocr.ocr = '48px_ctc' has no step limit (supported: ocr.ocr = '48px', '32px')")
+            if keys[1] == "mocr" and ocr.get("max_seq_length") is not None:
+                raise ValueError("ocr.max_seq_length is set, and ocr.ocr = 'mocr' takes its length limit from the model's generation config "
+                                 "(supported: ocr.ocr = '48px', '32px')")
             ocr_args = (_Cfg(), False) + ((steps,) if keys[1] == "32px" else ())
         lines = await self.ocr.infer(page, tls, *ocr_args) if tls else []
         lines = [l for l in lines if l.text.strip()]
